@@ -24,6 +24,10 @@ failed.  Under an outer `torchrun` (WORLD_SIZE set) it is one of the ranks, as b
 `collective_backend`, the weak value and `strong_config2`.
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+
+`--dump-outputs DIR`: what the last timed launch computed -- the arrays a caller of K4 receives (x, the updated z and logl, the
+accept / call counts, the moved flags, the final scales; under a process group also the gathered endpoints) -- is written as
+DIR/<name>.npy (float32 / float64), so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -223,6 +227,26 @@ def logz_report(dev, live_run):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each host array as <path>/<name>.npy; float32 / float64 kept, counts and flags as float64 (exact).  Past
+    DUMP_MAX_BYTES in all, every array keeps the same fraction of its rows, drawn with a fixed seed, and <name>_rows.npy says which."""
+    arrays = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in arrays.items()}
+    budget = DUMP_MAX_BYTES - (1 << 20)   # (1 MB left for the .npy headers)
+    sample = sum(a.nbytes for a in arrays.values()) > budget
+    with_index = sum(a.nbytes + 8 * a.shape[0] for a in arrays.values() if a.ndim >= 1)   # (a sampled row also costs its index)
+    os.makedirs(path, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        if sample and a.ndim >= 1 and a.shape[0] > 1:
+            k = max(1, a.shape[0] * budget // with_index)
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], k, replace=False))
+            np.save(os.path.join(path, name + '_rows.npy'), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a))
+
+
 def launch_ranks(n, argv, timeout_s=1800.0):
     """`--gpus n` without an outer launcher: n fresh child processes, one per GPU (never an exec of a process that has touched
     a GPU: the parent has not), rank 0's stdout relayed.  ALL children are polled: the first one that exits non-zero is named, its
@@ -325,7 +349,11 @@ def main():
     ap.add_argument('--no-logz', action='store_true', help='skip the live nested run (the fixtures are still reported)')
     ap.add_argument('--bare', action='store_true', help='the timed launches only (profiling runs: scripts/profile_bench.sh)')
     ap.add_argument('--launch-timeout', type=float, default=1800.0, help='--gpus N launcher: seconds before the ranks are stopped')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed launch computed as DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1 (the number of timed launches)')
     if args.bare:
         args.no_cpu_baseline = args.no_saturation = args.no_spline = args.no_logz = True
 
@@ -420,6 +448,14 @@ def main():
         ev1[k].record()
     barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:   # copied off the device now: the launches below reuse the state buffers
+        i_last = args.warmup + args.steps - 1
+        dumped = {'x': last['x'], 'z': zs[i_last], 'logl': ls[i_last], 'n_accept': last['n_accept'], 'n_call': last['n_call'],
+                  'moved': last['moved'], 'scale': last['scale']}
+        if gathered is not None:
+            dumped['gathered'] = gathered
+        dumped = {k: v.detach().cpu().numpy() for k, v in dumped.items()}
     # (first 20 timed launches, start of the first to end of the twentieth on the device's clock: no host sync inside the region)
     n20 = min(20, args.steps)
     dt_first20 = ev0[0].elapsed_time(ev1[n20 - 1]) / n20 if n20 else None
@@ -757,6 +793,8 @@ def main():
                 out['e2e'] = out['logz'].pop('e2e')   # (the wall-time split of the live run: a top-level object)
         if not args.no_cpu_baseline and world == 1 and dist is None:
             out['cpu_baseline'] = cpu_baseline(D, nvp.store_packed(), like, scale, C)
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Generate the golden fixtures under tests/golden/ by RUNNING the upstream reference.
 
-Test infrastructure, run in the build container only:  python oracle/gen_golden.py
-The reference (/root/reference, adammoss/nnest v0.4.2) is imported unmodified through
+Test infrastructure:  NNEST_REFERENCE=<checkout of the reference> python oracle/gen_golden.py
+The reference (adammoss/nnest v0.4.2) is imported unmodified through
 oracle/_refimport.py.  Only plain arrays (inputs + the reference's outputs) are written;
 no reference source, bytecode or pickled module goes into the fixtures.
 

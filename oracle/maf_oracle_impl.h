@@ -2,7 +2,7 @@
  * ORACLE -- TEST INFRASTRUCTURE ONLY.  Not part of the product path.
  *
  * Masked autoregressive flow (MAF).  [UNPINNED: absent from the reference -- nnest/trainer.py:83-100
- * accepts only 'choleksy' / 'nvp' / 'spline'; nothing in /root/reference to check against.  Build-defined; validated by
+ * accepts only 'choleksy' / 'nvp' / 'spline'; nothing in the reference to check against.  Build-defined; validated by
  * self-consistency: round trip, log-det antisymmetry, log-det against a brute-force Jacobian (the reference's own check of
  * its flows, nnest/trainer.py:373-382 / tests/test_flows.py:27-30), staged inverse == one-dimension-at-a-time inverse,
  * analytic gradient == finite differences.]

@@ -3,7 +3,7 @@
  *
  * CPU restatement (plain C) of the nnest hot path, one function per reference
  * function, each citing the reference file:line it follows (paths relative to
- * /root/reference, adammoss/nnest v0.4.2).  Only tests/, __graft_entry__.smoke()
+ * adammoss/nnest v0.4.2).  Only tests/, __graft_entry__.smoke()
  * and bench.py's cpu_baseline leg may load this.
  *
  * This header is included twice by nnest_oracle.c with

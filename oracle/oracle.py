@@ -3,7 +3,7 @@
 Importable by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg only; the product
 package nnest_amd/ never imports it.  Parity status: PINNED (tests/test_oracle_golden.py checks
 every function below against fixtures produced by running the reference, tests/golden/).
-Each method names the reference function it restates (paths under /root/reference).
+Each method names the reference function it restates (paths in adammoss/nnest v0.4.2).
 """
 import os
 import ctypes

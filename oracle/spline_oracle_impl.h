@@ -2,7 +2,7 @@
  * ORACLE -- TEST INFRASTRUCTURE ONLY.  Not part of the product path.
  *
  * CPU restatement (plain C) of the reference's neural-spline flow, SingleSpeedSpline
- * (nnest/networks.py:393-715, adammoss/nnest v0.4.2; paths relative to /root/reference):
+ * (nnest/networks.py:393-715, adammoss/nnest v0.4.2; paths relative to its root):
  *     per block:  ActNorm (:661-705)  ->  Invertible1x1Conv (:625-658)  ->  NSF_CL (:559-622)
  * NSF_CL = two rational-quadratic-spline couplings (Durkan et al. 2019) over the contiguous halves of the vector,
  * each conditioned by a 4-layer LeakyReLU(0.2) MLP (:393-409).
