@@ -1170,8 +1170,7 @@ hipError_t spline_rows_update(nnest_spline *h, const SplTrainShape &ts, const Sp
     }
     if (e != hipSuccess) return e;
     const dim3 grid(s.B + (a.n_jobs + 1 + 15) / 16);
-    static const bool s32 = getenv("NNEST_SPLR_STEPS32") != nullptr;   // (diagnostic)
-    if (u.M <= 104 && !s32) hipLaunchKernelGGL(splr_update_kernel<26>, grid, dim3(1024), ldsb, st, a);
+    if (u.M <= 104) hipLaunchKernelGGL(splr_update_kernel<26>, grid, dim3(1024), ldsb, st, a);
     else hipLaunchKernelGGL(splr_update_kernel<32>, grid, dim3(1024), ldsb, st, a);
     return hipGetLastError();
 }

@@ -1798,10 +1798,9 @@ static hipError_t launch_grad(const SplGradArgs &a_in, hipStream_t st) {
     const int per_wave = ((16 * (a.ts.s.D + 1) + SPL_TBATCH * 16 * 17) + 3) & ~3;
     size_t ldsb = (size_t)(SPL_TEAM * per_wave + 2 * SPL_TEAM * (a.ts.s.NTh + a.ts.s.NH) * 64 * 4 + SPL_TEAM * 16) * sizeof(float);
     // the blocks' conv fragments and ActNorm vectors in LDS where they fit (x_dim 50, three blocks: 48 + 12 KB on top of 61 KB)
-    static const bool heads_off = [] { const char *e = getenv("NNEST_SPL_LDS_HEADS"); return e && !strcmp(e, "0"); }();   // (diagnostic)
     const int T2 = 2 * a.ts.s.NTh;
     const size_t heads_b = (size_t)a.ts.s.B * (T2 * T2 * 256 + 4 * a.ts.s.NTh * 64 * 4) * sizeof(float);
-    a.lds_heads = (!heads_off && T2 <= SPL_TEAM && ldsb + heads_b <= (size_t)156 * 1024) ? 1 : 0;
+    a.lds_heads = (T2 <= SPL_TEAM && ldsb + heads_b <= (size_t)156 * 1024) ? 1 : 0;
     if (a.lds_heads) ldsb += heads_b;
     DISPATCH_SPLT(spl_grad_kernel, a.ts.s, tiles + a.val_tiles, 64 * SPL_TEAM, ldsb, st, a);
     return hipGetLastError();

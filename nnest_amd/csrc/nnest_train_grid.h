@@ -50,9 +50,6 @@ __device__ __forceinline__ void st_sc1(float *p, float v) { __hip_atomic_store(p
 // expected spread makes it the only one.
 __device__ __forceinline__ bool grid_barrier(unsigned int *ctr, int &phase, int G, int *err, int first_poll_sleep = 0) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores (incl. the asm ones the compiler does not count)
-#ifdef GRID_FENCE
-    __threadfence();
-#endif
     __syncthreads();
     phase += 1;
     __shared__ int ok;
@@ -71,9 +68,6 @@ __device__ __forceinline__ bool grid_barrier(unsigned int *ctr, int &phase, int 
         ok = good;
     }
     __syncthreads();
-#ifdef GRID_FENCE
-    __threadfence();
-#endif
     return ok != 0;
 }
 
@@ -943,8 +937,7 @@ static size_t grid_workspace_floats(const FlowShape &s) {
     return (size_t)s.B * 2 * CT * TRAIN_MAX_ROWS * 16 + (size_t)2 * s.B * 2 * NJOBS * 256 + (size_t)s.num_params() + 64 + 16 + 64 +
            (size_t)s.num_params() /* dead list */ +
            (size_t)GRID_WG * TRAIN_WAVES * 64 * 32 + 64 /* owners' records */ + (size_t)3 * (s.num_params() + 64) + 128 /* dead state */ +
-           (size_t)2 * (s.image_floats + 64) + 64 /* the published images */ +
-           (size_t)2 * s.B * 2 * CT * TRAIN_MAX_ROWS * 16 + 192 /* train_kernel_pipe's tagged staging area */;
+           (size_t)2 * (s.image_floats + 64) + 64 /* the published images */;
 }
 
 static hipError_t dispatch_train_grid(const TrainArgs &a, float *gridws, hipStream_t st) {
