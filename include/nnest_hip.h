@@ -332,6 +332,25 @@ int nnest_spline_mh_constrained_steps(nnest_spline_t *spl, const nnest_like_t *l
 enum { NNEST_SPLINE_MH_WAVE = 0, NNEST_SPLINE_MH_TEAM = 1, NNEST_SPLINE_MH_PAIR = 2 };
 int nnest_spline_mh_form_for(const nnest_spline_t *spl, int C, int flags);
 
+/* SLICE proposal in latent space with the spline flow: the definition, streams and counters of nnest_slice_steps (BUILD-DEFINED,
+ * parity unpinned: the reference has no slice proposal; held to oracle/oracle.py::slice_sample) with the spline's inverse and
+ * log-det in place of the NVP's.  Arguments as nnest_slice_steps; n_call_dev, n_move_dev, n_eval_dev may each be NULL.  The
+ * directions are the ones nnest_slice_fill_noise exports.  Kernel forms as the spline proposal kernel's: 16 walkers per wave,
+ * four waves per 16 walkers, four waves per 8 walkers held twice (x_dim > 32); walkers are not held in step (each evaluates its
+ * own next candidate in every round of the tile; one that has finished idles), so any C, no resident-grid requirement.  flags:
+ * bits 0..3 pin a form, NNEST_SPLINE_SLICE_FORM(NNEST_SPLINE_MH_WAVE / _TEAM / _PAIR), 0 = NNEST_SPLINE_SLICE_AUTO lets the
+ * library choose; the forms agree to float32 rounding.  Shapes: those of nnest_spline_mh_constrained_steps (hidden 16 up to
+ * x_dim 128, hidden 32 up to x_dim 64); NNEST_E_UNSUPPORTED for a pinned form the shape lacks.  (Added within ABI 15.) */
+enum { NNEST_SPLINE_SLICE_AUTO = 0 };
+#define NNEST_SPLINE_SLICE_FORM(f) (((f) + 1) & 15)
+int nnest_spline_slice_steps(nnest_spline_t *spl, const nnest_like_t *like, float *z_dev, float *x_dev, double *logl_dev,
+                             double loglstar, float width, int steps, int C, int max_stepout, int max_shrink, int flags,
+                             const float *noise_dz_dev, uint64_t seed, uint64_t walker_offset, float *hist_x_dev, int *n_call_dev,
+                             int *n_move_dev, int *n_eval_dev, void *stream);
+/* The form (NNEST_SPLINE_MH_WAVE / _TEAM / _PAIR) nnest_spline_slice_steps runs for C walkers under `flags`, -1 if it would refuse
+ * the launch.  (Added within ABI 15.) */
+int nnest_spline_slice_form_for(const nnest_spline_t *spl, int C, int flags);
+
 /* Training.  ActNorm's data-dependent initialisation (networks.py:698-705): s = -log std(x) (unbiased), t = -mean(x e^s)
  * block after block from the batch x_dev [N,D] -- in the reference this happens inside the first forward pass of a
  * fresh model, which under Trainer.train is the first (jittered) minibatch. */

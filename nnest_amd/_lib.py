@@ -111,6 +111,8 @@ SIGNATURES = {
     'nnest_mh_sync_words': [_i],
     'nnest_mh_form_for': [_vp, _i, _i],
     'nnest_spline_mh_form_for': [_vp, _i, _i],
+    'nnest_spline_slice_form_for': [_vp, _i, _i],
+    'nnest_spline_slice_steps': [_vp, _vp, _vp, _vp, _vp, _d, _f, _i, _i, _i, _i, _i, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp],
     'nnest_spline_train_form': [_vp, _i],
     'nnest_spline_forward': [_vp, _vp, _vp, _vp, _i, _vp],
     'nnest_spline_inverse': [_vp, _vp, _vp, _vp, _i, _vp],

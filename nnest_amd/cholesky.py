@@ -37,6 +37,12 @@ class HipCholesky(_HipFlow):
         except Exception:
             pass
 
+    def slice_steps(self, *args, **kwargs):
+        """the slice proposal exists for the NVP (nnest_slice_steps) and the spline flow (HipSpline.slice_steps) only: the
+        inherited method would hand this handle to the NVP's entry point"""
+        raise NotImplementedError("mcmc_proposal='slice' is not implemented for the Cholesky flow (flow='choleksy'); "
+                                  "use flow='nvp' or flow='spline'")
+
     def layer_shapes(self):
         D = self.D
         return [('flow.flows.0.bias', (D,)), ('flow.flows.0.lower_entries', (D * (D - 1) // 2,)), ('flow.flows.0.unconstrained_diag', (D,))]

@@ -44,6 +44,11 @@ struct SplArgs {
 hipError_t launch_spline_mh_pair(const MhArgs &a, const SplArgs &q, bool dbg, hipStream_t st);   // nnest_spline_mh.hip
 hipError_t launch_spline_mh_team(const MhArgs &a, const SplArgs &q, bool dbg, hipStream_t st);   // nnest_spline_mh.hip
 int spline_mh_form(const SplineShape &sp, int C, int flags, int num_cu);   // spline_kernels.h
+int spline_slice_form(const SplineShape &sp, int C, int flags, int num_cu);   // nnest_spline_slice.hip
+hipError_t launch_spline_slice(const float *img, const SplineShape &sp, const LikeSpec &like, float *z, float *x, double *logl,
+                               double loglstar, float width, int steps, int C, int max_out, int max_shrink, int flags,
+                               const float *noise_dz, uint64_t seed, uint64_t walker_offset, float *hist_x, int *n_call, int *n_move,
+                               int *n_eval, int num_cu, hipStream_t st);   // nnest_spline_slice.hip
 bool spline_shape_supported(const SplineShape &s);
 hipError_t launch_spline_pass(const float *img, const SplineShape &sp, int mode, const float *in, float *out, float *logdet,
                               double *logl, int *inbox, int N, const LikeSpec &like, int num_cu, hipStream_t st);

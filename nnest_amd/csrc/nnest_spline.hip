@@ -352,4 +352,30 @@ int nnest_spline_mh_constrained_steps(nnest_spline_t *h, const nnest_like_t *lik
     return NNEST_OK;
 }
 
+int nnest_spline_slice_form_for(const nnest_spline_t *h, int C, int flags) {
+    if (!h || C <= 0 || (flags & ~15)) return -1;
+    return spline_slice_form(h->s, C, flags, h->num_cu);
+}
+
+int nnest_spline_slice_steps(nnest_spline_t *h, const nnest_like_t *like, float *z_dev, float *x_dev, double *logl_dev, double loglstar,
+                             float width, int steps, int C, int max_stepout, int max_shrink, int flags, const float *noise_dz_dev,
+                             uint64_t seed, uint64_t walker_offset, float *hist_x_dev, int *n_call_dev, int *n_move_dev, int *n_eval_dev,
+                             void *stream) {
+    int rc = scheck_rows(h, z_dev, logl_dev, C);
+    if (rc) return rc;
+    LikeSpec lk;
+    if ((rc = scheck_like(like, h->s.D, &lk))) return rc;
+    if (steps < 0 || max_stepout < 0 || max_shrink < 1 || max_shrink > 60 || !(width > 0.f))
+        return spline_fail(NNEST_E_ARG, "steps=%d max_stepout=%d max_shrink=%d (1..60) width=%g", steps, max_stepout, max_shrink, (double)width);
+    if (flags & ~15) return spline_fail(NNEST_E_ARG, "flags=0x%x: bits 0..3 only (NNEST_SPLINE_SLICE_FORM)", flags);
+    if (C > 0 && spline_slice_form(h->s, C, flags, h->num_cu) < 0)
+        return spline_fail(NNEST_E_UNSUPPORTED, "spline slice proposal: form %d pinned, x_dim=%d (the pair form needs x_dim > 32)", (flags & 15) - 1, h->s.D);
+    hipError_t e = launch_spline_slice(h->img, h->s, lk, z_dev, x_dev, logl_dev, loglstar, width, steps, C, max_stepout, max_shrink, flags,
+                                       noise_dz_dev, seed, walker_offset, hist_x_dev, n_call_dev, n_move_dev, n_eval_dev, h->num_cu,
+                                       (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return spline_fail(NNEST_E_UNSUPPORTED, "spline slice proposal: x_dim=%d hidden_dim=%d not instantiated", h->s.D, h->s.H);
+    if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_slice: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
 }  // extern "C"

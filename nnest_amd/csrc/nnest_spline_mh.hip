@@ -29,36 +29,7 @@
 namespace nnest {
 
 #include "mh_body.h"
-
-template <int NT, int NH>
-struct SplineInverseHalves {
-    const float *img;
-    SplineShape sp;
-    float *buf;     // this wave's 16 x (D+1) layout-exchange buffer
-    f32x4 *xch;     // 2 x [4][NT][64]: the exchanges alternate between the two (one barrier each, round 6)
-    float *ldred;   // 2 x [4][16], likewise
-    const float *trunks;   // the conditioners' hidden parts in LDS (spline_stage_trunks)
-    int lane, wv;
-    mutable int xsel = 0, lsel = 0;
-#ifdef NNEST_STAMP
-    unsigned long long t_mlp = 0, t_xch = 0, t_upd = 0;
-#endif
-    __device__ __forceinline__ float operator()(f32x4 (&xs)[2][NT]) const {
-        f32x4 t[2][NT];
-        spl_from_parity<NT>(buf, sp.D, sp.nl, lane, xs, t);
-        float ld = group_sum(spline_inverse_tile_halves<NT, NH>(img, sp, lane, t, wv, xch, xsel, trunks));
-        float *lr = ldred + ((lsel & 1) ? 64 : 0);
-        lsel ^= 1;
-        if (lane < 16) lr[wv * 16 + lane] = ld;
-        spl_team_barrier();
-        const int w = lane & 15;
-        ld = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) ld += lr[k * 16 + w];
-        spl_to_parity<NT>(buf, sp.D, sp.nl, lane, t, xs);
-        return 0.25f * ld;  // the caller sums the four lanes of a walker
-    }
-};
+#include "spline_inverse.h"   // SplineInverseHalves, SplineInverseTeam
 
 template <int NT, int NH, bool DBG>
 __global__ void __launch_bounds__(256) spline_mh_kernel_pair(MhArgs a, SplArgs q) {
@@ -80,33 +51,6 @@ __global__ void __launch_bounds__(256) spline_mh_kernel_pair(MhArgs a, SplArgs q
 // Team form for small populations (fewer walker tiles than CUs): one workgroup of four waves per tile.  All four carry the
 // same proposal state (same noise streams, same decisions); only the spline evaluations of the flow inverse are divided
 // (spl_coupling TEAM = 4), and the log-det partials are summed through LDS.  Wave 0 writes the results.
-template <int NT, int NH, int TEAM>
-struct SplineInverseTeam {
-    const float *img;
-    SplineShape sp;
-    float *buf;     // this wave's 16 x (D+1) layout-exchange buffer
-    f32x4 *xch;     // [TEAM][NT][64]
-    float *ldred;   // [TEAM][16]
-    int lane, wv;
-#ifdef NNEST_STAMP
-    unsigned long long t_mlp = 0, t_xch = 0, t_upd = 0;
-#endif
-    __device__ __forceinline__ float operator()(f32x4 (&xs)[2][NT]) const {
-        f32x4 t[2][NT];
-        spl_from_parity<NT>(buf, sp.D, sp.nl, lane, xs, t);
-        float ld = group_sum(spline_inverse_tile<NT, NH, TEAM>(img, sp, lane, t, wv, xch));
-        if (lane < 16) ldred[wv * 16 + lane] = ld;
-        spl_team_barrier();
-        const int w = lane & 15;
-        ld = 0.f;
-#pragma unroll
-        for (int k = 0; k < TEAM; ++k) ld += ldred[k * 16 + w];
-        spl_team_barrier();
-        spl_to_parity<NT>(buf, sp.D, sp.nl, lane, t, xs);
-        return 0.25f * ld;  // the caller sums the four lanes of a walker
-    }
-};
-
 template <int NT, int NH, int TEAM, bool DBG>
 __global__ void __launch_bounds__(64 * TEAM) spline_mh_kernel_team(MhArgs a, SplArgs q) {
     extern __shared__ __attribute__((aligned(16))) float lds_buf[];

@@ -13,6 +13,7 @@
 // read from global memory / L2: every fragment load is one coalesced 256-byte line per wave.
 #pragma once
 #include "spline_train_tile.h"   // (already in at file scope: the fragment-prefetch helpers and the paired coupling of the 8-walker form)
+#include "spline_inverse.h"      // SplineInverse
 
 // (struct SplArgs: nnest_internal.h)
 
@@ -57,24 +58,6 @@ __global__ void __launch_bounds__(256) spline_pass_kernel(PassArgs a, SplArgs q)
         }
     }
 }
-
-template <int NT, int NH>
-struct SplineInverse {
-    const float *img;
-    SplineShape sp;
-    float *buf;
-    int lane;
-#ifdef NNEST_STAMP
-    unsigned long long t_mlp = 0, t_xch = 0, t_upd = 0;
-#endif
-    __device__ __forceinline__ float operator()(f32x4 (&xs)[2][NT]) const {
-        f32x4 t[2][NT];
-        spl_from_parity<NT>(buf, sp.D, sp.nl, lane, xs, t);
-        const float ld = spline_inverse_tile<NT, NH>(img, sp, lane, t);
-        spl_to_parity<NT>(buf, sp.D, sp.nl, lane, t, xs);
-        return ld;
-    }
-};
 
 template <int NT, int NH, bool DBG>
 __global__ void __launch_bounds__(256) spline_mh_kernel(MhArgs a, SplArgs q) {

@@ -69,6 +69,47 @@ class HipSpline(_PaddedVectors, _HipFlow):
         f = self._lib.nnest_spline_mh_form_for(self._h, int(C), _lib.mh_flags(dynamic, False, lag, None, 0))
         return self.SPLINE_MH_FORMS.get(f)
 
+    SPLINE_SLICE_FORMS = {None: -1, 'wave': 0, 'team': 1, 'pair': 2}
+
+    def _slice_flags(self, form):
+        if form not in self.SPLINE_SLICE_FORMS:
+            raise ValueError("form=%r: None (the library chooses), 'wave', 'team' or 'pair'" % (form,))
+        return (self.SPLINE_SLICE_FORMS[form] + 1) & 15   # NNEST_SPLINE_SLICE_FORM(f); 0 = NNEST_SPLINE_SLICE_AUTO
+
+    def slice_form_for(self, C, form=None):
+        """the form of the slice kernel `slice_steps` runs for C walkers (nnest_spline_slice_form_for): 'pair', 'team' or 'wave' as
+        for `kernel_form_for`; None if the launch would be refused (a pinned 'pair' at x_dim <= 32)"""
+        return self.SPLINE_MH_FORMS.get(self._lib.nnest_spline_slice_form_for(self._h, int(C), self._slice_flags(form)))
+
+    def slice_steps(self, like_id, like_scale, z, logl, loglstar, width, steps, max_stepout=8, max_shrink=32, noise=None, seed=0,
+                    walker_offset=0, history=False, like_params=None, form=None):
+        """SLICE proposal in latent space with the spline flow (nnest_spline_slice_steps; BUILD-DEFINED, the reference has none): the
+        definition, streams and return dict of _HipFlow.slice_steps -- x, n_call, n_move, moved (nested.py:432), n_eval, hist_x --
+        with the spline's inverse.  z [C,D] float32 and logl [C] float64 are updated in place; noise = dz [steps,C,D] replays
+        recorded directions (fill_slice_noise exports the in-kernel ones).  form: None (by population) | 'wave' | 'team' | 'pair'."""
+        assert z.is_cuda and z.dtype == torch.float32 and z.is_contiguous()
+        assert logl.is_cuda and logl.dtype == torch.float64 and logl.is_contiguous()
+        flags = self._slice_flags(form)
+        C, dev = z.shape[0], self.device
+        x = torch.empty_like(z)
+        n_call = torch.empty(C, dtype=torch.int32, device=dev)
+        n_move = torch.empty(C, dtype=torch.int32, device=dev)
+        n_eval = torch.empty(C, dtype=torch.int32, device=dev)
+        hx = torch.empty(C, steps + 1, self.D, dtype=torch.float32, device=dev) if history else None
+        dz = None
+        if noise is not None:
+            dz = _as_dev_f32(noise.reshape(-1, self.D), dev)
+            assert dz.shape[0] == steps * C
+        with torch.cuda.device(dev):
+            lk = _lib.like_spec(like_id, like_scale, like_params)
+            _lib.check(self._lib.nnest_spline_slice_steps(self._h, ctypes.byref(lk), _lib.ptr(z), _lib.ptr(x), _lib.ptr(logl),
+                                                          float(loglstar), float(width), int(steps), C, int(max_stepout), int(max_shrink),
+                                                          flags, _lib.ptr(dz), int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset),
+                                                          _lib.ptr(hx), _lib.ptr(n_call), _lib.ptr(n_move), _lib.ptr(n_eval),
+                                                          _lib.current_stream(dev)))
+        return dict(x=x, n_call=n_call, n_move=n_move & (_lib.MH_ALL_MOVED - 1), moved=(n_move & _lib.MH_ALL_MOVED) != 0, n_eval=n_eval,
+                    hist_x=hx)
+
     def train_form_for(self, batch):
         """'rows' (one row of the minibatch per workgroup, nnest_spline_rows.hip) or 'tiles' (nnest_spline_train.hip): what a minibatch
         of `batch` rows runs in (nnest_spline_train_form)"""
