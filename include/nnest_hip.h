@@ -215,10 +215,50 @@ int nnest_mh_form_for(const nnest_nvp_t *nvp, int C, int flags);
  * (or NULL): evaluations of the flow.  noise_dz_dev [steps,C,D] replays recorded directions (NULL: in-kernel Philox, the draws
  * nnest_slice_fill_noise exports); the uniforms are Philox4x32-10 words of (seed, walker, 64 step + k), exact in float32.
  * hist_x_dev [C, steps + 1, D] or NULL.  One walker per wave, no cross-workgroup wait: any C.  Shapes: the reference's defaults
- * (hidden 16, 3 blocks, 1 layer, scale ''), x_dim <= 128; NNEST_E_UNSUPPORTED otherwise.  (Added within ABI 15.) */
+ * (hidden 16, 3 blocks, 1 layer, scale ''), x_dim <= 128; NNEST_E_UNSUPPORTED otherwise.  (Added within ABI 15.)
+ * Every other flow (MAF, Cholesky, fast/slow, other NVP shapes) and every likelihood the kernels do not know (a host callable,
+ * derived parameters, another prior) run the same definition through nnest_slice_rounds_* below; the spline flow has
+ * nnest_spline_slice_steps. */
 int nnest_slice_steps(nnest_nvp_t *nvp, const nnest_like_t *like, float *z_dev, float *x_dev, double *logl_dev, double loglstar,
                       float width, int steps, int C, int max_stepout, int max_shrink, const float *noise_dz_dev, uint64_t seed,
                       uint64_t walker_offset, float *hist_x_dev, int *n_call_dev, int *n_move_dev, int *n_eval_dev, void *stream);
+
+/* SLICE proposal in ROUNDS, for any flow and any likelihood: the definition of nnest_slice_steps (directions, Philox uniforms, slice
+ * level, bracket, step-out, shrinkage, counters, NNEST_MH_ALL_MOVED), with each walker's state machine kept in a handle on the device
+ * and the flow's inverse and the likelihood evaluated by the CALLER between the launches.  One round:
+ *   z_cand --(caller: the flow's inverse entry point)--> x_cand, ld_cand
+ *   nnest_slice_rounds_screen: box test (or the caller's prior flags) and slice level; the x_cand rows whose likelihood decides are
+ *       packed into rows_dev in ascending walker order (their walkers in idx_dev); counts_dev = {packed rows, walkers whose candidate
+ *       was live}.  counts[1] == 0: every walker has finished, nothing further is to be evaluated.
+ *   caller: logl_rows[r] = logL(rows[r]) for r < counts[0] (float64, non-finite values as -1e100)
+ *   nnest_slice_rounds_advance: consumes the decisions, steps every walker, writes the next candidates into z_cand_dev.
+ * Walkers do not wait for each other: one that finishes an update starts its next in the next round, so a batch takes as many rounds
+ * as its busiest walker has evaluations (+ one that finds none live).  Device pointers, one stream, return codes.
+ *   create: state for C walkers of x_dim D and `steps` updates (device memory of the current device).
+ *   begin: z_dev [C,D] and its x_dev = f^-1(z), ld_dev = log|det dx/dz| (float32), logl_dev [C] (float64) start the chains (read only);
+ *       noise_dz_dev [steps,C,D] replays recorded directions (NULL: in-kernel Philox, what nnest_slice_fill_noise exports);
+ *       hist_x_dev / hist_z_dev [C, steps + 1, D], hist_logl_dev [C, steps + 1]: the state after every update, or NULL;
+ *       move_ref_dev [C, steps] or NULL: per update the packed row the walker moved to, counted over the rows of all rounds since
+ *       begin (the row of round r is  rows before round r + its row), -1 if it stayed -- what a caller needs to pick the derived
+ *       parameters it computed with a row; z_cand_dev [C,D] receives the first candidates.
+ *   screen: x_cand_dev [C,D], ld_cand_dev [C]; inbox_dev [C] int or NULL (NULL: UniformPrior(D, -1, 1), NaN inside); rows_dev
+ *       [C,D], idx_dev [C], counts_dev [2] int out.
+ *   advance: rows_dev and logl_rows_dev [>= counts[0]] of this round; z_cand_dev [C,D] out.
+ *   finish: z_dev, x_dev [C,D], logl_dev [C], n_call_dev, n_move_dev (with NNEST_MH_ALL_MOVED), n_eval_dev [C] out (each may be
+ *       NULL); n_call counts the packed rows of the walker, n_eval its candidates.
+ * (Added within ABI 15.) */
+typedef struct nnest_slice_rounds nnest_slice_rounds_t;
+int nnest_slice_rounds_create(int C, int D, int steps, nnest_slice_rounds_t **out);
+int nnest_slice_rounds_destroy(nnest_slice_rounds_t *h);
+int nnest_slice_rounds_begin(nnest_slice_rounds_t *h, const float *z_dev, const float *x_dev, const float *ld_dev, const double *logl_dev,
+                             double loglstar, float width, int max_stepout, int max_shrink, const float *noise_dz_dev, uint64_t seed,
+                             uint64_t walker_offset, float *hist_x_dev, float *hist_z_dev, double *hist_logl_dev, int *move_ref_dev,
+                             float *z_cand_dev, void *stream);
+int nnest_slice_rounds_screen(nnest_slice_rounds_t *h, const float *x_cand_dev, const float *ld_cand_dev, const int *inbox_dev,
+                              float *rows_dev, int *idx_dev, int *counts_dev, void *stream);
+int nnest_slice_rounds_advance(nnest_slice_rounds_t *h, const float *rows_dev, const double *logl_rows_dev, float *z_cand_dev, void *stream);
+int nnest_slice_rounds_finish(nnest_slice_rounds_t *h, float *z_dev, float *x_dev, double *logl_dev, int *n_call_dev, int *n_move_dev,
+                              int *n_eval_dev, void *stream);
 int nnest_slice_fill_noise(float *dz_dev, int steps, int C, int D, uint64_t seed, uint64_t walker_offset, void *stream);
 /* size of sync_dev in 8-byte words for a launch of `steps` steps */
 int nnest_mh_sync_words(int steps);

@@ -38,10 +38,10 @@ class HipCholesky(_HipFlow):
             pass
 
     def slice_steps(self, *args, **kwargs):
-        """the slice proposal exists for the NVP (nnest_slice_steps) and the spline flow (HipSpline.slice_steps) only: the
-        inherited method would hand this handle to the NVP's entry point"""
-        raise NotImplementedError("mcmc_proposal='slice' is not implemented for the Cholesky flow (flow='choleksy'); "
-                                  "use flow='nvp' or flow='spline'")
+        """the fused slice kernels exist for the NVP (nnest_slice_steps) and the spline flow (HipSpline.slice_steps) only: the
+        inherited method would hand this handle to the NVP's entry point.  The sampler's slice proposal runs this flow through
+        nnest_amd.slice_rounds (supports_fused_slice is False)."""
+        raise NotImplementedError("no fused slice kernel for the Cholesky flow (flow='choleksy'): use nnest_amd.slice_rounds")
 
     def layer_shapes(self):
         D = self.D

@@ -231,6 +231,10 @@ class HipFastSlowNVP(object):
     def prior_sample(self, num_samples):
         return torch.randn(int(num_samples), self.D, device=self.device)
 
+    def supports_fused_slice(self, C):
+        """no fused slice kernel for the fast/slow hierarchy: the slice proposal runs through nnest_amd.slice_rounds"""
+        return False
+
     # ---- training ---------------------------------------------------------------------------------------------------------
     epoch_chunk = 1 << 30
 

@@ -243,6 +243,11 @@ class _HipFlow(object):
         return dict(x=x, n_call=n_call, n_move=n_move & (_lib.MH_ALL_MOVED - 1), moved=(n_move & _lib.MH_ALL_MOVED) != 0, n_eval=n_eval,
                     hist_x=hx)
 
+    def supports_fused_slice(self, C):
+        """whether `slice_steps` (a fused slice kernel) takes this flow for C walkers; where it does not, the slice proposal runs
+        through nnest_amd.slice_rounds (any flow)"""
+        return False
+
     def fill_slice_noise(self, steps, C, seed=0, walker_offset=0):
         """the directions nnest_slice_steps draws (Philox normals), exported for the checker: dz [steps, C, D]"""
         dz = torch.empty(steps, C, self.D, dtype=torch.float32, device=self.device)
@@ -468,6 +473,10 @@ class HipNVP(_PaddedVectors, _HipFlow):
         self.prior = torch.distributions.MultivariateNormal(torch.zeros(self.D, device=self.device),
                                                             torch.eye(self.D, device=self.device))
         self.load_packed(self.default_init(seed))
+
+    def supports_fused_slice(self, C):
+        """nnest_slice_steps runs the reference's default coupling shape only (hidden 16, 3 blocks, 1 layer, scale '')"""
+        return self._Hn == 16 and self.B == 3 and self.L == 1 and self.scale == ''
 
     def __del__(self):
         try:

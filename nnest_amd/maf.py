@@ -46,6 +46,10 @@ class HipMAF(HipNVP):
                                                             torch.eye(self.D, device=self.device))
         self.load_packed(self.default_init(seed))
 
+    def supports_fused_slice(self, C):
+        """no fused slice kernel for the MAF: the slice proposal runs through nnest_amd.slice_rounds"""
+        return False
+
     def train_epochs(self, xtrain, xvalid, perm, noise=None, seed=0, jitter=0.0, batch=100, max_epochs=1, patience=50,
                      lr=1e-3, weight_decay=1e-6, epoch_offset=0, resume=False, finalize=True, result=None, one_cu=False):
         """Trainer.train's epoch loop (trainer.py:198-241) driven from the host: per minibatch one gradient (nnest_nvp_loss_grad:

@@ -68,8 +68,10 @@ class Sampler(object):
                  mcmc_history=False,
                  mcmc_proposal='mh'):
         # mcmc_proposal (not in the reference, whose _mcmc_sample proposes random-walk Metropolis moves only, sampler.py:310-316):
-        # 'mh' = that step; 'slice' = the build-defined slice proposal in latent space (BASELINE north_star; nnest_slice_steps,
-        # include/nnest_hip.h; parity unpinned) on the fused kernel path
+        # 'mh' = that step; 'slice' = the build-defined slice proposal in latent space (BASELINE north_star; include/nnest_hip.h,
+        # parity unpinned) under the hard constraint logL > L*, with every flow and every likelihood: the fused kernels
+        # (nnest_slice_steps, nnest_spline_slice_steps) where they take the flow and the likelihood is a known id, the round driver
+        # nnest_amd.slice_rounds otherwise (other flows and shapes; a user likelihood, derived parameters or another prior)
         if mcmc_proposal not in ('mh', 'slice'):
             raise ValueError("mcmc_proposal=%r: 'mh' (the reference's step) or 'slice' (build-defined)" % (mcmc_proposal,))
         self.mcmc_proposal = mcmc_proposal
@@ -252,6 +254,9 @@ class Sampler(object):
         last state unless the sampler was built with mcmc_history=True (nested.py:432-437 reads only those)."""
         if step_size <= 0.0:
             step_size = 2 / self.x_dim ** 0.5
+        if self.mcmc_proposal == 'slice':
+            return self._mcmc_sample_slice(mcmc_steps, step_size, init_samples, init_loglikes, init_derived, loglstar, walker_offset,
+                                           seed)
         fused = (self._fused_like_id is not None and init_samples is not None and init_loglikes is not None
                  and prior_volume_steps == 1)   # loglstar None = the unconstrained branch, also in the kernel
         if fused:
@@ -259,6 +264,52 @@ class Sampler(object):
                                            loglstar, walker_offset, seed, form)
         return self._mcmc_sample_host(mcmc_steps, step_size, dynamic_step_size, num_chains, init_samples,
                                       init_loglikes, init_derived, loglstar, max_start_tries, prior_volume_steps)
+
+    def _unit_box_prior(self):
+        p = self._user_prior
+        return p is not None and not self._transform_prior and bool(getattr(p, 'is_unit_box', lambda: False)())
+
+    def _slice_rounds(self, z, logl, loglstar, step_size, mcmc_steps, walker_offset, seed, history=False, init_derived=None):
+        """the slice proposal through nnest_amd.slice_rounds: the device likelihood when the kernels know it, else the host
+        protocol (self.loglike on the rows whose likelihood decides, so total_calls grows by exactly sum n_call; the prior in place
+        of the box unless it is the unit box).  Initial bracket: twice the Metropolis step, as the fused slice kernels."""
+        from .slice_rounds import slice_rounds
+        netG = self.trainer.netG
+        kw = dict(seed=self._next_seed() if seed is None else seed, walker_offset=walker_offset, history=history)
+        args = (netG, z, logl, float(loglstar), 2.0 * float(step_size), int(mcmc_steps))
+        if self._fused_like_id is not None:
+            res = slice_rounds(*args, like_id=self._fused_like_id, like_scale=self._linear_scale, like_params=self._fused_like_params, **kw)
+            ncall = int(res['n_call'].sum().item())
+            self.total_calls += ncall
+        else:
+            prior = None if self._unit_box_prior() else (lambda x: self.prior(x) > -1e30)
+            res = slice_rounds(*args, loglike=self.loglike, prior=prior, num_derived=self.num_derived, init_derived=init_derived, **kw)
+            ncall = int(res['n_call'].sum().item())
+        nmove = int(res['n_move'].sum().item())
+        self.total_accepted += nmove
+        self.total_rejected += z.shape[0] * int(mcmc_steps) - nmove
+        return res, ncall
+
+    def _mcmc_sample_slice(self, mcmc_steps, step_size, init_samples, init_loglikes, init_derived, loglstar, walker_offset, seed):
+        """_mcmc_sample with mcmc_proposal='slice': (samples, latent, derived, loglikes, scale, ncall) as _mcmc_sample_host returns
+        them, with the step axis steps + 1.  BUILD-DEFINED (the reference has no slice proposal)."""
+        if loglstar is None:
+            raise NotImplementedError("mcmc_proposal='slice' samples under the hard constraint logL > loglstar only")
+        if init_samples is None:
+            raise NotImplementedError("mcmc_proposal='slice' starts from given points (init_samples)")
+        netG = self.trainer.netG
+        ncall0 = 0
+        if init_loglikes is None or (self.num_derived > 0 and init_derived is None):
+            init_loglikes, init_derived = self.loglike(init_samples)
+            ncall0 = init_samples.shape[0]
+        z, _ = netG.forward(init_samples)
+        logl = torch.as_tensor(np.asarray(init_loglikes, dtype=np.float64)).to(z.device).contiguous()
+        res, ncall = self._slice_rounds(z, logl, loglstar, step_size, mcmc_steps, walker_offset, seed, history=True,
+                                        init_derived=init_derived)
+        C = z.shape[0]
+        derived = res['hist_derived'] if res['hist_derived'] is not None else np.empty((C, int(mcmc_steps) + 1, 0))
+        return (res['hist_x'].cpu().numpy(), res['hist_z'].cpu().numpy(), derived, res['hist_logl'].cpu().numpy(), float(step_size),
+                ncall + ncall0)
 
     def _fused_launch(self, mcmc_steps, step_size, dynamic, init_samples, init_loglikes, loglstar, walker_offset, seed,
                       form=None):
@@ -353,6 +404,11 @@ class Sampler(object):
                 raise NotImplementedError("mcmc_proposal='slice' samples under the hard constraint logL > loglstar only")
             z, _ = netG.forward(init_samples)
             logl = torch.as_tensor(np.asarray(init_loglikes, dtype=np.float64), device=z.device).contiguous()
+            fused_slice = getattr(netG, 'supports_fused_slice', None)
+            if fused_slice is not None and not fused_slice(C):   # no fused slice kernel for this flow: the round driver
+                res, ncall = self._slice_rounds(z, logl, loglstar, step_size, mcmc_steps, walker_offset, seed)
+                ends = torch.cat([res['x'].double(), logl[:, None], res['moved'][:, None].double()], dim=1)
+                return ends, float(step_size), ncall
             res = netG.slice_steps(self._fused_like_id, self._linear_scale, z, logl, float(loglstar), 2.0 * float(step_size),
                                    int(mcmc_steps), seed=self._next_seed() if seed is None else seed, walker_offset=walker_offset,
                                    like_params=self._fused_like_params)

@@ -81,6 +81,9 @@ class HipSpline(_PaddedVectors, _HipFlow):
         for `kernel_form_for`; None if the launch would be refused (a pinned 'pair' at x_dim <= 32)"""
         return self.SPLINE_MH_FORMS.get(self._lib.nnest_spline_slice_form_for(self._h, int(C), self._slice_flags(form)))
 
+    def supports_fused_slice(self, C):
+        return self.slice_form_for(C) is not None
+
     def slice_steps(self, like_id, like_scale, z, logl, loglstar, width, steps, max_stepout=8, max_shrink=32, noise=None, seed=0,
                     walker_offset=0, history=False, like_params=None, form=None):
         """SLICE proposal in latent space with the spline flow (nnest_spline_slice_steps; BUILD-DEFINED, the reference has none): the
