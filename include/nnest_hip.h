@@ -208,8 +208,12 @@ int nnest_mh_form_for(const nnest_nvp_t *nvp, int C, int flags);
  * (oracle/oracle.py::slice_sample).  `steps` slice-sampling updates (Neal 2003: stepping out, shrinkage) of every walker along a
  * fresh random direction of latent space, of the target the reference's constrained Metropolis step leaves invariant
  * (sampler.py:326-361): density |det dx/dz| on {x(z) in the unit box, logL(x(z)) > loglstar}.  Per step: eps ~ N(0, I),
- * candidates z + t * width * eps; log y = log|det|(z) + log u1; bracket [-u0, 1 - u0], stepped out by 1 up to max_stepout times per
- * side while the end lies in the slice; then up to max_shrink shrinkage draws t = t_l + (t_r - t_l) u_k.  z_dev [C,D] and logl_dev [C]
+ * candidates z + t * width * eps; log y = log|det|(z) + log u1; bracket [-u0, 1 - u0], stepped out by 1 while the end lies in the
+ * slice, left then right, within a budget of B = 2 max_stepout expansions in all.  If the slice's ends need more than B, the bracket
+ * restarts at [-u0, 1 - u0] and B is split at random between the sides (Neal 2003, sec. 4.1): at most J = min(B, floor(u63 (B + 1)))
+ * to the left, then at most B - J to the right.  (Separate caps per side are not reversible once they bind.)  max_stepout = 0: no
+ * stepping out; 0..2^24.  Then up to max_shrink (1..60) shrinkage draws t = t_l + (t_r - t_l) u_k, k = 2, 3, ...
+ * z_dev [C,D] and logl_dev [C]
  * are updated in place, x_dev [C,D] receives the chains' ends; n_call_dev [C]: candidates whose likelihood decided (inside the box and
  * above the slice level), n_move_dev [C]: steps that moved, with NNEST_MH_ALL_MOVED as in nnest_mh_constrained_steps, n_eval_dev [C]
  * (or NULL): evaluations of the flow.  noise_dz_dev [steps,C,D] replays recorded directions (NULL: in-kernel Philox, the draws
@@ -224,7 +228,8 @@ int nnest_slice_steps(nnest_nvp_t *nvp, const nnest_like_t *like, float *z_dev, 
                       uint64_t walker_offset, float *hist_x_dev, int *n_call_dev, int *n_move_dev, int *n_eval_dev, void *stream);
 
 /* SLICE proposal in ROUNDS, for any flow and any likelihood: the definition of nnest_slice_steps (directions, Philox uniforms, slice
- * level, bracket, step-out, shrinkage, counters, NNEST_MH_ALL_MOVED), with each walker's state machine kept in a handle on the device
+ * level, bracket, step-out within the budget of 2 max_stepout expansions, shrinkage, counters, NNEST_MH_ALL_MOVED), with
+ * each walker's state machine kept in a handle on the device
  * and the flow's inverse and the likelihood evaluated by the CALLER between the launches.  One round:
  *   z_cand --(caller: the flow's inverse entry point)--> x_cand, ld_cand
  *   nnest_slice_rounds_screen: box test (or the caller's prior flags) and slice level; the x_cand rows whose likelihood decides are
@@ -374,7 +379,8 @@ int nnest_spline_mh_form_for(const nnest_spline_t *spl, int C, int flags);
 
 /* SLICE proposal in latent space with the spline flow: the definition, streams and counters of nnest_slice_steps (BUILD-DEFINED,
  * parity unpinned: the reference has no slice proposal; held to oracle/oracle.py::slice_sample) with the spline's inverse and
- * log-det in place of the NVP's.  Arguments as nnest_slice_steps; n_call_dev, n_move_dev, n_eval_dev may each be NULL.  The
+ * log-det in place of the NVP's -- the stepping-out budget of 2 max_stepout expansions and its random split included.
+ * Arguments as nnest_slice_steps; n_call_dev, n_move_dev, n_eval_dev may each be NULL.  The
  * directions are the ones nnest_slice_fill_noise exports.  Kernel forms as the spline proposal kernel's: 16 walkers per wave,
  * four waves per 16 walkers, four waves per 8 walkers held twice (x_dim > 32); walkers are not held in step (each evaluates its
  * own next candidate in every round of the tile; one that has finished idles), so any C, no resident-grid requirement.  flags:

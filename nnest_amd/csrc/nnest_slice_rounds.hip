@@ -3,8 +3,9 @@
 // the reference proposes random-walk Metropolis moves only (nnest/sampler.py:310-316).  The definition is nnest_slice_steps's
 // (nnest_solo.hip slice_kernel_solo) and the round structure nnest_spline_slice.hip's slice_body: per update and walker a direction
 // eps (noise_normal4, stream DZ), uniforms u_k = noise_uniform(seed, walker, 64 it + k), the slice level log y = log|det|(z) + log u_1,
-// the bracket [-u_0, 1 - u_0] stepped out by at most max_stepout per side, then at most max_shrink shrinkage draws; inside(t) := the
-// box holds, log|det| > log y and logL > L*.
+// the bracket [-u_0, 1 - u_0] stepped out to the slice's ends within a budget of 2 max_stepout expansions, restarted with the budget
+// split at random between the sides by u_63 if it does not suffice (slice_stepout_left, Neal 2003 sec. 4.1), then at most max_shrink
+// shrinkage draws; inside(t) := the box holds, log|det| > log y and logL > L*.
 //
 // One round: the caller maps every walker's candidate z' through ANY flow's inverse (x', log|det|), rounds_screen_kernel tests the box
 // and the slice level and packs the x' rows that need a likelihood in ascending walker order, the caller evaluates the likelihood on
@@ -34,6 +35,9 @@ struct SliceWalker {   // one walker's state machine
     float tl, tr, tc;  // bracket, this round's candidate t
     float logy;        // slice level
     int it, phase, k;  // update (1-based), phase (0 / 1: stepping out to the left / right, k steps taken; 2: shrinkage, k draws taken)
+    int nl;            // < 0: the full step-out (at most 2 max_out expansions in all, k counting over both sides); else the split
+                       // step-out: at most nl steps left, 2 max_out - nl right
+    float t0;          // -u_0: the bracket's start
     int active;        // updates left (this round's candidate is live)
     int pre, slot;     // this round's screen: box and level passed; packed row (-1: none)
     int n_call, n_move, n_eval;
@@ -84,11 +88,23 @@ __device__ __forceinline__ void begin_update(const RoundArgs &a, SliceWalker &s,
     }
     const float u0 = noise_uniform(a.seed, walker, 64u * (uint32_t)s.it + 0u), u1 = noise_uniform(a.seed, walker, 64u * (uint32_t)s.it + 1u);
     s.logy = s.ld + __logf(u1);   // (u1 = 0: -inf, the whole feasible line is the slice)
-    s.tl = -u0;
+    s.t0 = -u0;
+    s.tl = s.t0;
     s.tr = 1.0f - u0;
     s.k = 0;
+    s.nl = -1;
     s.phase = a.max_out > 0 ? 0 : 2;
     s.tc = s.phase == 0 ? s.tl : shrink_candidate(a, s, walker);
+}
+
+// the full step-out took more than 2 max_out expansions: restart from [-u_0, 1 - u_0] with the budget split at random
+__device__ __forceinline__ void split_stepout(const RoundArgs &a, SliceWalker &s, uint64_t walker) {
+    s.tl = s.t0;
+    s.tr = 1.0f + s.t0;
+    s.k = 0;
+    s.nl = slice_stepout_left(a.seed, walker, (uint32_t)s.it, a.max_out);
+    s.phase = s.nl > 0 ? 0 : (s.nl < 2 * a.max_out ? 1 : 2);
+    s.tc = s.phase == 0 ? s.tl : s.phase == 1 ? s.tr : shrink_candidate(a, s, walker);
 }
 
 // z' = z + t * width * eps, one fused multiply-add per dim (slice_kernel_solo's candidate)
@@ -224,13 +240,25 @@ __global__ void __launch_bounds__(256) rounds_advance_kernel(RoundArgs a, const 
     s.n_eval += 1;
     s.n_call += pre ? 1 : 0;
     bool done = false;
-    if (s.phase == 0) {            // for j < max_out: if !inside(t_l) break; t_l -= 1
+    const uint64_t walker = a.walker_offset + (uint64_t)c;
+    if (s.phase == 0 && s.nl < 0) {            // full: while inside(t_l): t_l -= 1 (more than 2 max_out expansions: split)
         if (ins) { s.tl -= 1.0f; s.k += 1; }
-        if (ins && s.k < a.max_out) s.tc = s.tl;
-        else { s.phase = 1; s.k = 0; s.tc = s.tr; }
-    } else if (s.phase == 1) {     // the same to the right
+        if (!ins) { s.phase = 1; s.tc = s.tr; }
+        else if (s.k <= 2 * a.max_out) s.tc = s.tl;
+        else split_stepout(a, s, walker);
+    } else if (s.phase == 1 && s.nl < 0) {     // full: the same to the right, k counting on
         if (ins) { s.tr += 1.0f; s.k += 1; }
-        if (ins && s.k < a.max_out) s.tc = s.tr;
+        if (!ins) { s.phase = 2; s.k = 0; s.tc = shrink_candidate(a, s, walker); }
+        else if (s.k <= 2 * a.max_out) s.tc = s.tr;
+        else split_stepout(a, s, walker);
+    } else if (s.phase == 0) {     // split: for j < nl: if !inside(t_l) break; t_l -= 1
+        if (ins) { s.tl -= 1.0f; s.k += 1; }
+        if (ins && s.k < s.nl) s.tc = s.tl;
+        else if (s.nl < 2 * a.max_out) { s.phase = 1; s.k = 0; s.tc = s.tr; }
+        else { s.phase = 2; s.k = 0; s.tc = shrink_candidate(a, s, a.walker_offset + (uint64_t)c); }
+    } else if (s.phase == 1) {     // split: for j < 2 max_out - nl: the same to the right
+        if (ins) { s.tr += 1.0f; s.k += 1; }
+        if (ins && s.k < 2 * a.max_out - s.nl) s.tc = s.tr;
         else { s.phase = 2; s.k = 0; s.tc = shrink_candidate(a, s, a.walker_offset + (uint64_t)c); }
     } else if (ins) {              // shrinkage: the walker moves to the candidate (its z' and the packed x' row)
         const float *xr = rows + (size_t)s.slot * D;
@@ -349,8 +377,8 @@ int nnest_slice_rounds_begin(nnest_slice_rounds_t *h, const float *z_dev, const 
                              float *z_cand_dev, void *stream) {
     if (!h) return rfail(NNEST_E_ARG, "NULL handle");
     if (!z_dev || !x_dev || !ld_dev || !logl_dev || !z_cand_dev) return rfail(NNEST_E_ARG, "NULL device buffer");
-    if (max_stepout < 0 || max_shrink < 1 || max_shrink > 60 || !(width > 0.f))
-        return rfail(NNEST_E_ARG, "max_stepout=%d max_shrink=%d (1..60) width=%g", max_stepout, max_shrink, (double)width);
+    if (max_stepout < 0 || max_stepout > (1 << 24) || max_shrink < 1 || max_shrink > 60 || !(width > 0.f))
+        return rfail(NNEST_E_ARG, "max_stepout=%d (0..2^24) max_shrink=%d (1..60) width=%g", max_stepout, max_shrink, (double)width);
     RoundArgs &a = h->a;
     a.loglstar = loglstar; a.width = width; a.max_out = max_stepout; a.max_shrink = max_shrink;
     a.noise_dz = noise_dz_dev; a.seed = seed; a.walker_offset = walker_offset;

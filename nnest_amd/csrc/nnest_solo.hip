@@ -668,7 +668,12 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
 // logL(x(z)) > L*}.  Per step and walker:
 //   eps ~ N(0, I_D) (noise_normal4, stream DZ);  candidates z(t) = z + t * width * eps,  t in R
 //   log y = log|det|(z) + log u_1;   inside(t) := x(z(t)) in the box  and  log|det|(z(t)) > log y  and  logL(x(z(t))) > L*
-//   bracket [t_l, t_r] = [-u_0, 1 - u_0];  stepping out: while inside(t_l) and fewer than `max_out` steps: t_l -= 1 (the same to the right)
+//   bracket [t_l, t_r] = [-u_0, 1 - u_0];  stepping out (Neal 2003, sec. 4.1) within a budget of B = 2 max_out expansions: while
+//   inside(t_l): t_l -= 1, then while inside(t_r): t_r += 1 -- the full step-out, whose expansions are the grid points inside the slice
+//   between its two outside ends, a count every point of the bracket finds alike.  If it takes more than B expansions, the bracket
+//   restarts at [-u_0, 1 - u_0] and the budget is split at random: at most J = min(B, floor(u_63 (B + 1))) steps to the left, then at
+//   most B - J to the right (slice_stepout_left).  Either way the bracket is found from the new point with the probability it had
+//   from the old, so the update is reversible (separate caps per side were not, once they bound).  max_out = 0: no stepping out.
 //   shrinkage: t = t_l + (t_r - t_l) u_k (k = 2, 3, ...); inside(t) -> the walker moves there; else the bracket's end on t's side
 //   becomes t; after `max_shrink` draws the walker stays.
 // Every evaluation is one "eval" of the hot path (coupling-stack inverse + log-det + box + likelihood); n_call counts, as the
@@ -819,8 +824,19 @@ __global__ void __launch_bounds__(256) slice_kernel_solo(SliceArgs a) {
             return pre && (lc > loglstar);
         };
         float tl = -u0, tr = 1.0f - u0;
-        for (int j = 0; j < a.max_out; ++j) { if (!inside(tl)) break; tl -= 1.0f; }
-        for (int j = 0; j < a.max_out; ++j) { if (!inside(tr)) break; tr += 1.0f; }
+        if (a.max_out > 0) {
+            const int B = 2 * a.max_out;
+            int n = 0;   // expansions of the full step-out; more than B: the split step-out instead
+            while (n <= B && inside(tl)) { tl -= 1.0f; n += 1; }
+            while (n <= B && inside(tr)) { tr += 1.0f; n += 1; }
+            if (n > B) {
+                tl = -u0;
+                tr = 1.0f - u0;
+                const int nl = slice_stepout_left(a.seed, walker, (uint32_t)it, a.max_out);
+                for (int j = 0; j < nl; ++j) { if (!inside(tl)) break; tl -= 1.0f; }
+                for (int j = 0; j < B - nl; ++j) { if (!inside(tr)) break; tr += 1.0f; }
+            }
+        }
         bool moved = false;
         for (int k = 0; k < a.max_shrink; ++k) {
             const float uk = noise_uniform(a.seed, walker, 64u * (uint32_t)it + 2u + (uint32_t)k);

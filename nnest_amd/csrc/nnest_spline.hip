@@ -365,8 +365,8 @@ int nnest_spline_slice_steps(nnest_spline_t *h, const nnest_like_t *like, float 
     if (rc) return rc;
     LikeSpec lk;
     if ((rc = scheck_like(like, h->s.D, &lk))) return rc;
-    if (steps < 0 || max_stepout < 0 || max_shrink < 1 || max_shrink > 60 || !(width > 0.f))
-        return spline_fail(NNEST_E_ARG, "steps=%d max_stepout=%d max_shrink=%d (1..60) width=%g", steps, max_stepout, max_shrink, (double)width);
+    if (steps < 0 || max_stepout < 0 || max_stepout > (1 << 24) || max_shrink < 1 || max_shrink > 60 || !(width > 0.f))
+        return spline_fail(NNEST_E_ARG, "steps=%d max_stepout=%d (0..2^24) max_shrink=%d (1..60) width=%g", steps, max_stepout, max_shrink, (double)width);
     if (flags & ~15) return spline_fail(NNEST_E_ARG, "flags=0x%x: bits 0..3 only (NNEST_SPLINE_SLICE_FORM)", flags);
     if (C > 0 && spline_slice_form(h->s, C, flags, h->num_cu) < 0)
         return spline_fail(NNEST_E_UNSUPPORTED, "spline slice proposal: form %d pinned, x_dim=%d (the pair form needs x_dim > 32)", (flags & 15) - 1, h->s.D);

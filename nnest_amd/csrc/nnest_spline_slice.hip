@@ -2,8 +2,9 @@
 // nnest_spline_slice_steps).  BUILD-DEFINED, parity unpinned: the reference proposes random-walk Metropolis moves only
 // (nnest/sampler.py:310-316).  The definition is the one slice_kernel_solo implements for the NVP (nnest_solo.hip): per update
 // and walker a direction eps (noise_normal4, stream DZ), uniforms u_k = noise_uniform(seed, walker, 64 it + k), the slice level
-// log y = log|det|(z) + log u_1, the bracket [-u_0, 1 - u_0] stepped out by at most max_stepout per side, then at most max_shrink
-// shrinkage draws; inside(t) := the box holds, log|det| > log y and logL > L*.  Only the flow differs: the spline's inverse
+// log y = log|det|(z) + log u_1, the bracket [-u_0, 1 - u_0] stepped out to the slice's ends within a budget of 2 max_stepout
+// expansions, restarted with the budget split at random between the sides by u_63 if it does not suffice (slice_stepout_left,
+// Neal 2003 sec. 4.1), then at most max_shrink shrinkage draws; inside(t) := the box holds, log|det| > log y and logL > L*.  Only the flow differs: the spline's inverse
 // (spline_inverse.h) replaces the coupling stack.
 //
 // Layout: the tiles of the spline proposal kernels -- 16 walkers per wave (WAVE), four waves per 16 walkers (TEAM), or four waves
@@ -92,6 +93,9 @@ __device__ __forceinline__ void slice_body(const SplSliceArgs &a, int D, int til
     if (a.hist_x) store_tile<NT>(a.hist_x, (long)row * (S + 1), store, D, lane, x);
 
     int it = 0, phase = 0, k = 0;   // phase 0 / 1: stepping out to the left / right (k steps taken); 2: shrinkage (k draws taken)
+    int nl = -1;                    // < 0: the full step-out (at most 2 max_out expansions in all, k counts them over both sides);
+                                    // else the split step-out: at most nl steps left, 2 max_out - nl right
+    float t0 = 0.f;                 // -u_0: the bracket's start
     float tl = 0.f, tr = 0.f, logy = 0.f, tc = 0.f;   // bracket, slice level, the candidate of the next round
     int n_call = 0, n_move = 0, n_eval = 0;
     bool active = ok && S > 0;
@@ -105,11 +109,21 @@ __device__ __forceinline__ void slice_body(const SplSliceArgs &a, int D, int til
         else slice_direction<NT>(seed, walker, (uint32_t)it, D, lane, e);
         const float u0 = noise_uniform(seed, walker, 64u * (uint32_t)it + 0u), u1 = noise_uniform(seed, walker, 64u * (uint32_t)it + 1u);
         logy = ld + __logf(u1);   // (u1 = 0: -inf, the whole feasible line is the slice)
-        tl = -u0;
+        t0 = -u0;
+        tl = t0;
         tr = 1.0f - u0;
         k = 0;
+        nl = -1;
         phase = max_out > 0 ? 0 : 2;
         tc = phase == 0 ? tl : shrink_candidate();
+    };
+    auto split_stepout = [&]() {   // the full step-out took more than 2 max_out expansions: restart with the budget split at random
+        tl = t0;
+        tr = 1.0f + t0;
+        k = 0;
+        nl = slice_stepout_left(seed, walker, (uint32_t)it, max_out);
+        phase = nl > 0 ? 0 : (nl < 2 * max_out ? 1 : 2);
+        tc = phase == 0 ? tl : phase == 1 ? tr : shrink_candidate();
     };
     if (active) begin_update();
 
@@ -147,13 +161,24 @@ __device__ __forceinline__ void slice_body(const SplSliceArgs &a, int D, int til
             n_eval += 1;
             n_call += pre ? 1 : 0;
             bool done = false;
-            if (phase == 0) {            // for j < max_out: if !inside(t_l) break; t_l -= 1
+            if (phase == 0 && nl < 0) {          // full: while inside(t_l): t_l -= 1 (more than 2 max_out expansions: split)
                 if (ins) { tl -= 1.0f; k += 1; }
-                if (ins && k < max_out) tc = tl;
-                else { phase = 1; k = 0; tc = tr; }
-            } else if (phase == 1) {     // the same to the right
+                if (!ins) { phase = 1; tc = tr; }
+                else if (k <= 2 * max_out) tc = tl;
+                else split_stepout();
+            } else if (phase == 1 && nl < 0) {   // full: the same to the right, k counting on
                 if (ins) { tr += 1.0f; k += 1; }
-                if (ins && k < max_out) tc = tr;
+                if (!ins) { phase = 2; k = 0; tc = shrink_candidate(); }
+                else if (k <= 2 * max_out) tc = tr;
+                else split_stepout();
+            } else if (phase == 0) {             // split: for j < nl: if !inside(t_l) break; t_l -= 1
+                if (ins) { tl -= 1.0f; k += 1; }
+                if (ins && k < nl) tc = tl;
+                else if (nl < 2 * max_out) { phase = 1; k = 0; tc = tr; }
+                else { phase = 2; k = 0; tc = shrink_candidate(); }
+            } else if (phase == 1) {             // split: for j < 2 max_out - nl: the same to the right
+                if (ins) { tr += 1.0f; k += 1; }
+                if (ins && k < 2 * max_out - nl) tc = tr;
                 else { phase = 2; k = 0; tc = shrink_candidate(); }
             } else if (ins) {            // shrinkage: the walker moves to the candidate
                 n_move += 1;

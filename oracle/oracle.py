@@ -375,13 +375,24 @@ def slice_uniform(seed, walker, idx):
     return np.float32((r[0] >> 8) * 5.9604644775390625e-08)
 
 
+def slice_stepout_split(v, max_stepout):
+    """the split step-out's budget (Neal 2003, sec. 4.1): B = 2 max_stepout expansions, at most J = min(B, floor(v (B + 1))) to the
+    left and K = B - J to the right, v = the update's uniform 63.  v is a 24-bit fraction, so the product is exact in float64 (a float32
+    product could round up to B + 1)."""
+    B = 2 * int(max_stepout)
+    J = min(B, int(np.floor(np.float64(v) * np.float64(B + 1))))
+    return J, B - J
+
+
 def slice_sample(flow, like, like_scale, z0, logl0, loglstar, width, dz, seed, walker_offset=0, max_stepout=8, max_shrink=32,
                  margins=None):
     """[BUILD-DEFINED, parity unpinned: the reference proposes random-walk Metropolis moves only, nnest/sampler.py:310-316]
     CPU restatement of the slice proposal kernel (nnest_amd/csrc/nnest_solo.hip slice_kernel_solo; include/nnest_hip.h
     nnest_slice_steps): univariate slice sampling (stepping out + shrinkage) along the recorded directions dz [S, C, D] of the target
     |det dx/dz| on {x(z) in the unit box, logL > loglstar}; `flow` is an oracle flow object (NVP).  Returns the per-step x history
-    [C, S + 1, D], the final z, logl, and the counters.  margins [S, C] (optional): the smallest distance of any evaluated candidate of
+    [C, S + 1, D], the final z, logl, the counters, and per update the expansions of the bracket to the left / right
+    n_left, n_right [C, S] and `split` [C, S]: stepping out goes to the slice's ends, left then right, if that takes at most
+    B = 2 max_stepout expansions; otherwise it restarts with B split at random (slice_stepout_split).  margins [S, C] (optional): the smallest distance of any evaluated candidate of
     the step from a decision threshold (box edge, slice level, L*) -- a chain that differs from the kernel's must have come close."""
     S, C, D = dz.shape
     z = np.asarray(z0, dtype=np.float32).copy()
@@ -390,6 +401,7 @@ def slice_sample(flow, like, like_scale, z0, logl0, loglstar, width, dz, seed, w
     hx = np.empty((C, S + 1, D), np.float32)
     hx[:, 0] = x
     n_call, n_move, n_eval = np.zeros(C, int), np.zeros(C, int), np.zeros(C, int)
+    n_left, n_right, split = np.zeros((C, S), int), np.zeros((C, S), int), np.zeros((C, S), bool)
     w32 = np.float32(width)
     for c in range(C):
         zc, xc, ldc, lc = z[c].copy(), x[c].copy(), np.float32(ld[c]), float(logl[c])
@@ -414,15 +426,32 @@ def slice_sample(flow, like, like_scale, z0, logl0, loglstar, width, dz, seed, w
                             abs(lp - loglstar) / (1.0 + abs(loglstar)))
                 return (pre and lp > loglstar), zp, xp, ldp, lp
 
-            tl, tr = np.float32(-u0), np.float32(np.float32(1.0) - u0)
-            for _ in range(max_stepout):
-                if not inside(tl)[0]:
-                    break
-                tl = np.float32(tl - np.float32(1.0))
-            for _ in range(max_stepout):
-                if not inside(tr)[0]:
-                    break
-                tr = np.float32(tr + np.float32(1.0))
+            t0 = np.float32(-u0)
+            tl, tr = t0, np.float32(np.float32(1.0) - u0)
+            B = 2 * int(max_stepout)
+            if B:   # the full step-out, at most B expansions in all
+                n = 0
+                while n <= B and inside(tl)[0]:
+                    tl, n = np.float32(tl - np.float32(1.0)), n + 1
+                n_left[c, it - 1] = n
+                while n <= B and inside(tr)[0]:
+                    tr, n = np.float32(tr + np.float32(1.0)), n + 1
+                n_right[c, it - 1] = n - n_left[c, it - 1]
+                if n > B:   # more than B: restart with the budget split at random
+                    split[c, it - 1] = True
+                    tl, tr = t0, np.float32(np.float32(1.0) + t0)
+                    nl, nr = slice_stepout_split(slice_uniform(seed, walker_offset + c, 64 * it + 63), max_stepout)
+                    n_left[c, it - 1] = n_right[c, it - 1] = 0
+                    for _ in range(nl):
+                        if not inside(tl)[0]:
+                            break
+                        tl = np.float32(tl - np.float32(1.0))
+                        n_left[c, it - 1] += 1
+                    for _ in range(nr):
+                        if not inside(tr)[0]:
+                            break
+                        tr = np.float32(tr + np.float32(1.0))
+                        n_right[c, it - 1] += 1
             for k in range(max_shrink):
                 uk = slice_uniform(seed, walker_offset + c, 64 * it + 2 + k)
                 t = np.float32(np.float64(np.float32(tr - tl)) * np.float64(uk) + np.float64(tl))   # fmaf(tr - tl, uk, tl)
@@ -439,7 +468,8 @@ def slice_sample(flow, like, like_scale, z0, logl0, loglstar, width, dz, seed, w
             if margins is not None:
                 margins[it - 1, c] = mg[0]
         z[c], logl[c] = zc, lc
-    return dict(x=hx, z=z, logl=logl, n_call=n_call, n_move=n_move, n_eval=n_eval)
+    return dict(x=hx, z=z, logl=logl, n_call=n_call, n_move=n_move, n_eval=n_eval, n_left=n_left, n_right=n_right,
+                split=split)
 
 
 class FastSlowNVP(object):

@@ -56,3 +56,43 @@ def test_exact_rosenbrock_evidence_by_transfer_quadrature():
     assert abs(log_evidence(3) - brute) < 2e-3, (log_evidence(3), brute)
     assert abs(log_evidence(50, h=0.01) - log_evidence(50, h=0.005)) < 1e-6
     assert abs(log_evidence(50) + 231.9384) < 1e-3
+
+
+def test_stepping_out_keeps_within_its_budget_and_splits_it_at_random():
+    """stepping out goes left, then right, to the first grid point outside the slice on each side, if that takes at most
+    B = 2 max_stepout expansions; otherwise it restarts and splits B by the update's uniform 63 (Neal 2003, sec. 4.1):
+    J = min(B, floor(v (B + 1))) expansions at most to the left, K = B - J to the right.  An identity flow in the box (the slice is
+    the chord of the box) with a width small against it, so small budgets are exceeded and large ones are not."""
+    D, C, S, w = 2, 24, 4, 0.05
+    nvp = orc.NVP(D, 16, 3, 1, np.zeros(orc.NVP(D, 16, 3, 1).n, np.float32))   # the identity flow
+    rng = np.random.RandomState(5)
+    u0 = rng.uniform(-0.9, 0.9, size=(C, D))
+    l0 = orc.loglike('rosenbrock', u0, 5.0)
+    dz = rng.standard_normal((S, C, D)).astype(np.float32)
+    seed, off = 11, 7
+    uni = np.array([[[float(orc.slice_uniform(seed, off + c, 64 * it + k)) for k in (0, 63)] for it in range(1, S + 1)]
+                    for c in range(C)])
+    for m in (0, 1, 3, 20):
+        B = 2 * m
+        a = orc.slice_sample(nvp, 'rosenbrock', 5.0, u0.astype(np.float32), l0, -1e30, w, dz, seed, walker_offset=off, max_stepout=m)
+        J = np.array([[orc.slice_stepout_split(uni[c, it, 1], m)[0] for it in range(S)] for c in range(C)])
+        assert np.array_equal(J, np.minimum(B, np.floor(uni[:, :, 1] * (B + 1))))
+        nl, nr, sp = a['n_left'], a['n_right'], a['split']
+        assert np.all(nl[sp] <= J[sp]) and np.all(nr[sp] <= B - J[sp])
+        assert np.all(nl[~sp] + nr[~sp] <= B)
+        for c, it in zip(*np.nonzero(~sp & (B > 0))):   # the full step-out: both ends are the first grid points outside the box
+            x, e = a['x'][c, it].astype(np.float64), dz[it, c].astype(np.float64)
+            for t_end, t_in in ((-uni[c, it, 0] - nl[c, it], -uni[c, it, 0] - nl[c, it] + 1),
+                                (1 - uni[c, it, 0] + nr[c, it], 1 - uni[c, it, 0] + nr[c, it] - 1)):
+                out, inn = np.max(np.abs(x + t_end * w * e)), np.max(np.abs(x + t_in * w * e))
+                assert out > 1 - 1e-5 and (inn < 1 + 1e-5 or t_in * (t_in - t_end) < 0), (m, c, it, out, inn)
+        if m == 0:
+            assert not nl.any() and not nr.any() and not sp.any()
+        elif m < 20:
+            assert sp.mean() > 0.5                                      # the chords are ~30 brackets long
+            assert np.any((nl == J) & (J > 0) & sp) and np.any((nr == B - J) & (J < B) & sp)   # the split binds on each side
+        else:
+            assert sp.mean() < 0.5 and np.any(~sp & (np.maximum(nl, nr) > m))   # beyond what a per-side cap of m would allow
+        assert np.all(a['n_eval'] >= (nl + nr + 1).sum(1))             # every expansion is an evaluation, + one shrinkage draw
+    assert orc.slice_stepout_split(np.float32(1.0 - 2.0 ** -24), 8) == (16, 0) and orc.slice_stepout_split(np.float32(0.0), 8) == (0, 16)
+    assert orc.slice_stepout_split(np.float32(0.5), 8) == (8, 8)
