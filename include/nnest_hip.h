@@ -265,6 +265,63 @@ int nnest_slice_rounds_advance(nnest_slice_rounds_t *h, const float *rows_dev, c
 int nnest_slice_rounds_finish(nnest_slice_rounds_t *h, float *z_dev, float *x_dev, double *logl_dev, int *n_call_dev, int *n_move_dev,
                               int *n_eval_dev, void *stream);
 int nnest_slice_fill_noise(float *dz_dev, int steps, int C, int D, uint64_t seed, uint64_t walker_offset, void *stream);
+
+/* ENSEMBLE sampler: emcee 3's EnsembleSampler with its default StretchMove (RedBlueMove, a = 2, nsplits = 2, randomize_split = True)
+ * in the latent space of the flow, as Sampler._ensemble_sample runs it through emcee (nnest/sampler.py:632-724).  BUILD-DEFINED
+ * STREAM, EMCEE'S MOVE: the draws are this library's Philox4x32-10 words, so parity with emcee is statistical.  N = C walkers z_k in
+ * R^D; step t (global index, 0-based; `step0` is the index of a launch's first step):
+ *   1. split: inds = arange(N) % 2 shuffled by Fisher-Yates, i = N - 1 down to 1: swap inds[i], inds[j], j = (m (i + 1)) >> 24, m = the
+ *      top 24 bits of word (i & 3) of Philox(key seed; counter (i >> 2, t, 0, 4 << 28)).  Set 0 = {k : inds[k] = 0}, set 1 the rest,
+ *      each listed in ascending walker index.
+ *   2. set 0 moves against the current positions of set 1, then set 1 against the updated set 0.  Walker k of the moving set:
+ *      u1, u2, u3 = the top 24 bits of words 0, 1, 2 of Philox(key seed; counter (0, k, t, 3 << 28 | k >> 32)) / 2^24;
+ *      zz = ((a - 1) u1 + 1)^2 / a;  j = member floor(u2 Nc) of the other set (Nc its size);  q = z_j - (z_j - z_k) zz  (float32,
+ *      each operation rounded);  lnpdiff = (D - 1) log zz + lp(q) - lp(z_k) (float64);  the walker moves to q iff lnpdiff > log u3.
+ *   lp(z) (transformed_loglike, sampler.py:674-689): x = f^-1(z), ld = log|det dx/dz|, T(x) = x * t_std + t_mean per dimension
+ *      (float32), logL = safe_loglike(T(x)) (non-finite -> -1e100), prior = 0 if T(x) lies in the box [lo, hi] (NaN inside; no box:
+ *      lo = hi = NULL), else -inf.  constrained = 0: lp = (logL + ld) + prior;  constrained = 1: lp = -inf if logL < loglstar, else
+ *      ld + prior.
+ * A run is a function of the seed: the split of step t depends on (seed, t) only, the uniforms on (seed, walker, t), so neither the
+ * cut into launches nor the route changes it.  Callers refuse N < 2 D, as emcee does.  (All added within ABI 15.)
+ *
+ * work_dev: int32 scratch of nnest_ensemble_work_words(C, steps) words per launch (an error word, one step count per walker, the
+ * split tables of the launch's steps); -1 if the size does not fit an int.
+ * nnest_ensemble_fill_noise: writes the split of steps step0 .. step0 + steps - 1 into work_dev: inds [steps, C] int32 at word
+ * offset nnest_ensemble_work_words(C, 0), then the sets' member lists [steps, C] (set 0 then set 1); u_dev [steps, C, 3] float32
+ * (or NULL) receives u1, u2, u3.  The fused entry builds its own split; the round route calls this first.
+ * nnest_ensemble_max_walkers: the population nnest_ensemble_steps takes for this flow and likelihood id: 4 walkers per workgroup
+ * times the resident workgroups, min(occupancy API, 8, floor(800 / (SGPR granules + 16))) per CU; -1 if the flow's shape is not
+ * the fused route's.
+ * nnest_ensemble_steps: the FUSED route, `steps` steps in one launch, one walker per wave; the default NVP shape (hidden 16,
+ *   3 blocks, 1 layer, scale ''), x_dim <= 128, a known likelihood id (like->scale is ignored: the likelihood sees T(x)).  Walkers
+ *   hand positions to each other inside the launch, so every workgroup must be resident: C > nnest_ensemble_max_walkers is refused
+ *   with NNEST_E_UNSUPPORTED.  z_in_dev [C,D] (read only; not z_out_dev), lp_in_dev [C] or NULL (evaluate lp(z_in)); z_out_dev,
+ *   x_out_dev [C,D], lp_out_dev [C] the last state; hist_z_dev, hist_x_dev [C, steps, D], hist_lp_dev [C, steps] the state after
+ *   every step (required: the hand-off channel); n_accept_dev [C] or NULL.  t_std_dev, t_mean_dev [D].  The call waits for the
+ *   launch: a hand-off wait that runs out (~2 s) ends every wave and returns NNEST_E_HIP.
+ * nnest_ensemble_rounds_propose / _accept: the ROUND route, any flow and any likelihood.  Per half-step (half 0 / 1) of chunk step i
+ *   (global step step0 + i) the moving set has n0 = ceil(C/2) (half 0) or C - n0 (half 1) walkers; its rows are listed in ascending
+ *   walker order.  propose: q_dev [rows, D] = the moving walkers' proposals from z_cur_dev [C,D].  The caller maps them: x, ld =
+ *   f^-1(q) (any flow), logl = safe logL(T(x)) float64, and optionally lprior_dev [rows] float64 (the log prior of T(x); NULL: the box
+ *   on T(x) from lo/hi, no prior if those are NULL too).  accept: the rule; z_cur_dev, x_cur_dev, lp_cur_dev [C] and the history
+ *   rows of step i (hist_* as above) are updated, n_accept_dev [C] counts, acc_rows_dev [rows] (or NULL) flags the rows taken.
+ *   half = -1 in accept is the initial evaluation: rows = all C walkers in order, q = their z; it sets z_cur, x_cur, lp_cur and
+ *   zeroes n_accept. */
+int nnest_ensemble_work_words(int C, int steps);
+int nnest_ensemble_fill_noise(int *work_dev, float *u_dev, int C, int steps, uint64_t step0, uint64_t seed, void *stream);
+int nnest_ensemble_max_walkers(nnest_nvp_t *nvp, int like_id);
+int nnest_ensemble_steps(nnest_nvp_t *nvp, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                         const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, float *z_out_dev, float *x_out_dev,
+                         double *lp_out_dev, float *hist_z_dev, float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *work_dev,
+                         int C, int steps, uint64_t step0, uint64_t seed, int constrained, double loglstar, void *stream);
+int nnest_ensemble_rounds_propose(const int *work_dev, int C, int steps, int D, int i, int half, uint64_t step0, uint64_t seed,
+                                  const float *z_cur_dev, float *q_dev, void *stream);
+int nnest_ensemble_rounds_accept(const int *work_dev, int C, int steps, int D, int i, int half, uint64_t step0, uint64_t seed,
+                                 const float *q_dev, const float *x_dev, const float *ld_dev, const double *logl_dev,
+                                 const double *lprior_dev, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                                 const float *hi_dev, float *z_cur_dev, float *x_cur_dev, double *lp_cur_dev, float *hist_z_dev,
+                                 float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *acc_rows_dev, int constrained,
+                                 double loglstar, void *stream);
 /* size of sync_dev in 8-byte words for a launch of `steps` steps */
 int nnest_mh_sync_words(int steps);
 /* number of adaptation groups nnest_mh_constrained_steps uses for C walkers (size of scale_out_dev) */

@@ -11,5 +11,6 @@ def __getattr__(name):   # the reference's package-level names (nnest/__init__.p
         from .mcmc import MCMCSampler
         return MCMCSampler
     if name == 'EnsembleSampler':
-        raise NotImplementedError('EnsembleSampler (nnest/ensemble.py, an emcee front-end) is outside the scope of this build')
+        from .ensemble import EnsembleSampler
+        return EnsembleSampler
     raise AttributeError(name)

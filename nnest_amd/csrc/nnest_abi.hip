@@ -396,6 +396,92 @@ int nnest_slice_fill_noise(float *dz_dev, int steps, int C, int D, uint64_t seed
     return NNEST_OK;
 }
 
+int nnest_ensemble_work_words(int C, int steps) {
+    if (C < 0 || steps < 0) return -1;
+    const size_t w = ensemble_work_words(C, steps);
+    return w > (size_t)0x7fffffff ? -1 : (int)w;
+}
+
+static int ensemble_sizes(int C, int steps) {
+    if (C < 2 || C > (1 << 16) || steps < 0) return fail(NNEST_E_ARG, "ensemble: C=%d (2..65536 walkers) steps=%d", C, steps);
+    if (nnest_ensemble_work_words(C, steps) < 0) return fail(NNEST_E_ARG, "ensemble: C=%d x steps=%d: the work buffer exceeds 2^31 words", C, steps);
+    return NNEST_OK;
+}
+
+int nnest_ensemble_fill_noise(int *work_dev, float *u_dev, int C, int steps, uint64_t step0, uint64_t seed, void *stream) {
+    int rc = ensemble_sizes(C, steps);
+    if (rc) return rc;
+    if (!work_dev) return fail(NNEST_E_ARG, "NULL work_dev");
+    HIP_TRY(launch_ensemble_split(work_dev, u_dev, C, steps, (uint32_t)step0, seed, (hipStream_t)stream));
+    return NNEST_OK;
+}
+
+int nnest_ensemble_max_walkers(nnest_nvp_t *h, int like_id) {
+    if (!h || !ensemble_form_eligible(h->s)) return -1;
+    int n = 0;
+    if (ensemble_max_walkers(h->s, like_id, h->num_cu, &n) != hipSuccess) return -1;
+    return n;
+}
+
+int nnest_ensemble_steps(nnest_nvp_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                         const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, float *z_out_dev, float *x_out_dev,
+                         double *lp_out_dev, float *hist_z_dev, float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *work_dev,
+                         int C, int steps, uint64_t step0, uint64_t seed, int constrained, double loglstar, void *stream) {
+    if (!h) return fail(NNEST_E_ARG, "NULL handle");
+    int rc = ensemble_sizes(C, steps);
+    if (rc) return rc;
+    LikeSpec lk;
+    if ((rc = check_like(like, h->s.D, &lk))) return rc;
+    lk.scale = 1.0f;
+    if (!t_std_dev || !t_mean_dev || !z_in_dev || !z_out_dev || !x_out_dev || !lp_out_dev || !work_dev ||
+        (steps > 0 && (!hist_z_dev || !hist_x_dev || !hist_lp_dev)))
+        return fail(NNEST_E_ARG, "NULL device buffer");
+    if (!lo_dev != !hi_dev) return fail(NNEST_E_ARG, "lo_dev and hi_dev: both or neither");
+    if ((const void *)z_in_dev == (const void *)z_out_dev) return fail(NNEST_E_ARG, "z_in_dev must not be z_out_dev (partners read it during the launch)");
+    if (!ensemble_form_eligible(h->s))
+        return fail(NNEST_E_UNSUPPORTED, "ensemble: hidden 16, 3 blocks, 1 layer, scale '' (the one-walker-per-wave layout), x_dim <= 128");
+    char msg[400];
+    msg[0] = 0;
+    rc = launch_ensemble(h->s, h->w, lk, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, z_out_dev, x_out_dev, lp_out_dev,
+                         hist_z_dev, hist_x_dev, hist_lp_dev, n_accept_dev, work_dev, C, steps, (uint32_t)step0, seed, constrained ? 1 : 0,
+                         loglstar, h->num_cu, (hipStream_t)stream, msg, sizeof(msg));
+    if (rc) return fail(rc, "%s", msg);
+    return NNEST_OK;
+}
+
+int nnest_ensemble_rounds_propose(const int *work_dev, int C, int steps, int D, int i, int half, uint64_t step0, uint64_t seed,
+                                  const float *z_cur_dev, float *q_dev, void *stream) {
+    int rc = ensemble_sizes(C, steps);
+    if (rc) return rc;
+    if (!work_dev || !z_cur_dev || !q_dev) return fail(NNEST_E_ARG, "NULL device buffer");
+    if (D < 1 || i < 0 || i >= steps || (half != 0 && half != 1)) return fail(NNEST_E_ARG, "D=%d i=%d (steps %d) half=%d", D, i, steps, half);
+    const int rows = half ? C / 2 : (C + 1) / 2;
+    HIP_TRY(launch_ensemble_propose(work_dev, C, steps, D, i, half, (uint32_t)step0, seed, z_cur_dev, q_dev, rows, (hipStream_t)stream));
+    return NNEST_OK;
+}
+
+int nnest_ensemble_rounds_accept(const int *work_dev, int C, int steps, int D, int i, int half, uint64_t step0, uint64_t seed,
+                                 const float *q_dev, const float *x_dev, const float *ld_dev, const double *logl_dev,
+                                 const double *lprior_dev, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                                 const float *hi_dev, float *z_cur_dev, float *x_cur_dev, double *lp_cur_dev, float *hist_z_dev,
+                                 float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *acc_rows_dev, int constrained,
+                                 double loglstar, void *stream) {
+    int rc = ensemble_sizes(C, steps);
+    if (rc) return rc;
+    if (D < 1 || half < -1 || half > 1 || (half >= 0 && (i < 0 || i >= steps))) return fail(NNEST_E_ARG, "D=%d i=%d (steps %d) half=%d", D, i, steps, half);
+    if (!work_dev || !q_dev || !x_dev || !ld_dev || !logl_dev || !z_cur_dev || !x_cur_dev || !lp_cur_dev ||
+        (half >= 0 && (!hist_z_dev || !hist_x_dev || !hist_lp_dev)))
+        return fail(NNEST_E_ARG, "NULL device buffer");
+    if (!lo_dev != !hi_dev) return fail(NNEST_E_ARG, "lo_dev and hi_dev: both or neither");
+    if (lo_dev && !lprior_dev && (!t_std_dev || !t_mean_dev)) return fail(NNEST_E_ARG, "the box needs t_std_dev and t_mean_dev");
+    const int rows = half < 0 ? C : half ? C / 2 : (C + 1) / 2;
+    HIP_TRY(launch_ensemble_accept(work_dev, C, steps, D, half < 0 ? 0 : i, half, (uint32_t)step0, seed, q_dev, x_dev, ld_dev, logl_dev,
+                                   lprior_dev, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_cur_dev, x_cur_dev, lp_cur_dev, hist_z_dev,
+                                   hist_x_dev, hist_lp_dev, n_accept_dev, acc_rows_dev, constrained ? 1 : 0, loglstar, rows,
+                                   (hipStream_t)stream));
+    return NNEST_OK;
+}
+
 int nnest_mh_form_for(const nnest_nvp_t *h, int C, int flags) {
     if (!h || C < 1) return -1;
     return mh_form_for(h->s, C, flags, h->num_cu);

@@ -1,0 +1,588 @@
+// nnest_ensemble.hip -- emcee's affine-invariant STRETCH MOVE (Goodman & Weare 2010; emcee 3 EnsembleSampler with its default
+// StretchMove: RedBlueMove, a = 2, nsplits = 2, randomize_split = True) in the latent space of the trained flow, as the reference's
+// Sampler._ensemble_sample runs it through emcee (nnest/sampler.py:632-724).  BUILD-DEFINED STREAM, EMCEE'S MOVE: the draws are
+// Philox4x32-10 words of this library, so parity with emcee is statistical (its random streams cannot be reproduced).
+//
+// Definition (include/nnest_hip.h has it in full).  N walkers z_k in R^D, step t (global index, 0-based):
+//   split:    inds = arange(N) % 2 shuffled by Fisher-Yates from i = N - 1 down to 1, j = (m_i (i + 1)) >> 24 with m_i the top 24 bits
+//             of word (i & 3) of Philox(seed; i >> 2, t, 0, stream 4): set 0 = {k : inds_k = 0} (ceil(N/2) walkers), set 1 the rest,
+//             each listed in ascending walker index;
+//   half 0:   every walker k of set 0 against the current positions of set 1, then half 1: set 1 against the updated set 0;
+//             u1, u2, u3 = the top 24 bits of words x, y, z of Philox(seed; 0, k, t, stream 3 | k >> 32) / 2^24;
+//             zz = ((a - 1) u1 + 1)^2 / a;  j = member (m2 Nc) >> 24 (= floor(u2 Nc)) of the other set;  q = z_j - (z_j - z_k) zz
+//             (float32, no contraction);  lnpdiff = (D - 1) log zz + lp(q) - lp(z_k) (float64);  accept iff lnpdiff > log u3.
+//   lp(z):    x = f^-1(z), ld = log|det dx/dz|, T(x) = x std + mean per dimension (float32, no contraction), logL = safe_loglike(T(x))
+//             (non-finite -> -1e100), prior = 0 inside the box on T(x) (or no box), -inf outside;
+//             loglstar unset: lp = (logL + ld) + prior;  set: lp = -inf if logL < loglstar, else ld + prior (sampler.py:674-689).
+//
+// Two routes run that definition with the same draws:
+//   FUSED (ensemble_kernel): the default NVP shape of the solo layout (nnest_solo.hip: one walker per wave, the coupling inverse and
+//     the likelihood in the wave's registers), every step of a chunk in ONE launch.  A walker of the moving half reads its partner's
+//     position from the partner's history row: the partner publishes each finished step with an agent-scope release (its stores,
+//     one release fence, one relaxed sc1 store of its step count) and the reader polls that count from one lane, relaxed, with
+//     s_sleep, then takes one agent-scope acquire before reading the row (cdna_hip_programming.md Guideline 16, handoff-flag).  A
+//     set-0 walker of step t needs its partner's position after step t - 1, a set-1 walker its partner's after step t, which only
+//     waits on steps before t: every dependency points to an earlier (step, half), so the launch completes when every workgroup is
+//     resident -- the launcher refuses populations beyond the resident grid.  History rows are never overwritten in a launch, so
+//     there is no write-after-read hazard.  Every poll is bounded in wall-clock time; one that runs out sets the error word, and
+//     every waiting wave then leaves.
+//   ROUNDS (ensemble_propose_kernel / ensemble_accept_kernel): any flow, any likelihood.  Per half-step the propose kernel writes the
+//     moving set's proposals (rows in ascending walker order), the caller maps them through the flow's inverse and the likelihood,
+//     and the accept kernel applies the rule and writes the history.
+// Both read the split from one table (ensemble_split_kernel), built per chunk for its steps: a run is a function of the seed, not of
+// its chunking or its route.
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "flow_tile.h"
+#include "nnest_internal.h"
+#include "solo_loglike.h"
+#include "solo_tile.h"
+
+namespace nnest {
+
+enum { NOISE_STREAM_ENSEMBLE = 3, NOISE_STREAM_ENSEMBLE_SPLIT = 4 };
+constexpr float ENS_A = 2.0f;                  // the stretch scale a (emcee's default)
+constexpr long long ENS_SPIN_TICKS = 200000000;   // a hand-off wait gives up after ~2 s of the 100 MHz wall clock
+constexpr int ENS_CTRL_WORDS = 4;              // work: [error word, pad x 3][tags, padded to 4 words][inds S x N][members S x N]
+
+__host__ __device__ inline int ens_tags_words(int C) { return (C + 3) & ~3; }
+__host__ __device__ inline size_t ens_split_off(int C) { return (size_t)ENS_CTRL_WORDS + ens_tags_words(C); }
+
+// the walker's three uniforms of step t (24-bit fractions: exact in float32)
+struct EnsU { float u1, u2, u3; uint32_t m2; };
+__device__ __forceinline__ EnsU ens_uniforms(uint64_t seed, uint64_t walker, uint32_t t) {
+    u32x4 c;
+    c.x = 0;
+    c.y = (uint32_t)walker;
+    c.z = t;
+    c.w = ((uint32_t)(walker >> 32) & 0x0fffffffu) | ((uint32_t)NOISE_STREAM_ENSEMBLE << 28);
+    const u32x4 r = philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    EnsU u;
+    u.u1 = (float)(r.x >> 8) * 5.9604644775390625e-08f;
+    u.m2 = r.y >> 8;
+    u.u2 = (float)u.m2 * 5.9604644775390625e-08f;
+    u.u3 = (float)(r.z >> 8) * 5.9604644775390625e-08f;
+    return u;
+}
+
+#pragma clang fp contract(off)
+__device__ __forceinline__ float ens_zz(float u1) {
+    const float s = (ENS_A - 1.0f) * u1 + 1.0f;
+    return s * s / ENS_A;
+}
+__device__ __forceinline__ float ens_propose(float zj, float zk, float zz) { return zj - (zj - zk) * zz; }
+__device__ __forceinline__ float ens_T(float x, float sd, float mu) { return x * sd + mu; }
+// the latent log target from logL (already safe), the log-det and the prior's verdict
+__device__ __forceinline__ double ens_target(double logl, float ld, bool in_prior, int constrained, double loglstar) {
+    const double prior = in_prior ? 0.0 : -INFINITY;
+    if (constrained) return logl < loglstar ? -INFINITY : (double)ld + prior;
+    return (logl + (double)ld) + prior;
+}
+__device__ __forceinline__ bool ens_accept(double lp_new, double lp_old, float zz, float u3, int D) {
+    const double lnpdiff = (double)(D - 1) * log((double)zz) + lp_new - lp_old;
+    return lnpdiff > log((double)u3);
+}
+#pragma clang fp contract(fast)
+
+// ---- the split of each step of a chunk: one wave per step, the population shuffled in LDS, one byte per walker (hence at most
+// 65536 walkers: nnest_abi.hip) ----
+__global__ void __launch_bounds__(64) ensemble_split_kernel(int *__restrict__ work, int C, int S, uint32_t step0, uint64_t seed) {
+    extern __shared__ unsigned char inds_lds[];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= S) return;
+    const uint32_t t = step0 + (uint32_t)i;
+    __shared__ uint32_t words[256];
+    for (int k = lane; k < C; k += 64) inds_lds[k] = (unsigned char)(k & 1);
+    // Fisher-Yates, i = C - 1 .. 1, in windows of 256 indices [256 w, 256 w + 255]: the wave draws the window's 64 Philox blocks
+    // (256 words) at once, lane 0 swaps
+    for (int w = (C - 1) >> 8; w >= 0; --w) {
+        const int lo = 256 * w > 1 ? 256 * w : 1, hi = 256 * w + 255 < C - 1 ? 256 * w + 255 : C - 1;
+        const int b0 = 64 * w;
+        const int b = b0 + lane;
+        if (4 * b <= hi) {
+            u32x4 c;
+            c.x = (uint32_t)b;
+            c.y = t;
+            c.z = 0;
+            c.w = (uint32_t)NOISE_STREAM_ENSEMBLE_SPLIT << 28;
+            const u32x4 r = philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+            words[4 * lane + 0] = r.x;
+            words[4 * lane + 1] = r.y;
+            words[4 * lane + 2] = r.z;
+            words[4 * lane + 3] = r.w;
+        }
+        __syncthreads();
+        if (lane == 0) {
+            for (int ii = hi; ii >= lo; --ii) {
+                const uint32_t m = words[ii - 4 * b0] >> 8;
+                const int j = (int)(((uint64_t)m * (uint64_t)(ii + 1)) >> 24);
+                const unsigned char a = inds_lds[ii];
+                inds_lds[ii] = inds_lds[j];
+                inds_lds[j] = a;
+            }
+        }
+        __syncthreads();
+    }
+    // the sets in ascending walker order: set 0 at members[0 .. n0), set 1 at members[n0 .. C)
+    int *inds = work + ens_split_off(C) + (size_t)i * C;
+    int *members = work + ens_split_off(C) + (size_t)S * C + (size_t)i * C;
+    const int n0 = (C + 1) / 2;
+    int c0 = 0, c1 = 0;   // wave-uniform
+    for (int k0 = 0; k0 < C; k0 += 64) {
+        const int k = k0 + lane;
+        const int s = k < C ? inds_lds[k] : -1;
+        const unsigned long long m0 = __ballot(s == 0), m1 = __ballot(s == 1);
+        const uint32_t below0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, 0u));
+        const uint32_t below1 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, 0u));
+        if (k < C) {
+            inds[k] = s;
+            if (s == 0) members[c0 + below0] = k;
+            else members[n0 + c1 + below1] = k;
+        }
+        c0 += __popcll(m0);
+        c1 += __popcll(m1);
+    }
+}
+
+// the uniforms, exported for the checker: u [S][C][3]
+__global__ void ensemble_fill_u_kernel(float *__restrict__ u, int C, int S, uint32_t step0, uint64_t seed) {
+    const long n = (long)S * C;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        const int k = (int)(e % C), i = (int)(e / C);
+        const EnsU v = ens_uniforms(seed, (uint64_t)k, step0 + (uint32_t)i);
+        u[3 * e + 0] = v.u1;
+        u[3 * e + 1] = v.u2;
+        u[3 * e + 2] = v.u3;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// FUSED route: one walker per wave (the solo layout of nnest_solo.hip: lane = 32 n + 16 h + p holds dims 2U p + 2u + c; the four
+// (n, h) rows hold copies), four walkers per workgroup.
+struct EnsArgs {
+    FlowShape s;
+    const float *packed;
+    LikeSpec like;                  // scale 1: the likelihood sees T(x)
+    const float *t_std, *t_mean;    // [D]
+    const float *lo, *hi;           // the prior box on T(x) [D], or NULL (no prior)
+    const float *z_in;              // [C][D], read only (a partner may still read it after this walker has finished)
+    const double *lp_in;            // [C] or NULL: evaluate lp(z_in)
+    float *z_out, *x_out;           // [C][D]
+    double *lp_out;                 // [C]
+    float *hist_z, *hist_x;         // [C][S][D]
+    double *hist_lp;                // [C][S]
+    int *n_accept;                  // [C]
+    int *work;
+    int C, S, constrained;
+    uint32_t step0;
+    uint64_t seed;
+    double loglstar;
+};
+
+template <int U, int LK>
+__global__ void __launch_bounds__(256) ensemble_kernel(EnsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float wlds[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int D = a.s.D, S = a.S, C = a.C;
+    constexpr bool LDSW = U >= 3;   // (solo_lds_weights<U, 4>: x_dim > 64 keeps the weights in LDS)
+    {
+        if constexpr (!LDSW) {
+            const int n = a.s.nets_params();
+            for (int i = threadIdx.x; i < n; i += blockDim.x) wlds[i] = a.packed[i];
+        } else if (wave < 3) {
+            SoloNet<U> nb;
+            solo_gather<U>(nb, a.packed + (size_t)(wave * 2 + (lane >= 32 ? 1 : 0)) * a.s.net_params, D, (wave + 1) & 1, wave & 1, lane);
+            solo4_store<U>(wlds, wave, nb, lane);
+        }
+    }
+    __syncthreads();
+    const int pos = lane & 15;
+    const bool translate_half = lane >= 32, writer_lane = lane < 16;
+    const int row = blockIdx.x * 4 + wave;
+    if (row >= C) return;   // (no barrier behind this point)
+    SoloNet<U> net[LDSW ? 1 : 3];
+    if constexpr (!LDSW) {
+#pragma unroll
+        for (int b = 0; b < 3; ++b)
+            solo_gather<U>(net[b], wlds + (size_t)(b * 2 + (translate_half ? 1 : 0)) * a.s.net_params, D, (b + 1) & 1, b & 1, lane);
+    }
+    const unsigned sel = translate_half ? 0xffffffffu : 0u;
+    const bool h1 = (lane & 16) != 0;
+    auto inverse = [&](float (&xs)[2][U]) {   // NormalizingFlow.inverse (networks.py:34-42), blocks 2, 1, 0
+        if constexpr (LDSW) {
+            float ld = solo_coupling_inverse4<U>(Solo4Lds{wlds + (size_t)2 * SOLO4_NF * 64, lane}, sel, h1, xs[1], xs[0]);
+            ld += solo_coupling_inverse4<U>(Solo4Lds{wlds + (size_t)1 * SOLO4_NF * 64, lane}, sel, h1, xs[0], xs[1]);
+            ld += solo_coupling_inverse4<U>(Solo4Lds{wlds, lane}, sel, h1, xs[1], xs[0]);
+            return ld;
+        } else {
+            float ld = solo_coupling_inverse<U>(net[2], sel, h1, xs[1], xs[0]);
+            ld += solo_coupling_inverse<U>(net[1], sel, h1, xs[0], xs[1]);
+            ld += solo_coupling_inverse<U>(net[0], sel, h1, xs[1], xs[0]);
+            return ld;
+        }
+    };
+    // this lane's dims: T, the box
+    float sd[2][U], mu[2][U], blo[2][U], bhi[2][U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int d = 2 * U * pos + 2 * u + c;
+            const bool v = d < D;
+            sd[c][u] = v ? a.t_std[d] : 0.f;
+            mu[c][u] = v ? a.t_mean[d] : 0.f;
+            blo[c][u] = v && a.lo ? a.lo[d] : -INFINITY;
+            bhi[c][u] = v && a.hi ? a.hi[d] : INFINITY;
+        }
+    LikeSpec like = a.like;
+    like.scale = 1.0f;
+    // x <- f^-1(x) in place; returns lp
+    auto target = [&](float (&xs)[2][U]) -> double {
+        const float ld = solo_logdet_total(inverse(xs));
+        float tx[2][U];
+        int ok = 1;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                tx[c][u] = ens_T(xs[c][u], sd[c][u], mu[c][u]);
+                ok &= !(tx[c][u] < blo[c][u] || tx[c][u] > bhi[c][u]);   // (NaN counts as inside: UniformPrior, priors.py)
+            }
+        const bool in_prior = __ballot(ok != 0) == ~0ull;
+        const double logl = solo_loglike<U, LK>(like, D, lane, tx);
+        return ens_target(logl, ld, in_prior, a.constrained, a.loglstar);
+    };
+    auto load_row = [&](const float *base, float (&v)[2][U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int d = 2 * U * pos + 2 * u + c;
+                v[c][u] = d < D ? base[d] : 0.f;
+            }
+    };
+    auto store_row = [&](float *base, const float (&v)[2][U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int d = 2 * U * pos + 2 * u + c;
+                if (d < D) base[d] = v[c][u];
+            }
+    };
+    int *err = a.work;
+    unsigned *tags = reinterpret_cast<unsigned *>(a.work + ENS_CTRL_WORDS);
+    const int *inds = a.work + ens_split_off(C);
+    const int *members = inds + (size_t)S * C;
+    const int n0 = (C + 1) / 2;
+
+    float z[2][U], x[2][U];
+    load_row(a.z_in + (size_t)row * D, z);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) x[c][u] = z[c][u];
+    double lp = target(x);
+    if (a.lp_in) lp = a.lp_in[row];
+    int n_acc = 0;
+    for (int i = 0; i < S; ++i) {
+        const uint32_t t = a.step0 + (uint32_t)i;
+        const int set = __builtin_amdgcn_readfirstlane(inds[(size_t)i * C + row]);
+        const int Nc = set ? n0 : C - n0, cbase = set ? 0 : n0;
+        const EnsU u = ens_uniforms(a.seed, (uint64_t)row, t);
+        const int jr = (int)(((uint64_t)u.m2 * (uint64_t)Nc) >> 24);
+        const int j = __builtin_amdgcn_readfirstlane(members[(size_t)i * C + cbase + jr]);
+        const unsigned need = set ? (unsigned)i + 1u : (unsigned)i;   // the partner's position after step t - 1 (set 0) or t (set 1)
+        if (need > 0) {
+            int good = 1;
+            if (lane == 0) {
+                unsigned polls = 0;
+                const long long t0 = wall_clock64();
+                while (__hip_atomic_load(&tags[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
+                    __builtin_amdgcn_s_sleep(1);
+                    if ((++polls & 63) == 0 &&
+                        (wall_clock64() - t0 > ENS_SPIN_TICKS || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+                        __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        good = 0;
+                        break;
+                    }
+                }
+            }
+            if (!__builtin_amdgcn_readfirstlane(good)) return;   // a hand-off wait ran out: the call reports it
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        }
+        float zj[2][U];
+        load_row(need == 0 ? a.z_in + (size_t)j * D : a.hist_z + ((size_t)j * S + (need - 1)) * D, zj);
+        const float zz = ens_zz(u.u1);
+        float q[2][U], xq[2][U];
+#pragma unroll
+        for (int uu = 0; uu < U; ++uu)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                q[c][uu] = ens_propose(zj[c][uu], z[c][uu], zz);
+                xq[c][uu] = q[c][uu];
+            }
+        const double lpq = target(xq);
+        if (ens_accept(lpq, lp, zz, u.u3, D)) {
+#pragma unroll
+            for (int uu = 0; uu < U; ++uu)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) { z[c][uu] = q[c][uu]; x[c][uu] = xq[c][uu]; }
+            lp = lpq;
+            n_acc += 1;
+        }
+        const size_t hr = (size_t)row * S + i;
+        if (writer_lane) {
+            store_row(a.hist_z + hr * D, z);
+            store_row(a.hist_x + hr * D, x);
+            if (pos == 0) a.hist_lp[hr] = lp;
+        }
+        // publish: the wave's stores, then its step count (release: one fence for the whole wave, one relaxed sc1 store)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        if (lane == 0) __hip_atomic_store(&tags[row], (unsigned)i + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (writer_lane) {
+        store_row(a.z_out + (size_t)row * D, z);
+        store_row(a.x_out + (size_t)row * D, x);
+        if (pos == 0) {
+            a.lp_out[row] = lp;
+            if (a.n_accept) a.n_accept[row] = n_acc;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// ROUND route: one wave per moving row, each lane the dims lane, lane + 64, ...
+struct EnsRoundArgs {
+    const int *work;
+    int C, S, D, i, half;   // chunk step i (global step step0 + i); half 0 / 1 (-1: the initial evaluation, rows = walkers)
+    uint32_t step0;
+    uint64_t seed;
+};
+
+__device__ __forceinline__ int ens_row_walker(const EnsRoundArgs &a, int r) {
+    if (a.half < 0) return r;
+    const int *members = a.work + ens_split_off(a.C) + (size_t)a.S * a.C + (size_t)a.i * a.C;
+    return members[(a.half ? (a.C + 1) / 2 : 0) + r];
+}
+
+__global__ void __launch_bounds__(256) ensemble_propose_kernel(EnsRoundArgs a, const float *__restrict__ z_cur, float *__restrict__ q, int rows) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int C = a.C, D = a.D, n0 = (C + 1) / 2;
+    const int k = ens_row_walker(a, r);
+    const int Nc = a.half ? n0 : C - n0, cbase = a.half ? 0 : n0;
+    const EnsU u = ens_uniforms(a.seed, (uint64_t)k, a.step0 + (uint32_t)a.i);
+    const int jr = (int)(((uint64_t)u.m2 * (uint64_t)Nc) >> 24);
+    const int j = a.work[ens_split_off(C) + (size_t)a.S * C + (size_t)a.i * C + cbase + jr];
+    const float zz = ens_zz(u.u1);
+    for (int d = lane; d < D; d += 64) q[(size_t)r * D + d] = ens_propose(z_cur[(size_t)j * D + d], z_cur[(size_t)k * D + d], zz);
+}
+
+struct EnsAcceptArgs {
+    const float *q, *x, *ld;        // the rows: proposals, f^-1, log|det|
+    const double *logl;             // safe logL of the rows
+    const double *lprior;           // log prior of the rows (the caller's), or NULL: the box below
+    const float *t_std, *t_mean, *lo, *hi;   // the box on T(x) (lo / hi NULL: no prior)
+    float *z_cur, *x_cur;
+    double *lp_cur;
+    float *hist_z, *hist_x;         // [C][S][D]
+    double *hist_lp;                // [C][S]
+    int *n_accept;                  // [C]
+    int *acc_rows;                  // [rows] or NULL: 1 where the row's walker moved
+    int constrained;
+    double loglstar;
+};
+
+__global__ void __launch_bounds__(256) ensemble_accept_kernel(EnsRoundArgs a, EnsAcceptArgs b, int rows) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int D = a.D;
+    const int k = ens_row_walker(a, r);
+    const float *xr = b.x + (size_t)r * D;
+    bool in_prior = true;
+    if (b.lprior) {
+        in_prior = !(b.lprior[r] == -INFINITY);
+    } else if (b.lo) {
+        int ok = 1;
+        for (int d = lane; d < D; d += 64) {
+            const float tx = ens_T(xr[d], b.t_std[d], b.t_mean[d]);
+            ok &= !(tx < b.lo[d] || tx > b.hi[d]);
+        }
+        in_prior = __ballot(ok != 0) == ~0ull;
+    }
+    double lp_new = ens_target(b.logl[r], b.ld[r], in_prior, b.constrained, b.loglstar);
+    if (b.lprior && in_prior) lp_new = lp_new + b.lprior[r];   // (a prior density other than 0 / -inf: sampler.py:687-689 adds it)
+    bool moved;
+    if (a.half < 0) {
+        moved = true;
+    } else {
+        const EnsU u = ens_uniforms(a.seed, (uint64_t)k, a.step0 + (uint32_t)a.i);
+        moved = ens_accept(lp_new, b.lp_cur[k], ens_zz(u.u1), u.u3, D);
+    }
+    const float *qr = b.q + (size_t)r * D;
+    if (moved) {
+        for (int d = lane; d < D; d += 64) {
+            b.z_cur[(size_t)k * D + d] = qr[d];
+            b.x_cur[(size_t)k * D + d] = xr[d];
+        }
+    }
+    if (a.half >= 0) {
+        const size_t hr = (size_t)k * a.S + a.i;
+        for (int d = lane; d < D; d += 64) {
+            b.hist_z[hr * D + d] = moved ? qr[d] : b.z_cur[(size_t)k * D + d];
+            b.hist_x[hr * D + d] = moved ? xr[d] : b.x_cur[(size_t)k * D + d];
+        }
+    }
+    if (lane == 0) {
+        const double lp = moved ? lp_new : b.lp_cur[k];
+        b.lp_cur[k] = lp;
+        if (a.half >= 0) {
+            b.hist_lp[(size_t)k * a.S + a.i] = lp;
+            if (b.n_accept) b.n_accept[k] += moved ? 1 : 0;
+        } else if (b.n_accept) {
+            b.n_accept[k] = 0;
+        }
+        if (b.acc_rows) b.acc_rows[r] = moved ? 1 : 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+size_t ensemble_work_words(int C, int S) { return ens_split_off(C) + 2 * (size_t)S * C; }
+
+hipError_t launch_ensemble_split(int *work, float *u, int C, int S, uint32_t step0, uint64_t seed, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(work, 0, ens_split_off(C) * sizeof(int), st);   // the error word and the tags
+    if (e != hipSuccess) return e;
+    if (S > 0) {
+        hipLaunchKernelGGL(ensemble_split_kernel, dim3(S), dim3(64), (size_t)C, st, work, C, S, step0, seed);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (u && S > 0) {
+        hipLaunchKernelGGL(ensemble_fill_u_kernel, dim3(256), dim3(256), 0, st, u, C, S, step0, seed);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
+bool ensemble_form_eligible(const FlowShape &s) { return slice_form_eligible(s); }
+
+template <int U, int LK>
+static size_t ens_lds(const FlowShape &s) {
+    return U >= 3 ? (size_t)3 * SOLO4_NF * 64 * sizeof(float) : (size_t)s.nets_params() * sizeof(float);
+}
+
+// resident 256-thread workgroups per CU: min(the occupancy API, 8, floor(800 / (SGPR granules + 16))) (MI355X_MICROARCH.md,
+// "Residency and cooperative launch").  The runtime does not report a kernel's SGPRs, so the SGPR term is taken at the ceiling a
+// wave can allocate (102 -> 112 in granules of 16): 6 per CU; the kernels use far fewer and their VGPRs bind first.
+constexpr int ENS_SGPR_CEIL = 112;
+template <int U, int LK>
+static hipError_t ens_blocks_per_cu(const FlowShape &s, int *out) {
+    const void *fn = reinterpret_cast<const void *>(ensemble_kernel<U, LK>);
+    const size_t lds = ens_lds<U, LK>(s);
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    int n = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, lds);
+    if (e != hipSuccess) return e;
+    const int sg = 800 / (ENS_SGPR_CEIL + 16);
+    *out = n < 8 ? (n < sg ? n : sg) : (8 < sg ? 8 : sg);
+    return hipSuccess;
+}
+
+template <int U, int LK>
+static hipError_t ens_launch_k(const EnsArgs &a, int num_cu, bool launch, int *max_walkers, hipStream_t st) {
+    int per_cu = 0;
+    hipError_t e = ens_blocks_per_cu<U, LK>(a.s, &per_cu);
+    if (e != hipSuccess) return e;
+    *max_walkers = 4 * per_cu * num_cu;
+    if (!launch) return hipSuccess;
+    const size_t lds = ens_lds<U, LK>(a.s);
+    hipLaunchKernelGGL((ensemble_kernel<U, LK>), dim3((a.C + 3) / 4), dim3(256), lds, st, a);
+    return hipGetLastError();
+}
+
+// launch (when `launch` and C fits) or only size: *max_walkers = the resident population of the instantiation the call would run
+static hipError_t ens_dispatch(const EnsArgs &a, int num_cu, bool launch, int *max_walkers, hipStream_t st) {
+    const bool rosen = a.like.id == NNEST_LIKE_ROSENBROCK;
+    switch (a.s.NT) {
+        case 1: return rosen ? ens_launch_k<1, NNEST_LIKE_ROSENBROCK>(a, num_cu, launch, max_walkers, st) : ens_launch_k<1, -1>(a, num_cu, launch, max_walkers, st);
+        case 2: return rosen ? ens_launch_k<2, NNEST_LIKE_ROSENBROCK>(a, num_cu, launch, max_walkers, st) : ens_launch_k<2, -1>(a, num_cu, launch, max_walkers, st);
+        case 3: return rosen ? ens_launch_k<3, NNEST_LIKE_ROSENBROCK>(a, num_cu, launch, max_walkers, st) : ens_launch_k<3, -1>(a, num_cu, launch, max_walkers, st);
+        case 4: return rosen ? ens_launch_k<4, NNEST_LIKE_ROSENBROCK>(a, num_cu, launch, max_walkers, st) : ens_launch_k<4, -1>(a, num_cu, launch, max_walkers, st);
+    }
+    return hipErrorInvalidConfiguration;
+}
+
+hipError_t ensemble_max_walkers(const FlowShape &s, int like_id, int num_cu, int *out) {
+    EnsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.s = s;
+    a.like.id = like_id;
+    return ens_dispatch(a, num_cu, false, out, 0);
+}
+
+int launch_ensemble(const FlowShape &s, const float *packed, const LikeSpec &like, const float *t_std, const float *t_mean, const float *lo,
+                    const float *hi, const float *z_in, const double *lp_in, float *z_out, float *x_out, double *lp_out, float *hist_z,
+                    float *hist_x, double *hist_lp, int *n_accept, int *work, int C, int S, uint32_t step0, uint64_t seed, int constrained,
+                    double loglstar, int num_cu, hipStream_t st, char *msg, size_t msg_len) {
+    EnsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.s = s; a.packed = packed; a.like = like; a.t_std = t_std; a.t_mean = t_mean; a.lo = lo; a.hi = hi;
+    a.z_in = z_in; a.lp_in = lp_in; a.z_out = z_out; a.x_out = x_out; a.lp_out = lp_out;
+    a.hist_z = hist_z; a.hist_x = hist_x; a.hist_lp = hist_lp; a.n_accept = n_accept; a.work = work;
+    a.C = C; a.S = S; a.constrained = constrained; a.step0 = step0; a.seed = seed; a.loglstar = loglstar;
+    int max_walkers = 0;
+    hipError_t e = ens_dispatch(a, num_cu, false, &max_walkers, st);
+    if (e != hipSuccess) { snprintf(msg, msg_len, "occupancy query: %s", hipGetErrorString(e)); return NNEST_E_HIP; }
+    if (C > max_walkers) {
+        snprintf(msg, msg_len, "ensemble: %d walkers > %d resident (one walker per wave, every workgroup resident); the round route takes it",
+                 C, max_walkers);
+        return NNEST_E_UNSUPPORTED;
+    }
+    if ((e = launch_ensemble_split(work, nullptr, C, S, step0, seed, st)) != hipSuccess) {
+        snprintf(msg, msg_len, "split: %s", hipGetErrorString(e));
+        return NNEST_E_HIP;
+    }
+    if ((e = ens_dispatch(a, num_cu, true, &max_walkers, st)) != hipSuccess) {
+        snprintf(msg, msg_len, "ensemble_kernel: %s", hipGetErrorString(e));
+        return NNEST_E_HIP;
+    }
+    int host_err = 0;
+    if ((e = hipMemcpyAsync(&host_err, work, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess) {
+        snprintf(msg, msg_len, "ensemble_kernel: %s", hipGetErrorString(e));
+        return NNEST_E_HIP;
+    }
+    if (host_err) {
+        snprintf(msg, msg_len, "ensemble_kernel: a hand-off wait ran out (a workgroup was not resident?); the outputs are incomplete");
+        return NNEST_E_HIP;
+    }
+    return NNEST_OK;
+}
+
+hipError_t launch_ensemble_propose(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const float *z_cur,
+                                   float *q, int rows, hipStream_t st) {
+    if (rows <= 0) return hipSuccess;
+    EnsRoundArgs a = {work, C, S, D, i, half, step0, seed};
+    hipLaunchKernelGGL(ensemble_propose_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, a, z_cur, q, rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_ensemble_accept(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const float *q,
+                                  const float *x, const float *ld, const double *logl, const double *lprior, const float *t_std,
+                                  const float *t_mean, const float *lo, const float *hi, float *z_cur, float *x_cur, double *lp_cur,
+                                  float *hist_z, float *hist_x, double *hist_lp, int *n_accept, int *acc_rows, int constrained,
+                                  double loglstar, int rows, hipStream_t st) {
+    if (rows <= 0) return hipSuccess;
+    EnsRoundArgs a = {work, C, S, D, i, half, step0, seed};
+    EnsAcceptArgs b = {q, x, ld, logl, lprior, t_std, t_mean, lo, hi, z_cur, x_cur, lp_cur, hist_z, hist_x, hist_lp, n_accept, acc_rows,
+                       constrained, loglstar};
+    hipLaunchKernelGGL(ensemble_accept_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, a, b, rows);
+    return hipGetLastError();
+}
+
+}  // namespace nnest

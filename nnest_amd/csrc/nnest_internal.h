@@ -89,5 +89,21 @@ hipError_t launch_slice_solo(const FlowShape &s, const float *packed, const Like
                              float width, int steps, int C, int max_out, int max_shrink, uint64_t seed, uint64_t walker_offset,
                              const float *noise_dz, float *hist_x, int *n_call, int *n_move, int *n_eval, hipStream_t st);
 hipError_t launch_slice_fill_noise(float *dz, int steps, int C, int D, uint64_t seed, uint64_t walker_offset, hipStream_t st);
+// ensemble sampler, emcee's stretch move in latent space (nnest_ensemble.hip)
+size_t ensemble_work_words(int C, int S);
+bool ensemble_form_eligible(const FlowShape &s);
+hipError_t ensemble_max_walkers(const FlowShape &s, int like_id, int num_cu, int *out);
+hipError_t launch_ensemble_split(int *work, float *u, int C, int S, uint32_t step0, uint64_t seed, hipStream_t st);
+int launch_ensemble(const FlowShape &s, const float *packed, const LikeSpec &like, const float *t_std, const float *t_mean, const float *lo,
+                    const float *hi, const float *z_in, const double *lp_in, float *z_out, float *x_out, double *lp_out, float *hist_z,
+                    float *hist_x, double *hist_lp, int *n_accept, int *work, int C, int S, uint32_t step0, uint64_t seed, int constrained,
+                    double loglstar, int num_cu, hipStream_t st, char *msg, size_t msg_len);
+hipError_t launch_ensemble_propose(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const float *z_cur,
+                                   float *q, int rows, hipStream_t st);
+hipError_t launch_ensemble_accept(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const float *q,
+                                  const float *x, const float *ld, const double *logl, const double *lprior, const float *t_std,
+                                  const float *t_mean, const float *lo, const float *hi, float *z_cur, float *x_cur, double *lp_cur,
+                                  float *hist_z, float *hist_x, double *hist_lp, int *n_accept, int *acc_rows, int constrained,
+                                  double loglstar, int rows, hipStream_t st);
 
 }  // namespace nnest

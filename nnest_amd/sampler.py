@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .priors import UniformPrior
 from .utils import create_logger, get_or_create_run_dir, write_rows_e5
 
 
@@ -715,6 +716,126 @@ class Sampler(object):
             if j is not None:
                 return x[j:j + 1], lj, dj, ncall
             block = min(4 * block, 65536)
+
+    # ---- ensemble sampling (sampler.py:632-724): emcee's stretch move in latent space, build-defined stream -----------------
+    ENSEMBLE_HISTORY_BYTES = 256 << 20   # device history per launch; longer runs are cut into launches of fewer steps
+
+    def _ensemble_affine(self):
+        """T as (std, mean) per dimension when the transform is x * std + mean (EnsembleSampler.run installs one), else None"""
+        aff = getattr(self, '_ensemble_transform', None)
+        if aff is not None:
+            return aff
+        if self._user_transform is None:
+            return np.ones(self.x_dim), np.zeros(self.x_dim)
+        if self._linear_scale is not None:
+            return np.full(self.x_dim, self._linear_scale), np.zeros(self.x_dim)
+        return None
+
+    def _ensemble_device_like(self, affine):
+        """(like_id, like_params, lo, hi) when the likelihood and the prior run on the device for the transform `affine`, else None:
+        a likelihood the kernels know (checked against the host callable), no derived parameters, and no prior or a box on T(x)"""
+        like = self._user_loglike
+        like_id = getattr(like, 'hip_like_id', None)
+        if like_id is None or affine is None or self.num_derived != 0:
+            return None
+        prior = self._user_prior
+        lo = hi = None
+        if prior is not None:
+            if not (self._transform_prior and isinstance(prior, UniformPrior) and type(prior).__call__ is UniformPrior.__call__):
+                return None
+            lo, hi = np.asarray(prior.minimum, np.float32), np.asarray(prior.maximum, np.float32)
+        from . import flow
+        params = tuple(getattr(like, 'hip_like_params', ()) or ())
+        std, mean = (np.asarray(v, np.float32) for v in affine)
+        x = np.random.RandomState(4321).uniform(-1, 1, size=(32, self.x_dim)).astype(np.float32)
+        tx = x * std + mean
+        dev = flow.loglike(like_id, tx, 1.0, device=self.trainer.netG.device, like_params=params).cpu().numpy()
+        host = np.asarray(like(tx.astype(np.float64)), dtype=np.float64)
+        if not np.allclose(dev, host, rtol=1e-5, atol=1e-4):
+            self.logger.warning('ensemble: likelihood id %d disagrees with the host callable; using the host protocol' % like_id)
+            return None
+        return like_id, params, lo, hi
+
+    def _ensemble_sample(self, mcmc_steps, num_walkers, init_samples=None, init_loglikes=None, init_derived=None, loglstar=None,
+                         show_progress=False, max_start_tries=100, output_interval=None, stats_interval=None, plot_trace=True,
+                         moves=None, seed=None, chunk_steps=None, route=None):
+        """emcee's EnsembleSampler with its default stretch move in latent space (sampler.py:632-724).  BUILD-DEFINED STREAM, EMCEE'S
+        MOVE: include/nnest_hip.h nnest_ensemble_steps has the definition; parity with emcee is statistical.  The fused kernel runs
+        where it takes the flow, the likelihood and the population (route 'fused'), the round driver otherwise (route 'rounds';
+        `route` pins one, for tests).  The run is cut into launches of `chunk_steps` steps (default: by device memory); the cut does
+        not change it.  Returns (samples [N, S, D] (x, before the transform), latent_samples [N, S, D], derived_samples [N, S, nd],
+        loglikes [N, S] (the latent log target, emcee's log_prob), ncall)."""
+        if moves is not None:
+            raise NotImplementedError('ensemble: only the default stretch move is built (moves=None)')
+        S = int(mcmc_steps)
+        if init_samples is not None:
+            num_walkers = init_samples.shape[0]
+        N, D, nd = int(num_walkers), self.x_dim, self.num_derived
+        if N < 2 * D:   # emcee/moves/red_blue.py
+            raise RuntimeError('It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions.')
+        netG = self.trainer.netG
+        if init_samples is not None:
+            z, _ = netG.forward(init_samples)
+        else:   # sampler.py:662-672 (its retry loop tests np.all(...) > -1e30, which always holds: one draw)
+            z = netG.prior_sample(N)
+        z = z.contiguous()
+        lp0 = None if init_loglikes is None else torch.as_tensor(np.asarray(init_loglikes, np.float64)).to(z.device)
+        seed = self._next_seed() if seed is None else int(seed)
+        affine = self._ensemble_affine()
+        dlike = self._ensemble_device_like(affine)
+        fused_ok = (dlike is not None and getattr(netG, 'ensemble_steps', None) is not None
+                    and N <= netG.ensemble_max_walkers(dlike[0]))
+        if route is None:
+            route = 'fused' if fused_ok else 'rounds'
+        elif route == 'fused' and not fused_ok:
+            raise ValueError('ensemble: the fused route does not take this flow, likelihood or population')
+        if chunk_steps is None:
+            chunk_steps = max(1, self.ENSEMBLE_HISTORY_BYTES // (N * (8 * D + 8)))
+        chunk_steps = max(1, min(int(chunk_steps), S if S > 0 else 1))
+        if output_interval:
+            chunk_steps = min(chunk_steps, int(output_interval))
+        samples = np.empty((N, S, D), np.float32)
+        latent = np.empty((N, S, D), np.float32)
+        loglikes = np.empty((N, S))
+        derived = np.zeros((N, S, nd))
+        ncall = 0 if init_loglikes is not None else N
+        from .ensemble_rounds import ensemble_rounds
+        state, n_acc, done = None, 0, 0
+        while done < S:
+            k = min(chunk_steps, S - done)
+            if route == 'fused':
+                like_id, params, lo, hi = dlike
+                res = netG.ensemble_steps(like_id, z, k, t_std=affine[0], t_mean=affine[1], lo=lo, hi=hi, lp=lp0, loglstar=loglstar,
+                                          seed=seed, step0=done, like_params=params)
+                z, lp0 = res['z'], res['lp']
+                hz, hx, hl = res['hist_z'], res['hist_x'], res['hist_lp']
+                n_acc += int(res['n_accept'].sum().item())
+            else:
+                kw = dict(loglstar=loglstar, seed=seed, step0=done)
+                if dlike is not None:
+                    kw.update(like_id=dlike[0], like_params=dlike[1], t_std=affine[0], t_mean=affine[1], lo=dlike[2], hi=dlike[3])
+                else:
+                    kw.update(loglike=self.loglike, prior=self.prior if self._user_prior is not None else None, num_derived=nd,
+                              init_derived=init_derived)
+                acc0 = 0 if state is None else int(state.n_accept.sum().item())
+                state, h = ensemble_rounds(netG, z, k, state=state, lp=lp0, **kw)
+                hz, hx, hl = h['hist_z'], h['hist_x'], h['hist_lp']
+                n_acc += int(state.n_accept.sum().item()) - acc0
+                derived[:, done:done + k] = h['hist_derived']
+            samples[:, done:done + k] = hx.cpu().numpy()
+            latent[:, done:done + k] = hz.cpu().numpy()
+            loglikes[:, done:done + k] = hl.cpu().numpy()
+            done += k
+            if output_interval is not None and done % int(output_interval) == 0:
+                self._save_samples(self.transform(samples[:, :done].reshape(-1, D)), loglikes[:, :done].reshape(-1),
+                                   derived_samples=derived[:, :done].reshape(-1, nd))
+        ncall += N * S
+        if route == 'fused' or dlike is not None:   # (the host protocol counts its own calls in self.loglike)
+            self.total_calls += ncall
+        self.total_accepted += n_acc
+        self.total_rejected += N * S - n_acc
+        self.ensemble_route = route
+        return samples, latent, derived, loglikes, ncall
 
     # ---- chain files (sampler.py:494-527): getdist text format "weight -logL params..." ------------------------
     def _save_samples(self, samples, loglikes, weights=None, derived_samples=None, min_weight=1e-30, outfile='chain'):
