@@ -270,6 +270,11 @@ class Spline(object):
             loss = lib().spl32_spline_log_probs(*self._args(False), _p(xi, _fp), N, _p(lp, _fp), int(data_init))
         return lp, loss
 
+    def loss_grad(self, X):
+        """(loss = -mean(log_probs(X)), dloss/dw in packed order) in float64 by autograd (oracle/spline_grad.py)"""
+        from oracle import spline_grad
+        return spline_grad.loss_grad(self.w, self.P, X, self.D, self.H, self.B, self.K, self.tail, self.base_beta)
+
     def fd_grad(self, X, idx, h=5e-5):
         """central finite differences (float64 arithmetic, float32 weights) of loss = -mean(log_probs(X)) for the
         packed parameters `idx`: the yardstick for hand-written backward passes"""
