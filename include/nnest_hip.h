@@ -479,6 +479,54 @@ int nnest_spline_train(nnest_spline_t *spl, const float *xtrain_dev, int n_train
                        void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Chain statistics of a batch of MCMC histories x[C, T, D] (float32; element (i, j, d) at x_dev[i * chain_stride + j * step_stride
+ * + d], so a prefix [:, :t] of a longer history and the [C, steps + 1, D] history of nnest_mh_constrained_steps are read in place)
+ * -- nnest/utils/evaluation.py and Sampler._chain_stats, nnest/sampler.py:474-492, with the reference's definitions (float64
+ * sums; f32 products in the lag sums):
+ *   v = x, or x * a + b per dimension when affine_dev [2, D] float64 = (a, b) is given (the reference's T(x) = x * std + mean)
+ *   acceptance   #{(i, j): j = 1..T-1, v[i,j] != v[i,j-1] in at least one coordinate} / (C (T - 1))   (an exact count)
+ *   jump         sum_i sum_j ||v[i,j] - v[i,j-1]||_2 / (C (T - 1))
+ *   mu, sd       mean_dev / std_dev when given, else the mean and population std (ddof 0) over all C T rows
+ *   p_s[d]       (1 / C) sum_i mean_{j<T-s} (v[i,j,d] - mu_d)(v[i,j+s,d] - mu_d) / sd_d       -- divided by the STANDARD DEVIATION,
+ *                as the reference (sampler.py:480 passes std into evaluation.py:17's `var`)
+ *   ESS          e_d = 1; for s = 1 .. T-1: stop if no d has p_s[d] > 0.05, else e_d += 2 p_s[d] (1 - s / T) for every d with
+ *                p_s[d] > 0.05 (the stop is global over d); ESS_d = T / e_d
+ *   R-hat        (C > 1; NaN for C = 1) theta_i / sigma2_i = mean / variance of chain i over the steps, theta_bar = mean_i theta_i
+ *                (mu with NNEST_CHAIN_STATS_RHAT_AT_MEAN), B = T / (C - 1) sum_i sum_d (theta_i - theta_bar)^2 (ONE number: the
+ *                reference's np.sum has no axis, evaluation.py:88),
+ *                W = 1 / (C sum_i sigma2_i + 1e-5), V = (T - 1) / T W + (C + 1) / (C T) B, R-hat = sqrt(V / W)   (evaluation.py:77-93)
+ * Any C >= 1, T >= 2, D >= 1.  Every call is asynchronous on `stream` and bitwise repeatable (fixed-order sums, no float atomics).
+ * work_dev: float64 scratch of nnest_chain_stats_work_words(C, T, D) words (-1: bad shape), reused across the calls of one batch.
+ *
+ * nnest_chain_stats: all of it.  out_dev [4 + 4 D] float64 = acceptance, jump, stop lag (the s at which the ESS sum stopped; T if it
+ *   never did), C, then ESS[D], R-hat[D], mu[D], sd[D].  p_dev (optional) [T - 1, D]: p_s in row s - 1 for every lag computed.
+ *   Lags are computed in blocks of 256, 256, 512, 1024, 2048, 2048, ...; a block after the stop lag costs its launches only.
+ *   flags: NNEST_CHAIN_STATS_ALL_LAGS computes (and writes to p_dev) every lag; NO_ESS skips the lags (ESS and stop lag NaN).
+ * The stages, for a batch sharded over devices: the chain sums [3 + 3 D] (accepted pairs, jump sum, C, sum_i (theta_i - c)[D],
+ *   sum_i (theta_i - c)^2[D], sum_i sigma2_i[D]) and the lag sums [nlags, D] (sum_i sum_{j<T-s} y y) are ADDITIVE over shards:
+ *   all-reduce them between the stages.  c = center_dev [D] of nnest_chain_stats_chains -- the same on every shard (the mean passed
+ *   to prepare will do) -- or, when NULL, the first chain's theta of the call (one shard only); the centring keeps the moments
+ *   exact when the chain means are large compared with their spread.  chains -> (all-reduce) -> prepare (with the global C) -> for each lag block: lags -> (all-reduce) ->
+ *   advance -> finish.  nlags: a multiple of 256 up to 2048. */
+enum { NNEST_CHAIN_STATS_ALL_LAGS = 1, NNEST_CHAIN_STATS_NO_ESS = 2, NNEST_CHAIN_STATS_RHAT_AT_MEAN = 4 };
+int nnest_chain_stats_work_words(int C, int T, int D);
+int nnest_chain_stats(const float *x_dev, int C, int T, int D, long long chain_stride, long long step_stride, const double *affine_dev,
+                      const double *mean_dev, const double *std_dev, int flags, double *work_dev, double *p_dev, double *out_dev,
+                      void *stream);
+int nnest_chain_stats_chains(const float *x_dev, int C, int T, int D, long long chain_stride, long long step_stride,
+                             const double *affine_dev, const double *center_dev, double *work_dev, double *chain_sums_dev,
+                             void *stream);
+int nnest_chain_stats_prepare(const double *chain_sums_dev, int C, int T, int D, const double *mean_dev, const double *std_dev,
+                              double *work_dev, void *stream);
+int nnest_chain_stats_lags(const float *x_dev, int C, int T, int D, long long chain_stride, long long step_stride,
+                           const double *affine_dev, int lag0, int nlags, int flags, double *work_dev, double *lag_sums_dev,
+                           void *stream);
+int nnest_chain_stats_advance(const double *chain_sums_dev, const double *lag_sums_dev, int C, int T, int D, int lag0, int nlags,
+                              int flags, double *work_dev, double *p_dev, void *stream);
+int nnest_chain_stats_finish(const double *chain_sums_dev, int C, int T, int D, int flags, double *work_dev, double *out_dev,
+                             void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * 'choleksy' flow: SingleSpeedCholeksy(num_inputs=D) (networks.py:162-239): y = L x + b, L lower triangular with
  * diag = softplus(unconstrained_diag) + 1e-3.  Packed weights = state_dict order: bias[D], lower_entries[D(D-1)/2]
  * (np.tril_indices(D, -1) order), unconstrained_diag[D].  Conventions as the nnest_nvp_* functions.

@@ -163,7 +163,15 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _vp, _i, _d, _vp],
     'nnest_host_prior_consume': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  ctypes.c_longlong, _d, ctypes.c_longlong, ctypes.c_longlong, _d, _d, _i],
+    'nnest_chain_stats_work_words': [_i, _i, _i],
+    'nnest_chain_stats': [_vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
+    'nnest_chain_stats_chains': [_vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp],
+    'nnest_chain_stats_prepare': [_vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    'nnest_chain_stats_lags': [_vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, _vp, _i, _i, _i, _vp, _vp, _vp],
+    'nnest_chain_stats_advance': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    'nnest_chain_stats_finish': [_vp, _i, _i, _i, _i, _vp, _vp, _vp],
 }
+CHAIN_STATS_ALL_LAGS, CHAIN_STATS_NO_ESS, CHAIN_STATS_RHAT_AT_MEAN = 1, 2, 4   # include/nnest_hip.h NNEST_CHAIN_STATS_*
 HOST_FINISHED, HOST_RETRAIN, HOST_NEED_SAMPLES, HOST_LOG, HOST_CHECKPOINT, HOST_DEAD_FULL = range(6)   # include/nnest_hip.h NNEST_HOST_*
 HOST_EXPIRED = 6
 HOST_TOP, HOST_AFTER_TRAIN, HOST_AFTER_SAMPLES, HOST_AFTER_LOG = range(4)

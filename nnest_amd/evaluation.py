@@ -1,0 +1,149 @@
+"""Chain statistics on the GPU: the reference's nnest/utils/evaluation.py (acceptance rate, mean jump distance, lag autocorrelation,
+effective sample size, Gelman-Rubin R-hat) over a batch of chains x [C, T, D], computed by the HIP kernels behind
+include/nnest_hip.h nnest_chain_stats*.  The inputs are numpy arrays (copied to the device as float32) or CUDA tensors (read in place
+through their chain and step strides when float32 with a unit dimension stride).  The definitions, the reference's quirks included
+(the autocorrelation divided by the standard deviation; the ESS sum stopped globally over the dimensions), are in the header.
+There is no CPU path: without a GPU these raise NnestHipError."""
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import NnestHipError
+
+LAG_BLOCK = 256
+
+
+def _device_chains(x):
+    """x [C, T, D] -> (float32 CUDA tensor with unit dimension stride, chain stride, step stride); views of a CUDA tensor in place"""
+    if not torch.cuda.is_available():
+        raise NnestHipError('chain statistics run on the GPU (HIP); no device is available and there is no CPU fallback')
+    if isinstance(x, torch.Tensor):
+        t = x.detach()
+        if not t.is_cuda:
+            t = t.cuda()
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32)).cuda()
+    if t.dim() != 3:
+        raise ValueError('chains must be shaped [C, T, D], got %s' % (tuple(t.shape),))
+    if t.dtype != torch.float32 or t.stride(2) != 1:
+        t = t.float().contiguous()
+    return t, t.stride(0), t.stride(1)
+
+
+def _vec(v, D, device):
+    if v is None:
+        return None
+    a = torch.as_tensor(np.broadcast_to(np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64), (D,)).copy())
+    return a.to(device)
+
+
+def _affine(affine, D, device):
+    """affine = (a, b): T(x) = x * a + b per dimension -> [2, D] float64 on the device"""
+    if affine is None:
+        return None
+    a, b = affine
+    return torch.cat([_vec(a, D, device), _vec(b, D, device)]).contiguous()
+
+
+def chain_stats(x, mean=None, std=None, affine=None, all_lags=False, return_p=False, ess=True, rhat_at_mean=False):
+    """All the statistics of chains x [C, T, D] from one pass: a dict with acceptance, jump_distance (floats), ess, rhat (None for
+    one chain), mean, std ([D] float64 numpy), stop_lag (the lag at which the ESS sum stopped, T if it never did) and, with
+    return_p, p [T - 1, D] (the lag autocorrelations; NaN in the rows of lags not computed).  mean / std: those of
+    Sampler._chain_stats (default: over all C T rows); affine: (a, b), the statistics of x * a + b, computed without a copy;
+    all_lags: compute every lag, not only those up to the stop; ess=False: skip the lags; rhat_at_mean: R-hat about `mean`
+    (gelman_rubin_diagnostic(x, mu))."""
+    t, cs, ss = _device_chains(x)
+    C, T, D = t.shape
+    dev = t.device
+    lib = _lib.load()
+    words = lib.nnest_chain_stats_work_words(C, T, D)
+    if words < 0:
+        raise ValueError('chain_stats: unsupported shape C=%d T=%d D=%d (C >= 1, T >= 2, D >= 1)' % (C, T, D))
+    flags = ((_lib.CHAIN_STATS_ALL_LAGS if all_lags else 0) | (0 if ess else _lib.CHAIN_STATS_NO_ESS)
+             | (_lib.CHAIN_STATS_RHAT_AT_MEAN if rhat_at_mean else 0))
+    with torch.cuda.device(dev):
+        mu, sd, aff = _vec(mean, D, dev), _vec(std, D, dev), _affine(affine, D, dev)
+        work = torch.empty(words, dtype=torch.float64, device=dev)
+        out = torch.empty(4 + 4 * D, dtype=torch.float64, device=dev)
+        p = torch.full((T - 1, D), float('nan'), dtype=torch.float64, device=dev) if return_p else None
+        _lib.check(lib.nnest_chain_stats(_lib.ptr(t), C, T, D, cs, ss, _lib.ptr(aff), _lib.ptr(mu), _lib.ptr(sd), flags,
+                                         _lib.ptr(work), _lib.ptr(p), _lib.ptr(out), _lib.current_stream(dev)))
+        o = out.cpu().numpy()
+    res = dict(acceptance=float(o[0]), jump_distance=float(o[1]), stop_lag=None if np.isnan(o[2]) else int(o[2]),
+               ess=o[4:4 + D].copy() if ess else None, rhat=o[4 + D:4 + 2 * D].copy() if C > 1 else None,
+               mean=o[4 + 2 * D:4 + 3 * D].copy(), std=o[4 + 3 * D:4 + 4 * D].copy())
+    if return_p:
+        res['p'] = p.cpu().numpy()
+    return res
+
+
+class ShardedChainStats(object):
+    """The stages of include/nnest_hip.h for one shard of a batch whose chains are split over ranks: the chain sums and the lag
+    sums are additive, so `allreduce` (a callable summing a float64 CUDA tensor over the ranks in place) between the stages gives
+    every rank the statistics of the whole batch.  mean and std are required (the moments of the whole batch would need one
+    more round)."""
+
+    def __init__(self, allreduce):
+        self.allreduce = allreduce
+
+    def __call__(self, x, mean, std, affine=None):
+        """(acceptance, ESS [D], jump distance) of the whole batch; x [C_local, T, D] may hold no chains (C_local = 0)"""
+        t, cs, ss = _device_chains(x)
+        C, T, D = t.shape
+        dev = t.device
+        lib = _lib.load()
+        st = _lib.current_stream(dev)
+        with torch.cuda.device(dev):
+            work = torch.empty(lib.nnest_chain_stats_work_words(max(C, 1), T, D), dtype=torch.float64, device=dev)
+            sums = torch.zeros(3 + 3 * D, dtype=torch.float64, device=dev)
+            mu, sd, aff = _vec(mean, D, dev), _vec(std, D, dev), _affine(affine, D, dev)
+            if C > 0:
+                _lib.check(lib.nnest_chain_stats_chains(_lib.ptr(t), C, T, D, cs, ss, _lib.ptr(aff), _lib.ptr(mu), _lib.ptr(work),
+                                                        _lib.ptr(sums), st))
+            self.allreduce(sums)
+            Cw = max(C, 1)   # (the work layout of an empty shard)
+            _lib.check(lib.nnest_chain_stats_prepare(_lib.ptr(sums), Cw, T, D, _lib.ptr(mu), _lib.ptr(sd), _lib.ptr(work), st))
+            lag_sums = torch.zeros((LAG_BLOCK, D), dtype=torch.float64, device=dev)
+            for lag0 in range(1, T, LAG_BLOCK):
+                if C > 0:
+                    _lib.check(lib.nnest_chain_stats_lags(_lib.ptr(t), C, T, D, cs, ss, _lib.ptr(aff), lag0, LAG_BLOCK, 0, _lib.ptr(work),
+                                                          _lib.ptr(lag_sums), st))
+                self.allreduce(lag_sums)
+                _lib.check(lib.nnest_chain_stats_advance(_lib.ptr(sums), _lib.ptr(lag_sums), Cw, T, D, lag0, LAG_BLOCK, 0, _lib.ptr(work),
+                                                         None, st))
+            out = torch.empty(4 + 4 * D, dtype=torch.float64, device=dev)
+            _lib.check(lib.nnest_chain_stats_finish(_lib.ptr(sums), Cw, T, D, 0, _lib.ptr(work), _lib.ptr(out), st))
+            o = out.cpu().numpy()
+        return float(o[0]), o[4:4 + D].copy(), float(o[1])
+
+
+# ---- the reference's functions (nnest/utils/evaluation.py), same names and signatures ----------------------------------------
+def auto_correlation_time(x, s, mu, var):
+    """p_s [D]: (1 / C) sum_i mean_j (x_ij - mu)(x_i,j+s - mu) / var  (evaluation.py:6-14; `var` as the reference divides by it)"""
+    T = x.shape[1]
+    if not 1 <= s < T:
+        raise ValueError('lag s=%d outside 1..T-1 = %d' % (s, T - 1))
+    return chain_stats(x, mean=mu, std=var, all_lags=True, return_p=True)['p'][s - 1]
+
+
+def effective_sample_size(x, mu, var):
+    """evaluation.py:17-41"""
+    return chain_stats(x, mean=mu, std=var)['ess']
+
+
+def acceptance_rate(x):
+    """evaluation.py:44-58"""
+    return chain_stats(x, ess=False)['acceptance']
+
+
+def mean_jump_distance(x):
+    """evaluation.py:61-74"""
+    return chain_stats(x, ess=False)['jump_distance']
+
+
+def gelman_rubin_diagnostic(x, mu=None):
+    """evaluation.py:77-93 (one chain divides by C - 1 = 0, as in the reference)"""
+    if x.shape[0] < 2:
+        raise ZeroDivisionError('gelman_rubin_diagnostic: one chain (B divides by C - 1)')
+    return chain_stats(x, mean=mu, ess=False, rhat_at_mean=mu is not None)['rhat']

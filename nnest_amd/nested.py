@@ -86,7 +86,8 @@ class NestedSampler(Sampler):
                  checkpoint_min_seconds=2.0,
                  chain_min_seconds=30.0,
                  native_loop=True,
-                 mcmc_proposal='mh'):
+                 mcmc_proposal='mh',
+                 chain_stats=False):
         prior = UniformPrior(x_dim, -1, 1)  # nested.py:76
         super(NestedSampler, self).__init__(x_dim, loglike, transform=transform, append_run_num=append_run_num,
                                             hidden_dim=hidden_dim, num_slow=num_slow, num_derived=num_derived,
@@ -95,7 +96,7 @@ class NestedSampler(Sampler):
                                             resume=resume, use_gpu=use_gpu, base_dist=base_dist, scale=scale,
                                             trainer=trainer, prior=prior, transform_prior=False, log_level=log_level,
                                             param_names=param_names, oversample_rate=oversample_rate, fused=fused,
-                                            mcmc_history=mcmc_history, mcmc_proposal=mcmc_proposal)
+                                            mcmc_history=mcmc_history, mcmc_proposal=mcmc_proposal, chain_stats=chain_stats)
         self.num_live_points = num_live_points
         self.checkpoint_min_seconds = checkpoint_min_seconds
         self.chain_min_seconds = chain_min_seconds
@@ -112,6 +113,28 @@ class NestedSampler(Sampler):
                                         'logz', 'fraction_remain', 'ncall'])
 
     # ---- helpers ---------------------------------------------------------------------------------------------
+    def _batch_chain_stats(self, active_u, C, primary):
+        """chain_stats=True: the reference's acceptance, min ESS, max ESS and jump distance of the batch that supplied the accepted
+        point, with the mean and std of the live points (nested.py:446-456), and its 'Acceptance [..]' line (sampler.py:486-488).
+        The batch's history is read where it lies (the device history of the fused kernels, read in place); a sharded batch
+        all-reduces its additive sums, so the values cover every chain of the batch, as the reference's gathered samples do
+        (nested.py:418-427).  Every rank calls this at the same log point."""
+        from .evaluation import ShardedChainStats, chain_stats
+        h = self._chain_hist
+        if not torch.is_tensor(h):
+            h = torch.from_numpy(np.ascontiguousarray(h, dtype=np.float32)).to(self.trainer.netG.device)
+        mean, std = np.mean(active_u, axis=0), np.std(active_u, axis=0)
+        if self.use_mpi:
+            per = -(-C // self.mpi_size)
+            n = max(0, min(per, C - self.mpi_rank * per))     # (the padding chains of the last rank are not part of the batch)
+            acc, ess, jump = ShardedChainStats(self._all_reduce_)(h[:n], mean, std)
+        else:
+            r = chain_stats(h, mean=mean, std=std)
+            acc, ess, jump = r['acceptance'], r['ess'], r['jump_distance']
+        if primary:
+            self._log_chain_stats_line(acc, ess, jump)
+        return [acc, np.min(ess), np.max(ess), jump]
+
     def _initial_loglikes(self, active_u):
         """nested.py:210-228: likelihood of the initial live points through the host protocol (float64),
         sharded over ranks and all-gathered when distributed."""
@@ -443,6 +466,7 @@ class NestedSampler(Sampler):
                         s_x, _lat, s_d, s_l, scale, nc = self._mcmc_sample(
                             mcmc_steps, step_size=step_size, dynamic_step_size=dynamic,
                             init_derived=active_derived[my, :] if nd > 0 else np.empty((per, 0)), **kw)
+                        self._chain_hist = s_x if self.chain_stats else None
                         mv = np.all(s_x[:, 0, :] != s_x[:, -1, :], axis=1)   # a chain is usable if every coordinate moved (nested.py:432)
                         ends = np.concatenate([s_x[:, -1, :], s_l[:, -1:], mv[:, None], s_d[:, -1, :]], axis=1).astype(np.float64)
                     ends = self._all_gather_rows(ends)[:C]
@@ -458,6 +482,7 @@ class NestedSampler(Sampler):
                     st.nb = 0
                     st.resume = _lib.HOST_AFTER_SAMPLES
                 elif reason == _lib.HOST_LOG:                    # nested.py:439-456 (before `it` advances)
+                    stats = self._batch_chain_stats(active_u, C, primary) if self.chain_stats else None
                     if primary:
                         acc = self.total_accepted / max(1, self.total_accepted + self.total_rejected)
                         self.logger.info('Step [%d] loglstar [%5.4e] maxlogl [%5.4e] logz [%5.4e] vol [%6.5e] ncalls [%d] '
@@ -465,8 +490,9 @@ class NestedSampler(Sampler):
                         # (one handle for the loop, flushed row by row: a config-2 run appends 1000 rows, and open/close per row was 25 ms)
                         if results_f is None:
                             results_f = open(os.path.join(self.logs['results'], 'results.csv'), 'a')
-                        csv.writer(results_f).writerow([st.it, acc, float('nan'), float('nan'), float('nan'), scale, np.float64(st.loglstar),
-                                                        np.float64(st.logz), np.float64(st.fraction_remain), total_calls])
+                        cols = stats if stats is not None else [acc, float('nan'), float('nan'), float('nan')]
+                        csv.writer(results_f).writerow([st.it] + cols + [scale, np.float64(st.loglstar), np.float64(st.logz),
+                                                                         np.float64(st.fraction_remain), total_calls])
                         results_f.flush()
                     st.resume = _lib.HOST_AFTER_LOG
                 elif reason == _lib.HOST_CHECKPOINT:             # nested.py:473-485
@@ -752,6 +778,7 @@ class NestedSampler(Sampler):
                         s_x, _lat, s_d, s_l, scale, nc = self._mcmc_sample(
                             mcmc_steps, step_size=step_size, dynamic_step_size=mcmc_dynamic_step_size,
                             init_derived=active_derived[my, :] if nd > 0 else np.empty((per, 0)), **kw)
+                        self._chain_hist = s_x if self.chain_stats else None
                         mv = np.all(s_x[:, 0, :] != s_x[:, -1, :], axis=1)   # a chain is usable if every coordinate moved (nested.py:432)
                         ends = np.concatenate([s_x[:, -1, :], s_l[:, -1:], mv[:, None], s_d[:, -1, :]], axis=1).astype(np.float64)
                     ends = self._all_gather_rows(ends)[:C]
@@ -774,13 +801,16 @@ class NestedSampler(Sampler):
                         accept_point = True
                         break
                 total_calls = int(self._all_sum(self.total_calls))
+                stats = None
+                if accept_point and it > 0 and it % log_interval == 0 and self.chain_stats:
+                    stats = self._batch_chain_stats(np.asarray(active_u, dtype=np.float64), mcmc_num_chains, primary)
                 if accept_point and it > 0 and it % log_interval == 0 and primary:
                     acc = self.total_accepted / max(1, self.total_accepted + self.total_rejected)
                     self.logger.info('Step [%d] loglstar [%5.4e] maxlogl [%5.4e] logz [%5.4e] vol [%6.5e] ncalls [%d] '
                                      'scale [%5.4f]' % (it, loglstar, max_logl, ev.logz, np.exp(-it / N), total_calls, scale))
                     with open(os.path.join(self.logs['results'], 'results.csv'), 'a') as f:
-                        csv.writer(f).writerow([it, acc, float('nan'), float('nan'), float('nan'), scale, loglstar, ev.logz,
-                                                fraction_remain, total_calls])
+                        cols = stats if stats is not None else [acc, float('nan'), float('nan'), float('nan')]
+                        csv.writer(f).writerow([it] + cols + [scale, loglstar, ev.logz, fraction_remain, total_calls])
 
             if accept_point:                                 # nested.py:458-485
                 logvol -= 1.0 / N

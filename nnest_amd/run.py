@@ -43,7 +43,7 @@ def main(args):
     sampler = NestedSampler(like.x_dim, like, transform=lambda x: scale * x, log_dir=log_dir,
                             num_live_points=args.num_live_points, hidden_dim=args.hidden_dim,
                             num_layers=args.num_layers, num_blocks=args.num_blocks, flow=args.flow, base_dist=base_dist,
-                            scale=args.scale, mcmc_proposal=args.mcmc_proposal)
+                            scale=args.scale, mcmc_proposal=args.mcmc_proposal, chain_stats=args.chain_stats)
     start = time.time()
     sampler.run(train_iters=args.train_iters, mcmc_steps=args.mcmc_steps, volume_switch=args.switch, jitter=args.jitter,
                 mcmc_num_chains=args.mcmc_num_chains, mcmc_dynamic_step_size=not args.mcmc_fixed_step_size,
@@ -84,4 +84,5 @@ if __name__ == '__main__':
     p.add_argument('--beta', type=float, default=8.0)
     p.add_argument('--scale', type=str, default='')
     p.add_argument('--mcmc_proposal', type=str, default='mh', choices=('mh', 'slice'))   # 'slice': build-defined, not in the reference
+    p.add_argument('--chain_stats', action='store_true')   # acceptance / ESS / jump distance of each logged batch in results.csv (GPU)
     main(p.parse_args())

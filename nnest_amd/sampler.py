@@ -67,7 +67,8 @@ class Sampler(object):
                  param_names=None,
                  fused=True,
                  mcmc_history=False,
-                 mcmc_proposal='mh'):
+                 mcmc_proposal='mh',
+                 chain_stats=False):
         # mcmc_proposal (not in the reference, whose _mcmc_sample proposes random-walk Metropolis moves only, sampler.py:310-316):
         # 'mh' = that step; 'slice' = the build-defined slice proposal in latent space (BASELINE north_star; include/nnest_hip.h,
         # parity unpinned) under the hard constraint logL > L*, with every flow and every likelihood: the fused kernels
@@ -87,6 +88,10 @@ class Sampler(object):
             assert len(param_names) == self.num_params
         self.oversample_rate = oversample_rate if oversample_rate > 0 else self.num_fast / self.x_dim   # sampler.py:95
         self.mcmc_history = mcmc_history
+        # chain_stats: log the reference's chain statistics (acceptance, ESS, jump distance: sampler.py:474-492), computed on the
+        # GPU (nnest_amd.evaluation); off by default, which leaves every run as it was
+        self.chain_stats = bool(chain_stats)
+        self._chain_hist = None   # chain_stats: the history [C, steps + 1, D] of the last batch of chains (this rank's)
         self._user_loglike = loglike
         self._user_prior = prior
         self._transform_prior = transform_prior
@@ -319,8 +324,8 @@ class Sampler(object):
         z, _ = netG.forward(init_samples)                               # sampler.py:264
         logl = torch.as_tensor(np.ascontiguousarray(init_loglikes, dtype=np.float64)).to(netG.device)
         z0 = z.clone()
-        kw = dict(seed=self._next_seed() if seed is None else seed, walker_offset=walker_offset, history=self.mcmc_history,
-                  like_params=self._fused_like_params, form=form)
+        kw = dict(seed=self._next_seed() if seed is None else seed, walker_offset=walker_offset,
+                  history=self.mcmc_history or self.chain_stats, like_params=self._fused_like_params, form=form)
         star = None if loglstar is None else float(loglstar)
         args = (self._fused_like_id, self._linear_scale, z, logl, star, float(step_size), int(mcmc_steps))
         # dynamic: the reference's rule over the whole batch (sampler.py:422-431), `mcmc_step_lag` steps behind (0 = exactly
@@ -407,12 +412,14 @@ class Sampler(object):
             logl = torch.as_tensor(np.asarray(init_loglikes, dtype=np.float64), device=z.device).contiguous()
             fused_slice = getattr(netG, 'supports_fused_slice', None)
             if fused_slice is not None and not fused_slice(C):   # no fused slice kernel for this flow: the round driver
-                res, ncall = self._slice_rounds(z, logl, loglstar, step_size, mcmc_steps, walker_offset, seed)
+                res, ncall = self._slice_rounds(z, logl, loglstar, step_size, mcmc_steps, walker_offset, seed, history=self.chain_stats)
+                self._chain_hist = res['hist_x'] if self.chain_stats else None
                 ends = torch.cat([res['x'].double(), logl[:, None], res['moved'][:, None].double()], dim=1)
                 return ends, float(step_size), ncall
             res = netG.slice_steps(self._fused_like_id, self._linear_scale, z, logl, float(loglstar), 2.0 * float(step_size),
                                    int(mcmc_steps), seed=self._next_seed() if seed is None else seed, walker_offset=walker_offset,
-                                   like_params=self._fused_like_params)
+                                   like_params=self._fused_like_params, history=self.chain_stats)
+            self._chain_hist = res['hist_x'] if self.chain_stats else None
             ends = torch.cat([res['x'].double(), logl[:, None], res['moved'][:, None].double()], dim=1)
             counts = torch.stack([res['n_call'].sum(), res['n_move'].sum()]).cpu()
             ncall, nmove = int(counts[0]), int(counts[1])
@@ -426,6 +433,7 @@ class Sampler(object):
         # chain's last x against its first x = f^-1(z_0), coordinate by coordinate (NNEST_MH_ALL_MOVED; round 4 took "accepted at
         # least once" for it, which differs once a proposal is so small that a coordinate of x does not change in float32)
         moved = res['moved']
+        self._chain_hist = res['hist_x'] if self.chain_stats else None   # [C, steps + 1, D] on the device, read in place
         ends = torch.cat([res['x'].double(), logl[:, None], moved[:, None].double()], dim=1)
         counts = torch.stack([res['n_call'].sum(), res['n_accept'].sum()]).cpu()   # one small copy; orders the stream too
         netG.check_sync(res)
@@ -837,6 +845,38 @@ class Sampler(object):
         self.ensemble_route = route
         return samples, latent, derived, loglikes, ncall
 
+    # ---- chain statistics (sampler.py:474-492) ---------------------------------------------------------------------
+    def _chain_stats(self, samples, mean=None, std=None, step=None, affine=None):
+        """acceptance rate, ESS [D] and mean jump distance of chains samples [C, T, D] (numpy, or a CUDA tensor read in place), and
+        the reference's log line, as Sampler._chain_stats (the Gelman-Rubin R-hat, which the reference computes and discards, is in
+        nnest_amd.evaluation.chain_stats).  affine = (a, b): the statistics of samples * a + b, without a transformed copy."""
+        from .evaluation import chain_stats
+        r = chain_stats(samples, mean=mean, std=std, affine=affine)
+        acceptance, ess, jump_distance = r['acceptance'], r['ess'], r['jump_distance']
+        self._log_chain_stats_line(acceptance, ess, jump_distance, step)
+        return acceptance, ess, jump_distance
+
+    def _log_chain_stats_line(self, acceptance, ess, jump_distance, step=None):
+        if step is None:
+            self.logger.info('Acceptance [%5.4f] min ESS [%5.4f] max ESS [%5.4f] average jump [%5.4f]' %
+                             (acceptance, np.min(ess), np.max(ess), jump_distance))
+        else:
+            self.logger.info('Step [%d] acceptance [%5.4f] min ESS [%5.4f] max ESS [%5.4f] average jump [%5.4f]' %
+                             (step, acceptance, np.min(ess), np.max(ess), jump_distance))
+
+    def _log_chain_stats(self, samples, affine, mcmc_steps, stats_interval, prefix_offset, min_step):
+        """MCMCSampler / EnsembleSampler with chain_stats=True: the lines the reference logs while it samples (step `it` of
+        stats_interval, on the transformed chains up to that step: prefix_offset + it states, sampler.py:451-452 and :712-713,
+        steps > min_step), then once on the whole run (mcmc.py:119-120, ensemble.py:224-225).  One upload of the history; every
+        prefix is read in place through its strides, the transform applied on load."""
+        h = torch.from_numpy(np.ascontiguousarray(samples, dtype=np.float32)).to(self.trainer.netG.device)
+        if stats_interval is not None:
+            for it in range(int(stats_interval), int(mcmc_steps) + 1, int(stats_interval)):
+                if it > min_step and prefix_offset + it >= 2:
+                    self._chain_stats(h[:, :prefix_offset + it], step=it, affine=affine)
+        if mcmc_steps > 1:
+            self._chain_stats(h, affine=affine)
+
     # ---- chain files (sampler.py:494-527): getdist text format "weight -logL params..." ------------------------
     def _save_samples(self, samples, loglikes, weights=None, derived_samples=None, min_weight=1e-30, outfile='chain'):
         if self.logs is None:
@@ -876,6 +916,14 @@ class Sampler(object):
         t = (torch.as_tensor(np.ascontiguousarray(arr)) if as_numpy else arr).to(self._comm_device()).contiguous()
         torch.distributed.broadcast(t, src=src)
         return t.cpu().numpy() if as_numpy else t
+
+    def _all_reduce_(self, t):
+        """sum a tensor over the ranks in place (on the communication device, copied back)"""
+        if self.use_mpi:
+            c = t.to(self._comm_device())
+            torch.distributed.all_reduce(c)
+            t.copy_(c)
+        return t
 
     def _all_sum(self, value):
         if not self.use_mpi:
