@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .flow import HipNVP, _as_dev_f32
+from .flow import HipNVP, _as_dev_f32, train_epochs_host
 
 
 class HipFastSlowNVP(object):
@@ -238,12 +238,6 @@ class HipFastSlowNVP(object):
     # ---- training ---------------------------------------------------------------------------------------------------------
     epoch_chunk = 1 << 30
 
-    def _vjp(self, net, x, gz, gld):
-        return net.vjp(x, gz, gld)
-
-    def _adam(self, net, grad, lr, wd):
-        net.adam_step(grad, lr, wd)
-
     def loss_grad(self, x):
         """loss = -mean(log_probs(x)) and its gradient in the three stages' packed layouts (fast, slow, coupling)"""
         x = _as_dev_f32(x, self.device)
@@ -254,11 +248,11 @@ class HipFastSlowNVP(object):
         v = self._interleave(zs, zf)
         lp = self.coupling.log_probs(v) + (2 * self.m - self.D) * 0.9189385332046727 + lds + ldf
         z, _ = self.coupling.forward(v)
-        gC, gv = self._vjp(self.coupling, v, z / M, -1.0 / M)      # d(-mean log N(z))/dz = z / M
+        gC, gv = self.coupling.vjp(v, z / M, -1.0 / M)      # d(-mean log N(z))/dz = z / M
         gC = gC * self._cmask
         gys, gyf = self._split(gv)
-        gS, _ = self._vjp(self.slow, xs, gys, -1.0 / M)
-        gF, _ = self._vjp(self.fast, xf, gyf, -1.0 / M)
+        gS, _ = self.slow.vjp(xs, gys, -1.0 / M)
+        gF, _ = self.fast.vjp(xf, gyf, -1.0 / M)
         return -lp.mean(), (gF, gS, gC)
 
     def reference_gradient(self, grads):
@@ -278,51 +272,23 @@ class HipFastSlowNVP(object):
         finally:
             self._unused = saved
 
+    def _train_epoch(self, rows, epoch, n_train, batch, lr, weight_decay):
+        tot = 0.0
+        for b0 in range(0, n_train, batch):
+            loss, (gF, gS, gC) = self.loss_grad(rows(epoch, b0, b0 + batch))
+            self.fast.adam_step(gF, lr, weight_decay)
+            self.slow.adam_step(gS, lr, weight_decay)
+            self.coupling.adam_step(gC, lr, weight_decay)
+            tot += float(loss)
+        return tot
+
     def train_epochs(self, xtrain, xvalid, perm, noise=None, seed=0, jitter=0.0, batch=100, max_epochs=1, patience=50,
                      lr=1e-3, weight_decay=1e-6, epoch_offset=0, resume=False, finalize=True, result=None):
-        """Trainer.train's epoch loop (trainer.py:198-241), host-driven; arguments and return value as HipNVP.train_epochs"""
+        """Trainer.train's epoch loop (trainer.py:198-241), host-driven (flow.train_epochs_host); arguments and return value as
+        HipNVP.train_epochs"""
         assert not resume and epoch_offset == 0
-        dev = self.device
-        xtrain = _as_dev_f32(xtrain, dev)
-        xvalid = _as_dev_f32(xvalid, dev)
-        n_train, n_valid = xtrain.shape[0], xvalid.shape[0]
-        perm = perm.to(device=dev, dtype=torch.int64).view(max_epochs, n_train)
-        if noise is not None:
-            noise = noise.to(device=dev, dtype=torch.float32).view(max_epochs, n_train, self.D)
-        gen = torch.Generator(device=dev)
-        gen.manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF)
-        losses = np.zeros((max(max_epochs, 1), 2), np.float32)
-        best, best_epoch, counter, stopped, epochs_run = float('inf'), 0, 0, False, 0
-        best_w = self.store_packed()
-        keep_P = getattr(self, 'P', None)
-        for epoch in range(max_epochs):
-            tot = 0.0
-            for b0 in range(0, n_train, batch):
-                idx = perm[epoch, b0:b0 + batch]
-                rows = xtrain[idx]
-                if jitter != 0.0:
-                    nz = noise[epoch, b0:b0 + batch] if noise is not None else torch.randn(rows.shape, device=dev, generator=gen)
-                    rows = rows + float(jitter) * nz
-                loss, (gF, gS, gC) = self.loss_grad(rows)
-                self._adam(self.fast, gF, lr, weight_decay)
-                self._adam(self.slow, gS, lr, weight_decay)
-                self._adam(self.coupling, gC, lr, weight_decay)
-                tot += float(loss)
-            train_loss = tot / n_train
-            valid_loss = float(-self.log_probs(xvalid).mean()) / n_valid
-            losses[epoch] = (train_loss, valid_loss)
-            epochs_run = epoch + 1
-            if valid_loss < best:
-                best, best_epoch, counter, best_w = valid_loss, epoch + 1, 0, self.store_packed()
-            counter += 1
-            if counter > patience:
-                stopped = True
-                break
-        self.load_packed(best_w, keep_P)
-        if keep_P is not None:
-            self.fast.data_dep_init_done = self.slow.data_dep_init_done = True
-        return dict(losses=torch.from_numpy(losses), epochs_run=epochs_run, best_epoch=best_epoch, best_validation_loss=best,
-                    last_train_loss=float(losses[max(epochs_run - 1, 0), 0]), counter=counter, stopped=stopped, result=None)
+        return train_epochs_host(self, self._train_epoch, xtrain, xvalid, perm, noise, seed, jitter, batch, max_epochs, patience, lr,
+                                 weight_decay)
 
 
 class HipFastSlowSpline(HipFastSlowNVP):

@@ -62,11 +62,29 @@ TRAIN_KERNEL_MAX_BATCH = 128   # row slots of the one-launch training kernels (n
 
 
 class _HipFlow(object):
-    """What the two flow families share: the pass / proposal entry points differ only in the C symbol
-    (`self._sym[...]`, set by the subclass) -- same tensors in, same tensors out."""
+    """What the flow families share: the pass, proposal, gradient and optimiser entry points differ only in the C symbol
+    (`self._sym[...]`, filled in by the subclass through `_bind`) -- same tensors in, same tensors out."""
 
     base_beta = 0.0   # 0: N(0, I); > 0: GeneralisedNormal(0, 1, beta)
     base_dist = None  # the distribution object handed to Trainer(base_dist=...), if any
+
+    _FAMILY_ENTRIES = ('forward', 'inverse', 'log_probs', 'inverse_loglike', 'set_base', 'loss_grad', 'vjp', 'adam_step', 'destroy')
+
+    def _bind(self, family, **named):
+        """self._sym: the entry points `<family>_<name>` that the library declares for this family (nnest_chol has neither
+        inverse_loglike nor vjp: those names stay out), and the ones whose symbol does not follow the pattern, by name
+        (mh='nnest_mh_constrained_steps')"""
+        family_syms = [(n, '%s_%s' % (family, n)) for n in self._FAMILY_ENTRIES]
+        self._sym = {n: getattr(self._lib, sym) for n, sym in family_syms if sym in _lib.SIGNATURES}
+        self._sym.update((n, getattr(self._lib, sym)) for n, sym in named.items())
+
+    def __del__(self):
+        try:
+            if getattr(self, '_h', None) is not None and self._h.value:
+                self._sym['destroy'](self._h)
+                self._h = ctypes.c_void_p()
+        except Exception:
+            pass
 
     def set_base(self, base_dist):
         """NormalizingFlowModel(prior=...) (networks.py:47-59): None / MultivariateNormal(0, I) or GeneralisedNormal(0, 1, beta)"""
@@ -148,6 +166,40 @@ class _HipFlow(object):
                                                     _lib.ptr(x), _lib.ptr(ld), _lib.ptr(logl), _lib.ptr(inbox), N,
                                                     _lib.current_stream(self.device)))
         return x, ld, logl, inbox
+
+    # ---- gradient, chain-rule stage and optimiser step: one argument list in every family (_lib.SIGNATURES).  The library's vectors
+    # are the native ones (`_native_params` long; _PaddedVectors reorders, HipCholesky's are the packed ones as they are).
+    def loss_grad(self, x):
+        """loss = -mean(log_probs(x)) and dloss/dw (packed order) for one minibatch (loss.backward(), trainer.py:394-400), no weight
+        update.  The NVP's takes <= 128 rows."""
+        x = _as_dev_f32(x, self.device)
+        grad = torch.empty(self._native_params, dtype=torch.float32, device=self.device)
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._sym['loss_grad'](self._h, _lib.ptr(x), x.shape[0], _lib.ptr(grad), _lib.ptr(loss),
+                                              _lib.current_stream(self.device)))
+        return loss, self._from_native_dev(grad)
+
+    def vjp(self, x, gz, gld):
+        """the flow as one stage of a composite model (nnest_{nvp,spline}_vjp): upstream gradient gz [M,D] and dL/d(logdet) in,
+        dL/dw (packed order) and dL/dx out"""
+        fn = self._sym.get('vjp')
+        if fn is None:   # (a family without one: the handle must not reach another family's)
+            raise NotImplementedError('%s has no vjp entry point' % type(self).__name__)
+        M = x.shape[0]
+        grad = torch.empty(self._native_params, dtype=torch.float32, device=self.device)
+        gx = torch.empty_like(x)
+        with torch.cuda.device(self.device):
+            _lib.check(fn(self._h, _lib.ptr(x), _lib.ptr(gz.contiguous()), ctypes.c_float(gld), M, _lib.ptr(grad), _lib.ptr(gx),
+                          _lib.current_stream(self.device)))
+        return self._from_native_dev(grad), gx
+
+    def adam_step(self, grad, lr, weight_decay):
+        """one torch.optim.Adam step (coupled weight decay, trainer.py:121-122) from a gradient in packed order"""
+        grad = self._to_native_dev(grad)
+        with torch.cuda.device(self.device):
+            _lib.check(self._sym['adam_step'](self._h, _lib.ptr(grad), ctypes.c_float(lr), ctypes.c_float(weight_decay),
+                                              _lib.current_stream(self.device)))
 
     def mh_steps(self, like_id, like_scale, z, logl, loglstar, step_size, steps, dynamic=False, noise=None, seed=0,
                  walker_offset=0, history=False, like_params=None, lag=None, form=None, warm=None):
@@ -320,12 +372,21 @@ class _MhResult(dict):
             return default
 
 
-def train_epochs_host(net, xtrain, xvalid, perm, noise, seed, jitter, batch, max_epochs, patience, lr, weight_decay, chunk_rows):
-    """Trainer.train's epoch loop (nnest/trainer.py:198-241, :384-418) driven from the host for the shapes the one-launch training
-    kernels do not take (batch_size > 128: they hold a minibatch in one grid of 128 row slots): per minibatch the gradient of
-    -mean(log_probs) from `net.loss_grad` over chunks of at most `chunk_rows` rows -- the mean over M rows is the chunk means
-    weighted m_c / M, exact up to rounding -- and one `net.adam_step`; the early-stopping books as the reference keeps them.  A slower
-    path (a few launches per minibatch), not a refusal.  Arguments and return value as HipNVP.train_epochs."""
+def train_epochs_host(net, epoch_body, xtrain, xvalid, perm, noise, seed, jitter, batch, max_epochs, patience, lr, weight_decay,
+                      valid_sum=None):
+    """Trainer.train's epoch loop (nnest/trainer.py:198-241, :384-418) driven from the host, for every flow and shape the one-launch
+    training kernels do not take (HipNVP / HipSpline at batch_size > 128, and the MAF, Cholesky and fast/slow flows always): train an
+    epoch, validate, keep the best weights, count patience, restore the best.  A slower path (a few launches per minibatch), not a
+    refusal.  Needs nothing of `net` but store_packed / load_packed / log_probs / device (and `P`, handed back to load_packed where
+    the flow has one), so the books run on the CPU with a stand-in (tests/test_host_epoch_loop.py).
+
+    epoch_body(rows, epoch, n_train, batch, lr, weight_decay) pushes one epoch's minibatches through the flow and returns the sum of
+    their losses (a device scalar, read back together with the validation loss, or a float).  rows(epoch, lo, hi) are that epoch's
+    rows lo..hi in loader order with the jitter added (data + jitter * randn_like(data), trainer.py:392): recorded `noise`, or draws
+    of one generator seeded from `seed` -- in the order the body asks, so a body that asks for the whole epoch at once and one that
+    asks per minibatch see different draws, and each flow keeps the granularity it has.
+    valid_sum(xvalid): the validation loss before the division by n_valid; None = -mean over the whole set in one batch, as the
+    reference's valid_loader has it (trainer.py:190, :405-418).  Arguments and return value as HipNVP.train_epochs."""
     dev = net.device
     xtrain = _as_dev_f32(xtrain, dev)
     xvalid = _as_dev_f32(xvalid, dev)
@@ -335,32 +396,23 @@ def train_epochs_host(net, xtrain, xvalid, perm, noise, seed, jitter, batch, max
         noise = noise.to(device=dev, dtype=torch.float32).view(max_epochs, n_train, D)
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF)
+
+    def rows(epoch, lo, hi):
+        r = xtrain[perm[epoch, lo:hi]]
+        if jitter != 0.0:
+            nz = noise[epoch, lo:hi] if noise is not None else torch.randn(r.shape, device=dev, generator=gen)
+            r = r + float(jitter) * nz
+        return r
+
     losses = np.zeros((max(max_epochs, 1), 2), np.float32)
     best, best_epoch, counter, stopped, epochs_run = float('inf'), 0, 0, False, 0
     best_w = net.store_packed()                                            # best_model = deepcopy(netG)  trainer.py:194
     for epoch in range(max_epochs):
-        rows_all = xtrain[perm[epoch]]
-        if jitter != 0.0:                                                  # data + jitter * randn_like(data)  trainer.py:392
-            nz = noise[epoch] if noise is not None else torch.randn(rows_all.shape, device=dev, generator=gen)
-            rows_all = rows_all + float(jitter) * nz
-        tot = torch.zeros((), dtype=torch.float32, device=dev)
-        for lo in range(0, n_train, int(batch)):
-            rows = rows_all[lo:lo + int(batch)]
-            M = rows.shape[0]
-            if getattr(net, 'data_dep_init_done', True) is False:          # ActNorm: the first minibatch pushed forward through a
-                net.actnorm_init(rows.contiguous())                        # fresh spline flow initialises it (networks.py:698-705)
-            grad = loss = None
-            for c0 in range(0, M, int(chunk_rows)):
-                part = rows[c0:c0 + int(chunk_rows)].contiguous()
-                l_c, g_c = net.loss_grad(part)
-                wgt = part.shape[0] / M
-                grad = g_c * wgt if grad is None else grad + g_c * wgt
-                loss = l_c[0] * wgt if loss is None else loss + l_c[0] * wgt
-            net.adam_step(grad, lr, weight_decay)                          # trainer.py:400-401
-            tot = tot + loss                                               # train_loss += loss.item()  trainer.py:398
-        vsum = -net.log_probs(xvalid).mean()                               # one full batch  trainer.py:190, :405-418
-        both = torch.stack([tot, vsum.to(tot.dtype)]).cpu()                # one read-back per epoch
-        train_loss, valid_loss = float(both[0]) / n_train, float(both[1]) / n_valid
+        tot = epoch_body(rows, epoch, n_train, int(batch), lr, weight_decay)   # train_loss += loss.item()  trainer.py:398
+        vsum = -net.log_probs(xvalid).mean() if valid_sum is None else valid_sum(xvalid)
+        if torch.is_tensor(tot):
+            tot, vsum = torch.stack([tot, vsum.to(tot.dtype)]).cpu().tolist()  # one read-back per epoch
+        train_loss, valid_loss = tot / n_train, float(vsum) / n_valid      # trainer.py:403, :418
         losses[epoch] = (train_loss, valid_loss)
         epochs_run = epoch + 1
         if valid_loss < best:                                              # trainer.py:205-209
@@ -369,12 +421,38 @@ def train_epochs_host(net, xtrain, xvalid, perm, noise, seed, jitter, batch, max
         if counter > patience:                                             # trainer.py:223-232
             stopped = True
             break
-    if hasattr(net, 'P'):
-        net.load_packed(best_w, net.P)                                     # netG.load_state_dict(best_model)  trainer.py:241
+    P = getattr(net, 'P', None)                                            # the spline flows' permutations travel beside the packed vector
+    if P is None:
+        net.load_packed(best_w)                                            # netG.load_state_dict(best_model)  trainer.py:241
     else:
-        net.load_packed(best_w)
+        net.load_packed(best_w, P)
     return dict(losses=torch.from_numpy(losses), epochs_run=epochs_run, best_epoch=best_epoch, best_validation_loss=best,
                 last_train_loss=float(losses[max(epochs_run - 1, 0), 0]), counter=counter, stopped=stopped, result=None)
+
+
+def chunked_epoch(net, chunk_rows):
+    """the epoch body of HipNVP / HipSpline for train_epochs_host: per minibatch the gradient of -mean(log_probs) from `net.loss_grad`
+    over chunks of at most `chunk_rows` rows -- the mean over M rows is the chunk means weighted m_c / M, exact up to rounding -- and
+    one `net.adam_step`; one gather and one draw per epoch, a minibatch is a slice"""
+    def body(rows, epoch, n_train, batch, lr, weight_decay):
+        rows_all = rows(epoch, 0, n_train)
+        tot = torch.zeros((), dtype=torch.float32, device=net.device)
+        for lo in range(0, n_train, batch):
+            mb = rows_all[lo:lo + batch]
+            M = mb.shape[0]
+            if getattr(net, 'data_dep_init_done', True) is False:          # ActNorm: the first minibatch pushed forward through a
+                net.actnorm_init(mb.contiguous())                          # fresh spline flow initialises it (networks.py:698-705)
+            grad = loss = None
+            for c0 in range(0, M, int(chunk_rows)):
+                part = mb[c0:c0 + int(chunk_rows)].contiguous()
+                l_c, g_c = net.loss_grad(part)
+                wgt = part.shape[0] / M
+                grad = g_c * wgt if grad is None else grad + g_c * wgt
+                loss = l_c[0] * wgt if loss is None else loss + l_c[0] * wgt
+            net.adam_step(grad, lr, weight_decay)                          # trainer.py:400-401
+            tot = tot + loss
+        return tot
+    return body
 
 
 def native_hidden(H):
@@ -461,9 +539,7 @@ class HipNVP(_PaddedVectors, _HipFlow):
             raise ValueError("scale=%r: expected '', 'translate' or 'constant' (networks.py:330-332)" % (scale,))
         self.scale = scale
         self._lib = _lib.load()
-        L = self._lib
-        self._sym = dict(forward=L.nnest_nvp_forward, inverse=L.nnest_nvp_inverse, log_probs=L.nnest_nvp_log_probs,
-                         inverse_loglike=L.nnest_nvp_inverse_loglike, mh=L.nnest_mh_constrained_steps, set_base=L.nnest_nvp_set_base)
+        self._bind('nnest_nvp', mh='nnest_mh_constrained_steps')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (_PaddedVectors)
         with torch.cuda.device(self.device):
@@ -519,14 +595,6 @@ class HipNVP(_PaddedVectors, _HipFlow):
                 int(seed) & 0xFFFFFFFFFFFFFFFF, 0 if loglstar is None else 1, 0.0 if loglstar is None else float(loglstar),
                 _lib.current_stream(dev)))
         return out
-
-    def __del__(self):
-        try:
-            if getattr(self, '_h', None) is not None and self._h.value:
-                self._lib.nnest_nvp_destroy(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
 
     def _init_padding(self):
         """num_params and the packed layout are the USER's (hidden width H); the native vector has width _Hn"""
@@ -668,35 +736,6 @@ class HipNVP(_PaddedVectors, _HipFlow):
                                                      v.ctypes.data_as(ctypes.c_void_p), _lib.current_stream(self.device)))
             _lib.check(self._lib.nnest_nvp_adam_state(self._h, None, int(step), 0, _lib.current_stream(self.device)))
 
-    def loss_grad(self, x):
-        """loss = -mean(log_probs(x)) and dloss/dw (packed order) for one minibatch of <= 128 rows
-        (loss.backward(), trainer.py:394-400), no weight update."""
-        x = _as_dev_f32(x, self.device)
-        grad = torch.empty(self._native_params, dtype=torch.float32, device=self.device)
-        loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.nnest_nvp_loss_grad(self._h, _lib.ptr(x), x.shape[0], _lib.ptr(grad), _lib.ptr(loss),
-                                                     _lib.current_stream(self.device)))
-        return loss, self._from_native_dev(grad)
-
-    def vjp(self, x, gz, gld):
-        """the flow as one stage of a composite model (nnest_nvp_vjp): upstream gradient gz [M,D] and dL/d(logdet) in,
-        dL/dw (packed order) and dL/dx out"""
-        M = x.shape[0]
-        grad = torch.empty(self._native_params, dtype=torch.float32, device=self.device)
-        gx = torch.empty_like(x)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.nnest_nvp_vjp(self._h, _lib.ptr(x), _lib.ptr(gz.contiguous()), ctypes.c_float(gld), M, _lib.ptr(grad),
-                                               _lib.ptr(gx), _lib.current_stream(self.device)))
-        return self._from_native_dev(grad), gx
-
-    def adam_step(self, grad, lr, weight_decay):
-        """one torch.optim.Adam step (coupled weight decay, trainer.py:121-122) from a gradient in packed order"""
-        grad = self._to_native_dev(grad)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.nnest_nvp_adam_step(self._h, _lib.ptr(grad), ctypes.c_float(lr), ctypes.c_float(weight_decay),
-                                                     _lib.current_stream(self.device)))
-
     def train_epochs(self, xtrain, xvalid, perm, noise=None, seed=0, jitter=0.0, batch=100, max_epochs=1, patience=50,
                      lr=1e-3, weight_decay=1e-6, epoch_offset=0, resume=False, finalize=True, result=None, one_cu=False):
         """K5: Trainer.train's epoch loop (trainer.py:198-241) in one launch.  perm int32 [max_epochs, n_train];
@@ -708,8 +747,8 @@ class HipNVP(_PaddedVectors, _HipFlow):
         dev = self.device
         if int(batch) > TRAIN_KERNEL_MAX_BATCH:   # the reference takes any batch_size (trainer.py:36, :76, :185): a slower path, not a refusal
             assert not resume and epoch_offset == 0, 'batch_size > %d: the host-driven loop takes a run in one call' % TRAIN_KERNEL_MAX_BATCH
-            return train_epochs_host(self, xtrain, xvalid, perm, noise, seed, jitter, batch, max_epochs, patience, lr, weight_decay,
-                                     chunk_rows=TRAIN_KERNEL_MAX_BATCH)
+            return train_epochs_host(self, chunked_epoch(self, TRAIN_KERNEL_MAX_BATCH), xtrain, xvalid, perm, noise, seed, jitter, batch,
+                                     max_epochs, patience, lr, weight_decay)
         xtrain = _as_dev_f32(xtrain, dev)
         xvalid = _as_dev_f32(xvalid, dev)
         perm = perm.to(device=dev, dtype=torch.int32).contiguous()

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .flow import _HipFlow, _PaddedVectors, _as_dev_f32, pad_index, native_hidden, train_epochs_host, TRAIN_KERNEL_MAX_BATCH
+from .flow import _HipFlow, _PaddedVectors, _as_dev_f32, pad_index, native_hidden, train_epochs_host, chunked_epoch, TRAIN_KERNEL_MAX_BATCH
 
 
 class HipSpline(_PaddedVectors, _HipFlow):
@@ -32,9 +32,7 @@ class HipSpline(_PaddedVectors, _HipFlow):
         self.nl = self.D - self.nu
         self._lib = _lib.load()
         L = self._lib
-        self._sym = dict(forward=L.nnest_spline_forward, inverse=L.nnest_spline_inverse, log_probs=L.nnest_spline_log_probs,
-                         inverse_loglike=L.nnest_spline_inverse_loglike, mh=L.nnest_spline_mh_constrained_steps,
-                         set_base=L.nnest_spline_set_base)
+        self._bind('nnest_spline', mh='nnest_spline_mh_constrained_steps')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (flow._PaddedVectors: zero-padded, exact)
         with torch.cuda.device(self.device):
@@ -117,14 +115,6 @@ class HipSpline(_PaddedVectors, _HipFlow):
         """'rows' (one row of the minibatch per workgroup, nnest_spline_rows.hip) or 'tiles' (nnest_spline_train.hip): what a minibatch
         of `batch` rows runs in (nnest_spline_train_form)"""
         return 'rows' if self._lib.nnest_spline_train_form(self._h, int(batch)) == 1 else 'tiles'
-
-    def __del__(self):
-        try:
-            if getattr(self, '_h', None) is not None and self._h.value:
-                self._lib.nnest_spline_destroy(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
 
     # ---- weights ---------------------------------------------------------------------------------
     def layer_shapes(self):
@@ -240,34 +230,6 @@ class HipSpline(_PaddedVectors, _HipFlow):
     # ---- training ---------------------------------------------------------------------------------
     epoch_chunk = 1 << 30   # Trainer.train hands the whole run to one call (the epoch loop is host-driven here)
 
-    def loss_grad(self, x):
-        """loss = -mean(log_probs(x)) and dloss/dw (packed order), no weight update (trainer.py:394-400)"""
-        x = _as_dev_f32(x, self.device)
-        grad = torch.empty(self._native_params, dtype=torch.float32, device=self.device)
-        loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.nnest_spline_loss_grad(self._h, _lib.ptr(x), x.shape[0], _lib.ptr(grad), _lib.ptr(loss),
-                                                        _lib.current_stream(self.device)))
-        return loss, self._from_native_dev(grad)
-
-    def vjp(self, x, gz, gld):
-        """the flow as one stage of a composite model (nnest_spline_vjp): upstream gradient gz [M,D] and dL/d(logdet) in,
-        dL/dw (packed order) and dL/dx out"""
-        M = x.shape[0]
-        grad = torch.empty(self._native_params, dtype=torch.float32, device=self.device)
-        gx = torch.empty_like(x)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.nnest_spline_vjp(self._h, _lib.ptr(x), _lib.ptr(gz.contiguous()), ctypes.c_float(gld), M, _lib.ptr(grad),
-                                                  _lib.ptr(gx), _lib.current_stream(self.device)))
-        return self._from_native_dev(grad), gx
-
-    def adam_step(self, grad, lr, weight_decay):
-        """one torch.optim.Adam step (coupled weight decay, trainer.py:121-122) from a gradient in packed order"""
-        grad = self._to_native_dev(grad)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.nnest_spline_adam_step(self._h, _lib.ptr(grad), ctypes.c_float(lr), ctypes.c_float(weight_decay),
-                                                        _lib.current_stream(self.device)))
-
     def train_epochs(self, xtrain, xvalid, perm, noise=None, seed=0, jitter=0.0, batch=100, max_epochs=1, patience=50,
                      lr=1e-3, weight_decay=1e-6, epoch_offset=0, resume=False, finalize=True, result=None):
         """Trainer.train's epoch loop (trainer.py:198-241); same arguments and return value as HipNVP.train_epochs.  The
@@ -275,8 +237,9 @@ class HipSpline(_PaddedVectors, _HipFlow):
         assert not resume and epoch_offset == 0, 'the spline trainer takes a run in one call'
         dev = self.device
         if int(batch) > TRAIN_KERNEL_MAX_BATCH:   # the reference takes any batch_size (trainer.py:36, :76, :185): a slower path, not a refusal
-            return train_epochs_host(self, xtrain, xvalid, perm, noise, seed, jitter, batch, max_epochs, patience, lr, weight_decay,
-                                     chunk_rows=1 << 30)   # (nnest_spline_loss_grad takes a minibatch of any size in one call)
+            # (nnest_spline_loss_grad takes a minibatch of any size in one call: one chunk)
+            return train_epochs_host(self, chunked_epoch(self, 1 << 30), xtrain, xvalid, perm, noise, seed, jitter, batch, max_epochs,
+                                     patience, lr, weight_decay)
         xtrain = _as_dev_f32(xtrain, dev)
         xvalid = _as_dev_f32(xvalid, dev)
         perm = perm.to(device=dev, dtype=torch.int32).contiguous()

@@ -109,7 +109,7 @@ class Trainer(object):
             self.netG = HipNVP(x_dim, hidden_dim, num_blocks, num_layers, device=self.gpu, seed=seed, scale=scale)
         self.replicable = self.flow in ('nvp', 'spline') and num_slow == 0   # the two single-launch training paths
         if batch_size > 128:
-            self.netG.epoch_chunk = 1 << 30   # flow.train_epochs_host takes a run in one call
+            self.netG.epoch_chunk = 1 << 30   # the host-driven epoch loop (flow.train_epochs_host) takes a run in one call
         if gen_normal is not None:
             self.netG.set_base(gen_normal)
             self.netG.prior = gen_normal

@@ -67,7 +67,8 @@ def tensor_slices(shapes):
 #     ns = ceil(ceil(23 nmax / 16) / NW):  splr_grad_kernel<1,12> (NW 1), <2,8> (NW 2, ns <= 8), <2,12>, <4,9> (ns <= 9), <4,12>;
 #     splr_update_kernel<26> for M <= 104, <32> above.
 #   tile form (nnest_spline_train.hip, DISPATCH_SPLT): key = 10 NTh + NH, NTh = ceil(ceil(D/2) / 16), NH = native hidden / 16;
-#     rows per tile 16 for NTh 1, 8 above (rows_per_tile).  M > 128 takes the host epoch loop (train_epochs_host) over loss_grad.
+#     rows per tile 16 for NTh 1, 8 above (rows_per_tile).  M > 128 takes the host epoch loop (flow.train_epochs_host with
+#     flow.chunked_epoch) over loss_grad.
 # ROWS_TABLE runs the rows form in-process and the tile form (keys 11 / 21) in a child process with NNEST_SPL_ROWS=0.
 ROWS_TABLE = [
     # D,  H, B,   M    rows form                     tile form (NNEST_SPL_ROWS=0)
