@@ -218,9 +218,10 @@ __global__ void __launch_bounds__(256) ensemble_kernel(EnsArgs a) {
             ld += solo_coupling_inverse4<U>(Solo4Lds{wlds, lane}, sel, h1, xs[1], xs[0]);
             return ld;
         } else {
-            float ld = solo_coupling_inverse<U>(net[2], sel, h1, xs[1], xs[0]);
-            ld += solo_coupling_inverse<U>(net[1], sel, h1, xs[0], xs[1]);
-            ld += solo_coupling_inverse<U>(net[0], sel, h1, xs[1], xs[0]);
+            float ld;
+            solo_coupling_inverse<U, true>(net[2], sel, h1, xs[1], xs[0], ld);
+            solo_coupling_inverse<U, false>(net[1], sel, h1, xs[0], xs[1], ld);
+            solo_coupling_inverse<U, false>(net[0], sel, h1, xs[1], xs[0], ld);
             return ld;
         }
     };

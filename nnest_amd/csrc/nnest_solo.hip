@@ -19,7 +19,8 @@
 // rows issue the same row_ror:0..7), one v_permlane16_swap + add joins the halves, one v_permlane32_swap hands log_s to the
 // translate half and t to the scale half: both nets of a coupling block run concurrently in ONE wave, with no LDS exchange
 // and no workgroup barrier inside the flow.  Per block and U = 2: 40 v_fmac (against 12 MFMA + 9 DPP + 9 permlane + ...),
-// 4 half-joins, 2 net swaps; 44 weight registers per lane and block.
+// 2 half-joins (the last layer runs over the whole K per row: row h owns output slot h), 1 net swap, 1 swap that hands the two
+// new slots to both rows; 44 weight registers per lane and block; the block is one asm statement (solo_tile.h: solo_block2).
 //
 // One workgroup = WPG net waves (walkers WPG tile .. WPG tile + WPG - 1; WPG = 4, or 8 / 12 beyond one walker per SIMD: round 4)
 // + one noise wave that draws the next step's proposal noise (the xoshiro streams of every other form: nnest_mh_fill_noise
@@ -350,9 +351,10 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
             ld += solo_coupling_inverse4<U>(Solo4Lds{wlds, lane}, sel, h1, xs[1], xs[0]);
             return ld;
         } else {
-            float ld = solo_coupling_inverse<U>(net[2], sel, h1, xs[1], xs[0]);
-            ld += solo_coupling_inverse<U>(net[1], sel, h1, xs[0], xs[1]);
-            ld += solo_coupling_inverse<U>(net[0], sel, h1, xs[1], xs[0]);
+            float ld;
+            solo_coupling_inverse<U, true>(net[2], sel, h1, xs[1], xs[0], ld);
+            solo_coupling_inverse<U, false>(net[1], sel, h1, xs[0], xs[1], ld);
+            solo_coupling_inverse<U, false>(net[0], sel, h1, xs[1], xs[0], ld);
             return ld;
         }
     };
@@ -434,8 +436,12 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
 #pragma unroll
             for (int uu = 0; uu < U; ++uu) r.xp[c][uu] = r.zp[c][uu];
         STAMP(st1);
-        r.ldp = solo_logdet_total(inverse(r.xp));  // sampler.py:321
+        // sampler.py:321.  The kernel compiled for Rosenbrock hands the lane's log-det partial to the likelihood, whose row sum carries
+        // the partial's reduction in its wait states (solo_logdet_total_and_row_sum); the general kernel reduces it here
+        constexpr bool RIDE = LK == NNEST_LIKE_ROSENBROCK;
+        r.ldp = RIDE ? inverse(r.xp) : solo_logdet_total(inverse(r.xp));
         STAMP(st2);
+        if constexpr (RIDE) r.lp = solo_loglike<U, LK>(like, D, lane, r.xp, &r.ldp);
         // log_ratio = log_det_J' - log_det_J, -inf outside the prior box  (sampler.py:326-331); UniformPrior(D,-1,1)
         // (priors.py:39-43): NaN compares false, i.e. counts as inside; padded dims hold 0
         int okl = 1;
@@ -448,7 +454,7 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         float ratio = fminf(__expf(log_ratio), 1.0f);  // exp().clamp(max=1)  :335
         if (log_ratio != log_ratio) ratio = log_ratio;  // NaN stays NaN (u < NaN is false, as in torch)
         r.pre = ok && (u < ratio);                      // :336
-        r.lp = solo_loglike<U, LK>(like, D, lane, r.xp);
+        if constexpr (!RIDE) r.lp = solo_loglike<U, LK>(like, D, lane, r.xp);
         r.acc = r.pre && (r.lp > loglstar);  // :361
         if (free_mode) {  // sampler.py:396-410
             const double lr = inb ? (double)(r.ldp - ld) + (r.lp - logl) : -INFINITY;
@@ -641,9 +647,10 @@ __global__ void __launch_bounds__(256) slice_kernel_solo(SliceArgs a) {
             ld += solo_coupling_inverse4<U>(Solo4Lds{wlds, lane}, sel, h1, xs[1], xs[0]);
             return ld;
         } else {
-            float ld = solo_coupling_inverse<U>(net[2], sel, h1, xs[1], xs[0]);
-            ld += solo_coupling_inverse<U>(net[1], sel, h1, xs[0], xs[1]);
-            ld += solo_coupling_inverse<U>(net[0], sel, h1, xs[1], xs[0]);
+            float ld;
+            solo_coupling_inverse<U, true>(net[2], sel, h1, xs[1], xs[0], ld);
+            solo_coupling_inverse<U, false>(net[1], sel, h1, xs[0], xs[1], ld);
+            solo_coupling_inverse<U, false>(net[0], sel, h1, xs[1], xs[0], ld);
             return ld;
         }
     };

@@ -7,9 +7,12 @@ namespace nnest {
 
 // ---- likelihoods on a solo wave (the per-term arithmetic of loglike_tile, flow_tile.h; sums over the 16 positions) ----
 #pragma clang fp contract(off)
+// ld_ride: if given, the lane's log-det partial, replaced by the walker's total (solo_logdet_total) -- its reduction rides in the
+// wait states of the likelihood's own row sum where there is one (Rosenbrock: solo_logdet_total_and_row_sum), same bits either way.
 template <int U, int LK>   // LK >= 0: the likelihood id is known at compile time (the other branches are not instantiated)
-static __device__ __forceinline__ double solo_loglike(const LikeSpec &lk_in, int D, int lane, const float (&xs)[2][U]) {
+static __device__ __forceinline__ double solo_loglike(const LikeSpec &lk_in, int D, int lane, const float (&xs)[2][U], float *ld_ride = nullptr) {
     struct { int id; float scale; const float *p; } lk = {LK >= 0 ? LK : lk_in.id, lk_in.scale, lk_in.p};
+    if (ld_ride && lk.id != 0) *ld_ride = solo_logdet_total(*ld_ride);
     const int m = lane & 15;
     const float scale = lk.scale;
     float th[2 * U + 1];
@@ -32,7 +35,9 @@ static __device__ __forceinline__ double solo_loglike(const LikeSpec &lk_in, int
             float term = e + q;
             facc = facc + ((i + 1 < D) ? term : 0.f);
         }
-        acc = -(double)solo_row_sum(facc);
+        if (ld_ride) solo_logdet_total_and_row_sum(*ld_ride, facc);
+        else facc = solo_row_sum(facc);
+        acc = -(double)facc;
     } else if (lk.id == 1) {
         // GaussianMix (likelihoods.py:165-189): logsumexp_k[ log w_k - |theta - mu_k|^2/2 - (D/2) log 2pi ]
         float facc = 0.f;

@@ -54,6 +54,8 @@ struct SoloNet {  // this lane's share of one coupling block (its net n, its K-h
     float w1[U][8], w2[8], w3[U][8];
     float b1, b2, b3[U];  // biases ride in the h = 0 half; 0 in the h = 1 half
 };
+// U = 2 lays the LAST layer out differently (solo_block2, solo_chain_full): row h holds the 16 rotations of output slot h --
+// w3[0][t] rotation t, w3[1][t] rotation 8 + t, b3[0] the slot's bias in both rows, b3[1] = 0 -- still 44 weights per lane.
 
 // gather from the packed (block, net) region (LDS copy), state_dict layout W0[H][D] b0[H] W1[H][H] b1[H] Wo[D][H] bo[D]
 // (nnest/networks.py:271-282).  cc / ct: conditioning / transformed parity class of the block.
@@ -74,8 +76,13 @@ static __device__ __forceinline__ void solo_gather(SoloNet<U> &n, const float *p
         for (int u = 0; u < U; ++u) {
             const int d = 2 * U * q + 2 * u + cc;
             n.w1[u][t] = d < D ? cs * p[pos * D + d] : 0.f;
-            const int dO = 2 * U * pos + 2 * u + ct;  // dim of this lane's transformed slot u
-            n.w3[u][t] = dO < D ? p[pWo + dO * H + q] : 0.f;
+            if constexpr (U == 2) {   // last layer over the whole K: row h owns output slot h, rotations t in w3[0], 8 + t in w3[1]
+                const int dO = 2 * U * pos + 2 * h + ct;
+                n.w3[u][t] = dO < D ? p[pWo + dO * H + ((pos - t - 8 * u) & 15)] : 0.f;
+            } else {
+                const int dO = 2 * U * pos + 2 * u + ct;  // dim of this lane's transformed slot u
+                n.w3[u][t] = dO < D ? p[pWo + dO * H + q] : 0.f;
+            }
         }
         n.w2[t] = cs * p[pW1 + pos * H + q];
     }
@@ -83,8 +90,9 @@ static __device__ __forceinline__ void solo_gather(SoloNet<U> &n, const float *p
     n.b2 = h == 0 ? cs * p[pb1 + pos] : 0.f;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const int dO = 2 * U * pos + 2 * u + ct;
-        n.b3[u] = (h == 0 && dO < D) ? p[pbo + dO] : 0.f;
+        const int dO = 2 * U * pos + 2 * (U == 2 ? h : u) + ct;
+        if constexpr (U == 2) n.b3[u] = (u == 0 && dO < D) ? p[pbo + dO] : 0.f;   // the bias of slot h rides in the first accumulator of both rows
+        else n.b3[u] = (h == 0 && dO < D) ? p[pbo + dO] : 0.f;
     }
 }
 
@@ -136,6 +144,18 @@ static __device__ __forceinline__ void solo_chain_2out(float &a0, float &a1, flo
         : "v"(x), "v"(w0[0]), "v"(w0[1]), "v"(w0[2]), "v"(w0[3]), "v"(w0[4]), "v"(w0[5]), "v"(w0[6]), "v"(w0[7]),
           "v"(w1[0]), "v"(w1[1]), "v"(w1[2]), "v"(w1[3]), "v"(w1[4]), "v"(w1[5]), "v"(w1[6]), "v"(w1[7]), "v"(b0), "v"(b1));
 }
+// one output over the WHOLE K: a0 = b0 + sum_{t < 8} w0[t] x[(p - t) & 15],  a1 = +0 + sum_{t < 8} w1[t] x[(p - 8 - t) & 15] -- the
+// two K-halves that solo_chain_2out leaves in the rows h = 0 / 1 for one of its outputs, operation for operation (the h = 1 rows
+// open theirs with v_fma(x, w, +0): hence the zeroed register, whose move is also the wait state of the first DPP read of x)
+static __device__ __forceinline__ void solo_chain_full(float &a0, float &a1, float b0, float x, const float (&w0)[8], const float (&w1)[8]) {
+    asm("v_fma_f32 %0, %2, %3, %19\n\t" "v_mov_b32 %1, 0\n\t" SOLO_D(1, 2, 11, 8)
+        SOLO_D(0, 2, 4, 1) SOLO_D(1, 2, 12, 9) SOLO_D(0, 2, 5, 2) SOLO_D(1, 2, 13, 10) SOLO_D(0, 2, 6, 3) SOLO_D(1, 2, 14, 11)
+        SOLO_D(0, 2, 7, 4) SOLO_D(1, 2, 15, 12) SOLO_D(0, 2, 8, 5) SOLO_D(1, 2, 16, 13) SOLO_D(0, 2, 9, 6) SOLO_D(1, 2, 17, 14)
+        SOLO_D(0, 2, 10, 7) SOLO_D(1, 2, 18, 15)
+        : "=&v"(a0), "=&v"(a1)
+        : "v"(x), "v"(w0[0]), "v"(w0[1]), "v"(w0[2]), "v"(w0[3]), "v"(w0[4]), "v"(w0[5]), "v"(w0[6]), "v"(w0[7]),
+          "v"(w1[0]), "v"(w1[1]), "v"(w1[2]), "v"(w1[3]), "v"(w1[4]), "v"(w1[5]), "v"(w1[6]), "v"(w1[7]), "v"(b0));
+}
 // a0 = b0 + sum_{t even} w[t] x[(p - t) & 15],  a1 = sum_{t odd} ...   (one input, one output over two accumulators)
 static __device__ __forceinline__ void solo_chain_1(float &a0, float &a1, float b0, float x, const float (&w)[8]) {
     asm("s_nop 0\n\t"
@@ -172,45 +192,160 @@ static __device__ __forceinline__ void solo_swap16(float &a, float &b) {
 }
 
 // CouplingLayer.inverse (networks.py:300-309), both nets at once (the wave's two halves); returns the lane's log-det partial.
-// U = 2: the last layer's two outputs are reduce-SCATTERED over the K-halves (one swap: row h ends with output u = h), so the
-// affine update runs once per lane on the slot its row owns and one more swap hands both results to both rows; the log-det
-// partial is then per row (the caller sums rows h = 0 and 1, solo_logdet_total).
+// One slot per class (U = 1), statement by statement: the chains, joins and swaps above, hipcc's code in between.
 template <int U>
-static __device__ __forceinline__ float solo_coupling_inverse(const SoloNet<U> &w, unsigned sel, bool h1, const float (&cond)[U],
-                                                              float (&trans)[U]) {
+static __device__ __forceinline__ float solo_coupling_inverse1(const SoloNet<U> &w, unsigned sel, bool h1, const float (&cond)[U],
+                                                               float (&trans)[U]) {
+    static_assert(U == 1, "the statement-by-statement block: one slot per class");
     float a0, a1;
-    if constexpr (U == 2) {
-        solo_chain_2in(a0, a1, w.b1, solo_rot8_h1(cond[0]), solo_rot8_h1(cond[1]), w.w1[0], w.w1[1]);
-    } else {
-        solo_chain_1(a0, a1, w.b1, solo_rot8_h1(cond[0]), w.w1[0]);
-    }
+    solo_chain_1(a0, a1, w.b1, solo_rot8_h1(cond[0]), w.w1[0]);
     float hid = solo_activate(solo_join_rot(a0 + a1), sel);   // (h = 1 rows: rotated by 8, as the next chain reads it)
     solo_chain_1(a0, a1, w.b2, hid, w.w2);
     const float hin = solo_activate(solo_join_rot(a0 + a1), sel);
-    if constexpr (U == 2) {
-        float o0, o1;
-        solo_chain_2out(o0, o1, w.b3[0], w.b3[1], hin, w.w3[0], w.w3[1]);
-        solo_swap16(o0, o1);               // rows h = 0: both halves of output 0; rows h = 1: both halves of output 1
-        float ls, tt;
-        solo_nets(o0 + o1, ls, tt);
-        const float cur = h1 ? trans[1] : trans[0];
-        float nw = (cur - tt) * __expf(-ls);  // (inputs - t) * exp(-log_s)   networks.py:307-309
-        float nb = nw;
-        solo_swap16(nw, nb);               // every row: nw = slot 0's new value, nb = slot 1's
-        trans[0] = nw;
-        trans[1] = nb;
-        return -ls;
+    float o0, o1;
+    solo_chain_1(o0, o1, w.b3[0], hin, w.w3[0]);
+    float ls, tt;
+    solo_nets(solo_join(o0 + o1), ls, tt);
+    trans[0] = (trans[0] - tt) * __expf(-ls);
+    return h1 ? 0.f : -ls;             // the same value in both rows: counted once
+}
+
+// ---- U = 2: a coupling block as ONE asm statement --------------------------------------------------------------------------
+// Statement by statement (the form above, which U = 2 had through round 6) hipcc pads a wait state behind every statement whose
+// outputs the next instruction reads, cannot move its own instructions into the wait states the statements carry, and copies a
+// value whenever a swap wants it twice: a quarter of the step's issue slots were s_nop and v_mov_b32, on a wave that pays 4 cycles
+// for each.  Here the whole block is ours; every wait state the hardware asks for is in the string, filled with an instruction
+// of the block where one is free, and nothing else:
+//   VALU write -> DPP read of it: 2 states;  VALU write -> v_permlane*_swap operand: 2;  v_exp / v_rcp -> other VALU read: 1.
+// The arithmetic is, operation for operation and operand for operand, the one hipcc emitted for the statements:
+//   x_k    = cond_k, rotated by 8 in the h = 1 rows                                   (v_mov + row-masked v_mov_dpp)
+//   a0, a1 = first layer, one accumulator per input, bias in a0                       (16)
+//   cur    = the slot this row updates (v_bfi_b32 on the row mask), placed where the rotation's DPP read needs a wait state
+//   s      = a0 + a1;  b = ror8(a0) + ror8(a1) -- bit for bit ror8(s) -- ; swap; s + b (solo_join_rot; the rotated copy comes from
+//            a DPP move of a1 and a DPP add of a0: neither waits for s, and s itself is the wait state a0's last write needs)
+//   hid    = bfi(sel, max(0, v), 1 - 2 rcp(exp2(v) + 1))                              (solo_activate; v_max between exp and add)
+//   second layer on two accumulators (solo_chain_1), plain join (the sum written twice: the swap's second copy), activation
+//   last layer over the WHOLE K: row h computes output slot h -- rotations 0..7 on one accumulator, started from the bias,
+//            8..15 on the other, started from a zeroed register (as the h = 1 rows' v_fma(x, w, +0) did: the zeroing is the wait state
+//            the first DPP read of the activation needs) -- which are the two K-halves the rows used to trade with a swap
+//   o = a0 + a1 (twice), v_permlane32_swap: log_s and t in every lane;  new = (cur - t) * exp2(-log2(e) log_s) (twice),
+//            the log-det partial, v_permlane16_swap: both new slots in every row, in the registers the next block reads them from.
+// Per block: 83 instructions, 7 of them s_nop (3 x s_nop 1 in front of the swaps that nothing fills, 4 x s_nop 0), no v_mov_b32
+// but the two that start the rotated inputs.  tools/check_wait_states.py checks the distances in the built kernels.
+#define SOLO_BD(acc, x, w, t) "v_fmac_f32_dpp %[" #acc "], %[" #x "], %[" #w "] row_ror:" #t " row_mask:0xf bank_mask:0xf\n\t"
+#define SOLO_BW8(n, a) [n##0] "v"(a[0]), [n##1] "v"(a[1]), [n##2] "v"(a[2]), [n##3] "v"(a[3]), [n##4] "v"(a[4]), [n##5] "v"(a[5]), [n##6] "v"(a[6]), [n##7] "v"(a[7])
+#define SOLO_BLOCK2_ACT /* p0 = activation of a0 (p0, p1 scratch); result in a0 */                                           \
+        "v_exp_f32 %[p0], %[a0]\n\t"                                                                                          \
+        "v_max_f32 %[p1], 0, %[a0]\n\t"                                                                                       \
+        "v_add_f32 %[p0], 1.0, %[p0]\n\t"                                                                                     \
+        "v_rcp_f32 %[p0], %[p0]\n\t"                                                                                          \
+        "s_nop 0\n\t"                                                                                                         \
+        "v_fma_f32 %[p0], %[p0], -2.0, 1.0\n\t"                                                                               \
+        "v_bfi_b32 %[a0], %[sel], %[p1], %[p0]\n\t"
+#define SOLO_BLOCK2(LD_LINE)                                                                                                  \
+        "v_mov_b32 %[p0], %[c0]\n\t"                                                                                          \
+        "v_mov_b32 %[p1], %[c1]\n\t"                                                                                          \
+        "v_bfi_b32 %[cur], %[h1], %[i1], %[i0]\n\t"          /* the slot this row updates; here it is a wait state */        \
+        "v_mov_b32_dpp %[p0], %[c0] row_ror:8 row_mask:0xa bank_mask:0xf\n\t"                                                 \
+        "v_mov_b32_dpp %[p1], %[c1] row_ror:8 row_mask:0xa bank_mask:0xf\n\t"                                                 \
+        "v_fma_f32 %[a0], %[p0], %[wa0], %[b1]\n\t"                                                                           \
+        "v_mul_f32 %[a1], %[p1], %[wb0]\n\t"                                                                                  \
+        SOLO_BD(a1, p1, wb1, 1) SOLO_BD(a0, p0, wa1, 1) SOLO_BD(a1, p1, wb2, 2) SOLO_BD(a0, p0, wa2, 2)                       \
+        SOLO_BD(a1, p1, wb3, 3) SOLO_BD(a0, p0, wa3, 3) SOLO_BD(a1, p1, wb4, 4) SOLO_BD(a0, p0, wa4, 4)                       \
+        SOLO_BD(a1, p1, wb5, 5) SOLO_BD(a0, p0, wa5, 5) SOLO_BD(a1, p1, wb6, 6) SOLO_BD(a0, p0, wa6, 6)                       \
+        SOLO_BD(a1, p1, wb7, 7) SOLO_BD(a0, p0, wa7, 7)                                                                       \
+        "v_add_f32 %[p1], %[a0], %[a1]\n\t"                                                                                   \
+        "v_mov_b32_dpp %[p0], %[a1] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"                                                 \
+        "v_add_f32_dpp %[p0], %[a0], %[p0] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"                                          \
+        "s_nop 1\n\t"                                                                                                         \
+        "v_permlane16_swap_b32 %[p1], %[p0]\n\t"                                                                              \
+        "v_add_f32 %[a0], %[p1], %[p0]\n\t"                                                                                   \
+        SOLO_BLOCK2_ACT                                                                                                       \
+        "v_fma_f32 %[p0], %[a0], %[wc0], %[b2]\n\t"                                                                           \
+        "s_nop 0\n\t"                                                                                                         \
+        "v_mul_f32_dpp %[p1], %[a0], %[wc1] row_ror:1 row_mask:0xf bank_mask:0xf\n\t"                                         \
+        SOLO_BD(p0, a0, wc2, 2) SOLO_BD(p1, a0, wc3, 3) SOLO_BD(p0, a0, wc4, 4) SOLO_BD(p1, a0, wc5, 5)                       \
+        SOLO_BD(p0, a0, wc6, 6) SOLO_BD(p1, a0, wc7, 7)                                                                       \
+        "v_add_f32 %[a0], %[p0], %[p1]\n\t"                                                                                   \
+        "v_add_f32 %[a1], %[p0], %[p1]\n\t"                                                                                   \
+        "s_nop 1\n\t"                                                                                                         \
+        "v_permlane16_swap_b32 %[a0], %[a1]\n\t"                                                                              \
+        "v_add_f32 %[a0], %[a0], %[a1]\n\t"                                                                                   \
+        SOLO_BLOCK2_ACT                                                                                                       \
+        "v_fma_f32 %[p0], %[a0], %[wd0], %[b3]\n\t"                                                                           \
+        "v_mov_b32 %[p1], 0\n\t"                                                                                              \
+        SOLO_BD(p1, a0, we0, 8)                                                                                               \
+        SOLO_BD(p0, a0, wd1, 1) SOLO_BD(p1, a0, we1, 9) SOLO_BD(p0, a0, wd2, 2) SOLO_BD(p1, a0, we2, 10)                      \
+        SOLO_BD(p0, a0, wd3, 3) SOLO_BD(p1, a0, we3, 11) SOLO_BD(p0, a0, wd4, 4) SOLO_BD(p1, a0, we4, 12)                     \
+        SOLO_BD(p0, a0, wd5, 5) SOLO_BD(p1, a0, we5, 13) SOLO_BD(p0, a0, wd6, 6) SOLO_BD(p1, a0, we6, 14)                     \
+        SOLO_BD(p0, a0, wd7, 7) SOLO_BD(p1, a0, we7, 15)                                                                      \
+        "v_add_f32 %[a0], %[p0], %[p1]\n\t"                                                                                   \
+        "v_add_f32 %[a1], %[p0], %[p1]\n\t"                                                                                   \
+        "s_nop 1\n\t"                                                                                                         \
+        "v_permlane32_swap_b32 %[a0], %[a1]\n\t"               /* a0 = log_s, a1 = t, in every lane */                        \
+        "v_mul_f32 %[p0], 0xbfb8aa3b, %[a0]\n\t"                                                                              \
+        "v_exp_f32 %[p0], %[p0]\n\t"                                                                                          \
+        "v_sub_f32 %[p1], %[cur], %[a1]\n\t"                                                                                  \
+        "v_mul_f32 %[t0], %[p1], %[p0]\n\t"                                                                                   \
+        "v_mul_f32 %[t1], %[p1], %[p0]\n\t"                                                                                   \
+        LD_LINE                                                                                                               \
+        "s_nop 0\n\t"                                                                                                         \
+        "v_permlane16_swap_b32 %[t0], %[t1]\n\t"               /* every row: t0 = slot 0's new value, t1 = slot 1's */
+#define SOLO_BLOCK2_IN(w)                                                                                                     \
+        [c0] "v"(c0), [c1] "v"(c1), [i0] "v"(i0), [i1] "v"(i1), [sel] "v"(sel), [h1] "v"(h1v), [b1] "v"(w.b1), [b2] "v"(w.b2), [b3] "v"(w.b3[0]),          \
+        SOLO_BW8(wa, w.w1[0]), SOLO_BW8(wb, w.w1[1]), SOLO_BW8(wc, w.w2), SOLO_BW8(wd, w.w3[0]), SOLO_BW8(we, w.w3[1])
+// (c0, c1) condition, (i0, i1) are transformed into (t0, t1): inputs and outputs are separate operands, so a caller that keeps
+// its inputs (the proposal z' of a step) pays no copy.  FIRST: the log-det partial starts here (ld = -log_s); otherwise
+// ld -= log_s.  h1v: all ones in the h = 1 rows (v_bfi_b32 picks the row's slot, as `sel` picks the half's activation).
+template <bool FIRST>
+static __device__ __forceinline__ void solo_block2(const SoloNet<2> &w, unsigned sel, unsigned h1v, float c0, float c1, float i0, float i1,
+                                                   float &t0, float &t1, float &ld) {
+    float p0, p1, a0, a1, cur;
+    if constexpr (FIRST) {
+        asm(SOLO_BLOCK2("v_mul_f32 %[ld], -1.0, %[a0]\n\t")
+            : [t0] "=&v"(t0), [t1] "=&v"(t1), [ld] "=&v"(ld), [p0] "=&v"(p0), [p1] "=&v"(p1), [a0] "=&v"(a0), [a1] "=&v"(a1), [cur] "=&v"(cur)
+            : SOLO_BLOCK2_IN(w));
     } else {
-        float o0, o1;
-        solo_chain_1(o0, o1, w.b3[0], hin, w.w3[0]);
-        float ls, tt;
-        solo_nets(solo_join(o0 + o1), ls, tt);
-        trans[0] = (trans[0] - tt) * __expf(-ls);
-        return h1 ? 0.f : -ls;             // the same value in both rows: counted once
+        asm(SOLO_BLOCK2("v_sub_f32 %[ld], %[ld], %[a0]\n\t")
+            : [t0] "=&v"(t0), [t1] "=&v"(t1), [ld] "+v"(ld), [p0] "=&v"(p0), [p1] "=&v"(p1), [a0] "=&v"(a0), [a1] "=&v"(a1), [cur] "=&v"(cur)
+            : SOLO_BLOCK2_IN(w));
+    }
+}
+
+// One block of NormalizingFlow.inverse on the register-resident weights; the lane's log-det partial starts (FIRST) or continues in ld.
+template <int U, bool FIRST>
+static __device__ __forceinline__ void solo_coupling_inverse(const SoloNet<U> &w, unsigned sel, bool h1, const float (&cond)[U],
+                                                              float (&trans)[U], float &ld) {
+    if constexpr (U == 2) {
+        float t0, t1;
+        solo_block2<FIRST>(w, sel, h1 ? 0xffffffffu : 0u, cond[0], cond[1], trans[0], trans[1], t0, t1, ld);
+        trans[0] = t0;
+        trans[1] = t1;
+    } else {
+        const float v = solo_coupling_inverse1<U>(w, sel, h1, cond, trans);
+        ld = FIRST ? v : ld + v;
     }
 }
 // log-det of the walker from the lanes' partials: over the 16 positions of a row, then over the two K-halves
 static __device__ __forceinline__ float solo_logdet_total(float ld) { return solo_join(solo_row_sum(ld)); }
+// ld = solo_logdet_total(ld) and v = solo_row_sum(v) in one statement: the two four-stage ladders are independent, so each
+// stage of one is a wait state of the other (a stage's DPP read follows the write of its operand by two states: the other
+// ladder's add and one s_nop 0, where a ladder alone carries s_nop 1), and the join's second copy is the last stage written
+// twice.  Pairing order of both sums as solo_row_sum: v + ror8, + ror4, + ror2, + ror1.
+#define SOLO_LADDER(a, t) "v_add_f32_dpp %[" #a "], %[" #a "], %[" #a "] row_ror:" #t " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+static __device__ __forceinline__ void solo_logdet_total_and_row_sum(float &ld, float &v) {
+    float l2;
+    asm("s_nop 1\n\t"                      // (either input may be the result of the instruction in front of the statement)
+        SOLO_LADDER(ld, 8) SOLO_LADDER(v, 8) "s_nop 0\n\t"
+        SOLO_LADDER(ld, 4) SOLO_LADDER(v, 4) "s_nop 0\n\t"
+        SOLO_LADDER(ld, 2) SOLO_LADDER(v, 2) "s_nop 0\n\t"
+        "v_add_f32_dpp %[l2], %[ld], %[ld] row_ror:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        SOLO_LADDER(ld, 1) SOLO_LADDER(v, 1)
+        "s_nop 0\n\t"
+        "v_permlane16_swap_b32 %[ld], %[l2]\n\t"
+        "v_add_f32 %[ld], %[ld], %[l2]\n\t"
+        : [ld] "+v"(ld), [v] "+v"(v), [l2] "=&v"(l2));
+}
 
 // ---- x_dim 97..128 (U = 4): a lane's share of a block is 78 weights, 234 for the three blocks -- more than the register file
 // leaves beside the state.  They live in LDS instead, field-major ([block][field / 4][lane][4]: one conflict-free ds_read_b128
@@ -287,14 +422,19 @@ static __device__ __forceinline__ float solo_coupling_inverse4(const W &wsrc, un
     float hid = solo_activate(solo_join_rot(a0 + a1), sel);   // (h = 1 rows: rotated by 8, as the next chain reads it)
     wsrc.load8(wa, 32);
     solo_chain_1(a0, a1, bA.y, hid, wa);
-    const float hin = solo_activate(solo_join_rot(a0 + a1), sel);
+    constexpr bool FULLK = U == 2;   // the last layer over the whole K (solo_gather): its input un-rotated in every row
+    const float hin = solo_activate(FULLK ? solo_join(a0 + a1) : solo_join_rot(a0 + a1), sel);
     float ld = 0.f;
 #pragma unroll
     for (int k = 0; k < U / 2; ++k) {
         float o0, o1;
         wsrc.load8(wa, 40 + 16 * k); wsrc.load8(wb, 48 + 16 * k);
-        solo_chain_2out(o0, o1, k == 0 ? bA.z : bB.x, k == 0 ? bA.w : bB.y, hin, wa, wb);
-        solo_swap16(o0, o1);               // rows h = 0: both halves of output 2 k; rows h = 1: both halves of output 2 k + 1
+        if constexpr (FULLK) {
+            solo_chain_full(o0, o1, bA.z, hin, wa, wb);   // row h: output h, rotations 0..7 and 8..15
+        } else {
+            solo_chain_2out(o0, o1, k == 0 ? bA.z : bB.x, k == 0 ? bA.w : bB.y, hin, wa, wb);
+            solo_swap16(o0, o1);           // rows h = 0: both halves of output 2 k; rows h = 1: both halves of output 2 k + 1
+        }
         float ls, tt;
         solo_nets(o0 + o1, ls, tt);
         const float cur = h1 ? trans[2 * k + 1] : trans[2 * k];
