@@ -34,12 +34,6 @@ class HipCholesky(_HipFlow):
 
     _from_native_dev = _to_native_dev
 
-    def slice_steps(self, *args, **kwargs):
-        """the fused slice kernels exist for the NVP (nnest_slice_steps) and the spline flow (HipSpline.slice_steps) only: the
-        inherited method would hand this handle to the NVP's entry point.  The sampler's slice proposal runs this flow through
-        nnest_amd.slice_rounds (supports_fused_slice is False)."""
-        raise NotImplementedError("no fused slice kernel for the Cholesky flow (flow='choleksy'): use nnest_amd.slice_rounds")
-
     def layer_shapes(self):
         D = self.D
         return [('flow.flows.0.bias', (D,)), ('flow.flows.0.lower_entries', (D * (D - 1) // 2,)), ('flow.flows.0.unconstrained_diag', (D,))]

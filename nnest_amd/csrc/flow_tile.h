@@ -22,6 +22,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "slice_walk.h"
 
 namespace nnest {
 
@@ -813,13 +814,9 @@ __device__ __forceinline__ float noise_uniform(uint64_t seed, uint64_t walker, u
     return (float)(r.x >> 8) * 5.9604644775390625e-08f;
 }
 
-// the slice proposal's stepping-out budget of one update (nnest_slice_steps): B = 2 max_out expansions split at random (Neal 2003,
-// sec. 4.1), at most J = min(B, floor(v (B + 1))) to the left and B - J to the right, v = noise_uniform(seed, walker, 64 it + 63).
-// v is a 24-bit fraction m / 2^24, so J = (m (B + 1)) >> 24 exactly, in integers (a float32 product could round up to B + 1).
+// the slice proposal's stepping-out budget of one update (nnest_slice_steps): the split of slice_walk.h from the update's uniform 63
 __device__ __forceinline__ int slice_stepout_left(uint64_t seed, uint64_t walker, uint32_t it, int max_out) {
-    const uint64_t m = (uint64_t)(noise_uniform(seed, walker, 64u * it + 63u) * 16777216.0f);
-    const int B = 2 * max_out, J = (int)((m * (uint64_t)(B + 1)) >> 24);
-    return J < B ? J : B;
+    return slice_split_left(noise_uniform(seed, walker, 64u * it + 63u), max_out);
 }
 
 // ---- proposal stream of the persistent MH kernel -------------------------------------------------------

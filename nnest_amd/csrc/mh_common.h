@@ -73,6 +73,22 @@ struct MhArgs {
     int *sync_err;              // set to 1 if a bounded poll of `sync` ran out (a workgroup was not resident)
 };
 
+// the launch arguments of the fused slice kernels (nnest_slice_steps, nnest_spline_slice_steps; the rule: slice_walk.h).  The flow
+// goes beside them: FlowShape + packed weights (nnest_solo.hip), SplArgs (nnest_spline_slice.hip)
+struct SliceArgs {
+    float *z, *x;
+    double *logl;
+    double loglstar;
+    float width;
+    int steps, C, max_out, max_shrink;
+    LikeSpec like;
+    uint64_t seed, walker_offset;
+    const float *noise_dz;   // recorded directions [steps][C][D] (tests) or NULL
+    float *hist_x;           // [C][steps + 1][D] or NULL
+    float *x0;               // the tile forms: the chains' first x, for the usable-chain test behind the launch (mh_first_x_buffer), or NULL
+    int *n_call, *n_move, *n_eval;
+};
+
 // the usable-chain test of the 16-walker-tile forms behind their launch (nnest_kernels.hip)
 float *mh_first_x_buffer(size_t floats, hipStream_t st);
 hipError_t launch_mh_all_moved(const MhArgs &a, hipStream_t st);

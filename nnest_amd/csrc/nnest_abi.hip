@@ -380,12 +380,13 @@ int nnest_slice_steps(nnest_nvp_t *h, const nnest_like_t *like, float *z_dev, fl
     if (rc) return rc;
     LikeSpec lk;
     if ((rc = check_like(like, h->s.D, &lk))) return rc;
-    if (steps < 0 || max_stepout < 0 || max_stepout > (1 << 24) || max_shrink < 1 || max_shrink > 60 || !(width > 0.f))
+    if (!slice_params_ok(steps, max_stepout, max_shrink, width))
         return fail(NNEST_E_ARG, "steps=%d max_stepout=%d (0..2^24) max_shrink=%d (1..60) width=%g", steps, max_stepout, max_shrink, (double)width);
     if (!slice_form_eligible(h->s))
         return fail(NNEST_E_UNSUPPORTED, "slice proposal: hidden 16, 3 blocks, 1 layer, scale '' (the one-walker-per-wave layout), x_dim <= 128");
-    hipError_t e = launch_slice_solo(h->s, h->w, lk, z_dev, x_dev, logl_dev, loglstar, width, steps, C, max_stepout, max_shrink, seed,
-                                     walker_offset, noise_dz_dev, hist_x_dev, n_call_dev, n_move_dev, n_eval_dev, (hipStream_t)stream);
+    const SliceArgs a = {z_dev, x_dev, logl_dev, loglstar, width, steps, C, max_stepout, max_shrink, lk, seed, walker_offset, noise_dz_dev,
+                         hist_x_dev, nullptr, n_call_dev, n_move_dev, n_eval_dev};
+    hipError_t e = launch_slice_solo(h->s, h->w, a, (hipStream_t)stream);
     if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_slice_solo: %s", hipGetErrorString(e));
     return NNEST_OK;
 }

@@ -22,7 +22,8 @@ hipError_t launch_mh(const float *img, const FlowShape &s, const LikeSpec &like,
                      const float *noise_u, uint64_t seed, uint64_t walker_offset, float *hist_x, double *hist_logl,
                      int *n_accept, int *n_call, float *scale_out, const float *packed, unsigned long long *sync, int num_cu,
                      hipStream_t st);
-struct MhArgs;
+struct MhArgs;      // mh_common.h
+struct SliceArgs;   // mh_common.h
 bool quad_form_eligible(const MhArgs &a, int num_cu);        // nnest_quad.hip
 hipError_t launch_mh_quad(const MhArgs &a, int num_cu, hipStream_t st);  // nnest_quad.hip
 bool solo_form_eligible(const MhArgs &a, int num_cu);        // nnest_solo.hip
@@ -45,10 +46,7 @@ hipError_t launch_spline_mh_pair(const MhArgs &a, const SplArgs &q, bool dbg, hi
 hipError_t launch_spline_mh_team(const MhArgs &a, const SplArgs &q, bool dbg, hipStream_t st);   // nnest_spline_mh.hip
 int spline_mh_form(const SplineShape &sp, int C, int flags, int num_cu);   // spline_kernels.h
 int spline_slice_form(const SplineShape &sp, int C, int flags, int num_cu);   // nnest_spline_slice.hip
-hipError_t launch_spline_slice(const float *img, const SplineShape &sp, const LikeSpec &like, float *z, float *x, double *logl,
-                               double loglstar, float width, int steps, int C, int max_out, int max_shrink, int flags,
-                               const float *noise_dz, uint64_t seed, uint64_t walker_offset, float *hist_x, int *n_call, int *n_move,
-                               int *n_eval, int num_cu, hipStream_t st);   // nnest_spline_slice.hip
+hipError_t launch_spline_slice(const SplArgs &q, const SliceArgs &a, int flags, int num_cu, hipStream_t st);   // nnest_spline_slice.hip
 bool spline_shape_supported(const SplineShape &s);
 hipError_t launch_spline_pass(const float *img, const SplineShape &sp, int mode, const float *in, float *out, float *logdet,
                               double *logl, int *inbox, int N, const LikeSpec &like, int num_cu, hipStream_t st);
@@ -85,9 +83,7 @@ hipError_t launch_maf_loss_grad(const FlowShape &s, const float *imgf, const flo
 hipError_t launch_training_jitter(const double *samples, int N, int D, double *out, hipStream_t st);
 // slice proposal in latent space (nnest_solo.hip; build-defined: the reference has none)
 bool slice_form_eligible(const FlowShape &s);
-hipError_t launch_slice_solo(const FlowShape &s, const float *packed, const LikeSpec &like, float *z, float *x, double *logl, double loglstar,
-                             float width, int steps, int C, int max_out, int max_shrink, uint64_t seed, uint64_t walker_offset,
-                             const float *noise_dz, float *hist_x, int *n_call, int *n_move, int *n_eval, hipStream_t st);
+hipError_t launch_slice_solo(const FlowShape &s, const float *packed, const SliceArgs &a, hipStream_t st);
 hipError_t launch_slice_fill_noise(float *dz, int steps, int C, int D, uint64_t seed, uint64_t walker_offset, hipStream_t st);
 // ensemble sampler, emcee's stretch move in latent space (nnest_ensemble.hip)
 size_t ensemble_work_words(int C, int S);

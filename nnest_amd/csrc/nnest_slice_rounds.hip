@@ -1,11 +1,6 @@
 // nnest_slice_rounds.hip -- the SLICE proposal in latent space as a state machine on the device that advances in ROUNDS, with the
-// flow's inverse and the likelihood outside the kernels (include/nnest_hip.h nnest_slice_rounds_*).  BUILD-DEFINED, parity unpinned:
-// the reference proposes random-walk Metropolis moves only (nnest/sampler.py:310-316).  The definition is nnest_slice_steps's
-// (nnest_solo.hip slice_kernel_solo) and the round structure nnest_spline_slice.hip's slice_body: per update and walker a direction
-// eps (noise_normal4, stream DZ), uniforms u_k = noise_uniform(seed, walker, 64 it + k), the slice level log y = log|det|(z) + log u_1,
-// the bracket [-u_0, 1 - u_0] stepped out to the slice's ends within a budget of 2 max_stepout expansions, restarted with the budget
-// split at random between the sides by u_63 if it does not suffice (slice_stepout_left, Neal 2003 sec. 4.1), then at most max_shrink
-// shrinkage draws; inside(t) := the box holds, log|det| > log y and logL > L*.
+// flow's inverse and the likelihood outside the kernels (include/nnest_hip.h nnest_slice_rounds_*: the definition and the noise
+// streams, nnest_slice_steps's; slice_walk.h: the bracket rule of one update).  BUILD-DEFINED, parity unpinned.
 //
 // One round: the caller maps every walker's candidate z' through ANY flow's inverse (x', log|det|), rounds_screen_kernel tests the box
 // and the slice level and packs the x' rows that need a likelihood in ascending walker order, the caller evaluates the likelihood on
@@ -32,12 +27,8 @@ namespace nnest {
 struct SliceWalker {   // one walker's state machine
     double logl;       // logL of the current point
     float ld, ldc;     // log|det dx/dz| of the current point, of this round's candidate
-    float tl, tr, tc;  // bracket, this round's candidate t
     float logy;        // slice level
-    int it, phase, k;  // update (1-based), phase (0 / 1: stepping out to the left / right, k steps taken; 2: shrinkage, k draws taken)
-    int nl;            // < 0: the full step-out (at most 2 max_out expansions in all, k counting over both sides); else the split
-                       // step-out: at most nl steps left, 2 max_out - nl right
-    float t0;          // -u_0: the bracket's start
+    SliceWalk walk;    // update, phase and bracket (slice_walk.h); walk.tc: this round's candidate t
     int active;        // updates left (this round's candidate is live)
     int pre, slot;     // this round's screen: box and level passed; packed row (-1: none)
     int n_call, n_move, n_eval;
@@ -63,54 +54,39 @@ struct RoundArgs {
         for (int r__ = 0, d = 4 * q__; r__ < 4; ++r__, d = 4 * q__ + r__)          \
             if (d < (D))
 
-__device__ __forceinline__ float shrink_candidate(const RoundArgs &a, const SliceWalker &s, uint64_t walker) {
-    const float uk = noise_uniform(a.seed, walker, 64u * (uint32_t)s.it + 2u + (uint32_t)s.k);
-    return __builtin_fmaf(s.tr - s.tl, uk, s.tl);
-}
+// uniform k of the walker's current update
+struct RoundDraw {
+    uint64_t seed, walker;
+    const SliceWalk &walk;
+    __device__ __forceinline__ float operator()(int k) const { return noise_uniform(seed, walker, 64u * (uint32_t)walk.it + (uint32_t)k); }
+};
 
-// the next update: direction, u_0, u_1, level, bracket, first candidate
+// the next update: bracket and first candidate (slice_walk.h), direction, level
 __device__ __forceinline__ void begin_update(const RoundArgs &a, SliceWalker &s, int c, int lane) {
-    s.it += 1;
     const uint64_t walker = a.walker_offset + (uint64_t)c;
-    const int D = a.D;
+    const RoundDraw draw = {a.seed, walker, s.walk};
+    s.walk.begin(draw, a.max_out);
+    const int D = a.D, it = s.walk.it;
     float *e = a.e + (size_t)c * D;
     if (a.noise_dz) {
-        const float *src = a.noise_dz + ((size_t)(s.it - 1) * a.C + c) * D;
+        const float *src = a.noise_dz + ((size_t)(it - 1) * a.C + c) * D;
         FOR_LANE_DIMS(D, lane, d) e[d] = src[d];
     } else {
         for (int q = lane; 4 * q < D; q += 64) {
-            const f32x4 n = noise_normal4(a.seed, walker, (uint32_t)s.it, (uint32_t)q, NOISE_STREAM_DZ);
+            const f32x4 n = noise_normal4(a.seed, walker, (uint32_t)it, (uint32_t)q, NOISE_STREAM_DZ);
             const float v[4] = {n.x, n.y, n.z, n.w};
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (4 * q + r < D) e[4 * q + r] = v[r];
         }
     }
-    const float u0 = noise_uniform(a.seed, walker, 64u * (uint32_t)s.it + 0u), u1 = noise_uniform(a.seed, walker, 64u * (uint32_t)s.it + 1u);
-    s.logy = s.ld + __logf(u1);   // (u1 = 0: -inf, the whole feasible line is the slice)
-    s.t0 = -u0;
-    s.tl = s.t0;
-    s.tr = 1.0f - u0;
-    s.k = 0;
-    s.nl = -1;
-    s.phase = a.max_out > 0 ? 0 : 2;
-    s.tc = s.phase == 0 ? s.tl : shrink_candidate(a, s, walker);
-}
-
-// the full step-out took more than 2 max_out expansions: restart from [-u_0, 1 - u_0] with the budget split at random
-__device__ __forceinline__ void split_stepout(const RoundArgs &a, SliceWalker &s, uint64_t walker) {
-    s.tl = s.t0;
-    s.tr = 1.0f + s.t0;
-    s.k = 0;
-    s.nl = slice_stepout_left(a.seed, walker, (uint32_t)s.it, a.max_out);
-    s.phase = s.nl > 0 ? 0 : (s.nl < 2 * a.max_out ? 1 : 2);
-    s.tc = s.phase == 0 ? s.tl : s.phase == 1 ? s.tr : shrink_candidate(a, s, walker);
+    s.logy = s.ld + __logf(draw(1));   // (u1 = 0: -inf, the whole feasible line is the slice)
 }
 
 // z' = z + t * width * eps, one fused multiply-add per dim (slice_kernel_solo's candidate)
 __device__ __forceinline__ void propose(const RoundArgs &a, const SliceWalker &s, int c, int lane, float *z_cand) {
     const int D = a.D;
-    const float tw = s.tc * a.width;
+    const float tw = s.walk.tc * a.width;
     const float *z = a.z + (size_t)c * D, *e = a.e + (size_t)c * D;
     float *o = z_cand + (size_t)c * D;
     FOR_LANE_DIMS(D, lane, d) o[d] = __builtin_fmaf(e[d], tw, z[d]);
@@ -239,28 +215,9 @@ __global__ void __launch_bounds__(256) rounds_advance_kernel(RoundArgs a, const 
     const bool ins = pre && (lc > a.loglstar);
     s.n_eval += 1;
     s.n_call += pre ? 1 : 0;
-    bool done = false;
-    const uint64_t walker = a.walker_offset + (uint64_t)c;
-    if (s.phase == 0 && s.nl < 0) {            // full: while inside(t_l): t_l -= 1 (more than 2 max_out expansions: split)
-        if (ins) { s.tl -= 1.0f; s.k += 1; }
-        if (!ins) { s.phase = 1; s.tc = s.tr; }
-        else if (s.k <= 2 * a.max_out) s.tc = s.tl;
-        else split_stepout(a, s, walker);
-    } else if (s.phase == 1 && s.nl < 0) {     // full: the same to the right, k counting on
-        if (ins) { s.tr += 1.0f; s.k += 1; }
-        if (!ins) { s.phase = 2; s.k = 0; s.tc = shrink_candidate(a, s, walker); }
-        else if (s.k <= 2 * a.max_out) s.tc = s.tr;
-        else split_stepout(a, s, walker);
-    } else if (s.phase == 0) {     // split: for j < nl: if !inside(t_l) break; t_l -= 1
-        if (ins) { s.tl -= 1.0f; s.k += 1; }
-        if (ins && s.k < s.nl) s.tc = s.tl;
-        else if (s.nl < 2 * a.max_out) { s.phase = 1; s.k = 0; s.tc = s.tr; }
-        else { s.phase = 2; s.k = 0; s.tc = shrink_candidate(a, s, a.walker_offset + (uint64_t)c); }
-    } else if (s.phase == 1) {     // split: for j < 2 max_out - nl: the same to the right
-        if (ins) { s.tr += 1.0f; s.k += 1; }
-        if (ins && s.k < 2 * a.max_out - s.nl) s.tc = s.tr;
-        else { s.phase = 2; s.k = 0; s.tc = shrink_candidate(a, s, a.walker_offset + (uint64_t)c); }
-    } else if (ins) {              // shrinkage: the walker moves to the candidate (its z' and the packed x' row)
+    const int it = s.walk.it;
+    const bool done = s.walk.advance(ins, RoundDraw{a.seed, a.walker_offset + (uint64_t)c, s.walk}, a.max_out, a.max_shrink);
+    if (done && ins) {   // the walker moves to the candidate (its z' and the packed x' row)
         const float *xr = rows + (size_t)s.slot * D;
         FOR_LANE_DIMS(D, lane, d) {
             a.z[o + d] = z_cand[o + d];
@@ -269,17 +226,11 @@ __global__ void __launch_bounds__(256) rounds_advance_kernel(RoundArgs a, const 
         s.ld = s.ldc;
         s.logl = lc;
         s.n_move += 1;
-        if (a.move_ref && lane == 0) a.move_ref[(size_t)c * a.steps + s.it - 1] = a.base[0] + s.slot;
-        done = true;
-    } else {                       // the bracket's end on the candidate's side becomes the candidate
-        if (s.tc < 0.f) s.tl = s.tc; else s.tr = s.tc;
-        s.k += 1;
-        if (s.k < a.max_shrink) s.tc = shrink_candidate(a, s, a.walker_offset + (uint64_t)c);
-        else done = true;          // after max_shrink draws the walker stays
+        if (a.move_ref && lane == 0) a.move_ref[(size_t)c * a.steps + it - 1] = a.base[0] + s.slot;
     }
     if (done) {
-        store_history(a, s, c, lane, s.it);
-        if (s.it < a.steps) begin_update(a, s, c, lane);
+        store_history(a, s, c, lane, it);
+        if (it < a.steps) begin_update(a, s, c, lane);
         else s.active = 0;
     }
     if (s.active) propose(a, s, c, lane, z_cand);
@@ -377,7 +328,7 @@ int nnest_slice_rounds_begin(nnest_slice_rounds_t *h, const float *z_dev, const 
                              float *z_cand_dev, void *stream) {
     if (!h) return rfail(NNEST_E_ARG, "NULL handle");
     if (!z_dev || !x_dev || !ld_dev || !logl_dev || !z_cand_dev) return rfail(NNEST_E_ARG, "NULL device buffer");
-    if (max_stepout < 0 || max_stepout > (1 << 24) || max_shrink < 1 || max_shrink > 60 || !(width > 0.f))
+    if (!slice_params_ok(h->steps, max_stepout, max_shrink, width))
         return rfail(NNEST_E_ARG, "max_stepout=%d (0..2^24) max_shrink=%d (1..60) width=%g", max_stepout, max_shrink, (double)width);
     RoundArgs &a = h->a;
     a.loglstar = loglstar; a.width = width; a.max_out = max_stepout; a.max_shrink = max_shrink;

@@ -559,35 +559,14 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
 // logL(x(z)) > L*}.  Per step and walker:
 //   eps ~ N(0, I_D) (noise_normal4, stream DZ);  candidates z(t) = z + t * width * eps,  t in R
 //   log y = log|det|(z) + log u_1;   inside(t) := x(z(t)) in the box  and  log|det|(z(t)) > log y  and  logL(x(z(t))) > L*
-//   bracket [t_l, t_r] = [-u_0, 1 - u_0];  stepping out (Neal 2003, sec. 4.1) within a budget of B = 2 max_out expansions: while
-//   inside(t_l): t_l -= 1, then while inside(t_r): t_r += 1 -- the full step-out, whose expansions are the grid points inside the slice
-//   between its two outside ends, a count every point of the bracket finds alike.  If it takes more than B expansions, the bracket
-//   restarts at [-u_0, 1 - u_0] and the budget is split at random: at most J = min(B, floor(u_63 (B + 1))) steps to the left, then at
-//   most B - J to the right (slice_stepout_left).  Either way the bracket is found from the new point with the probability it had
-//   from the old, so the update is reversible (separate caps per side were not, once they bound).  max_out = 0: no stepping out.
-//   shrinkage: t = t_l + (t_r - t_l) u_k (k = 2, 3, ...); inside(t) -> the walker moves there; else the bracket's end on t's side
-//   becomes t; after `max_shrink` draws the walker stays.
+//   the bracket [t_l, t_r] of t, stepped out within a budget of 2 max_out expansions and then shrunk by at most `max_shrink` draws:
+//   slice_walk.h has the rule (the kernel below restates it as nested loops)
 // Every evaluation is one "eval" of the hot path (coupling-stack inverse + log-det + box + likelihood); n_call counts, as the
 // Metropolis kernel does, the candidates whose likelihood decided (those that passed the box and the slice level).
 // One walker per wave (the solo layout): the data-dependent loops of a walker are uniform over its wave, walkers do not wait for
 // each other, and no step crosses a workgroup -- any population, no resident-grid requirement.  u_k = noise_uniform(seed, walker,
 // 64 step + k): exact in float32, so the CPU checker of the tests restates them word for word; the normals are exported for
 // it (nnest_slice_fill_noise), like nnest_mh_fill_noise exports the Metropolis kernel's.
-struct SliceArgs {
-    FlowShape s;
-    const float *packed;
-    float *z, *x;
-    double *logl;
-    double loglstar;
-    float width;
-    int steps, C, max_out, max_shrink;
-    LikeSpec like;
-    uint64_t seed, walker_offset;
-    const float *noise_dz;   // recorded directions [steps][C][D] (tests) or NULL
-    float *hist_x;           // [C][steps + 1][D] or NULL
-    int *n_call, *n_move, *n_eval;
-};
-
 template <int U>   // this lane's 2U normals of (walker, step): dims 2U pos + 2u + c, the quads of noise_normal4
 static __device__ __forceinline__ void slice_normals(uint64_t seed, uint64_t walker, uint32_t step, int pos, int D, float (&e)[2][U]) {
     const int d0 = 2 * U * pos;
@@ -609,18 +588,18 @@ static __device__ __forceinline__ void slice_normals(uint64_t seed, uint64_t wal
 }
 
 template <int U, int LK>
-__global__ void __launch_bounds__(256) slice_kernel_solo(SliceArgs a) {
+__global__ void __launch_bounds__(256) slice_kernel_solo(SliceArgs a, FlowShape s, const float *packed) {
     extern __shared__ __attribute__((aligned(16))) float wlds[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int D = a.s.D, S = a.steps, C = a.C;
+    const int D = s.D, S = a.steps, C = a.C;
     constexpr bool LDSW = solo_lds_weights<U, 4>();
     {
         if constexpr (!LDSW) {
-            const int n = a.s.nets_params();
-            for (int i = threadIdx.x; i < n; i += blockDim.x) wlds[i] = a.packed[i];
+            const int n = s.nets_params();
+            for (int i = threadIdx.x; i < n; i += blockDim.x) wlds[i] = packed[i];
         } else if (wave < 3) {
             SoloNet<U> nb;
-            solo_gather<U>(nb, a.packed + (size_t)(wave * 2 + (lane >= 32 ? 1 : 0)) * a.s.net_params, D, (wave + 1) & 1, wave & 1, lane);
+            solo_gather<U>(nb, packed + (size_t)(wave * 2 + (lane >= 32 ? 1 : 0)) * s.net_params, D, (wave + 1) & 1, wave & 1, lane);
             solo4_store<U>(wlds, wave, nb, lane);
         }
     }
@@ -636,7 +615,7 @@ __global__ void __launch_bounds__(256) slice_kernel_solo(SliceArgs a) {
     if constexpr (!LDSW) {
 #pragma unroll
         for (int b = 0; b < 3; ++b)
-            solo_gather<U>(net[b], wlds + (size_t)(b * 2 + (translate_half ? 1 : 0)) * a.s.net_params, D, (b + 1) & 1, b & 1, lane);
+            solo_gather<U>(net[b], wlds + (size_t)(b * 2 + (translate_half ? 1 : 0)) * s.net_params, D, (b + 1) & 1, b & 1, lane);
     }
     const unsigned sel = translate_half ? 0xffffffffu : 0u;
     const bool h1 = (lane & 16) != 0;
@@ -715,6 +694,7 @@ __global__ void __launch_bounds__(256) slice_kernel_solo(SliceArgs a) {
             n_call += pre ? 1 : 0;
             return pre && (lc > loglstar);
         };
+        // (slice_walk.h's rule; its state machine cost registers here: DESIGN.md 3.6)
         float tl = -u0, tr = 1.0f - u0;
         if (a.max_out > 0) {
             const int B = 2 * a.max_out;
@@ -787,11 +767,11 @@ __global__ void slice_fill_noise_kernel(float *__restrict__ dz, int steps, int C
 }
 
 template <int U, int LK>
-static hipError_t launch_slice_k(const SliceArgs &a, hipStream_t st) {
-    const size_t lds = solo_lds_weights<U, 4>() ? (size_t)3 * SOLO4_NF * 64 * sizeof(float) : (size_t)a.s.nets_params() * sizeof(float);
+static hipError_t launch_slice_k(const FlowShape &s, const float *packed, const SliceArgs &a, hipStream_t st) {
+    const size_t lds = solo_lds_weights<U, 4>() ? (size_t)3 * SOLO4_NF * 64 * sizeof(float) : (size_t)s.nets_params() * sizeof(float);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(slice_kernel_solo<U, LK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((slice_kernel_solo<U, LK>), dim3((a.C + 3) / 4), dim3(256), lds, st, a);
+    hipLaunchKernelGGL((slice_kernel_solo<U, LK>), dim3((a.C + 3) / 4), dim3(256), lds, st, a, s, packed);
     return hipGetLastError();
 }
 
@@ -799,22 +779,15 @@ bool slice_form_eligible(const FlowShape &s) {
     return s.kind == FLOW_KIND_NVP && s.H == 16 && s.B == 3 && s.L == 1 && s.scale_mode == 0 && s.NT >= 1 && s.NT <= 4;
 }
 
-hipError_t launch_slice_solo(const FlowShape &s, const float *packed, const LikeSpec &like, float *z, float *x, double *logl, double loglstar,
-                             float width, int steps, int C, int max_out, int max_shrink, uint64_t seed, uint64_t walker_offset,
-                             const float *noise_dz, float *hist_x, int *n_call, int *n_move, int *n_eval, hipStream_t st) {
-    if (C <= 0) return hipSuccess;
+hipError_t launch_slice_solo(const FlowShape &s, const float *packed, const SliceArgs &a, hipStream_t st) {
+    if (a.C <= 0) return hipSuccess;
     if (!slice_form_eligible(s)) return hipErrorInvalidConfiguration;
-    SliceArgs a;
-    memset(&a, 0, sizeof(a));
-    a.s = s; a.packed = packed; a.z = z; a.x = x; a.logl = logl; a.loglstar = loglstar; a.width = width; a.steps = steps; a.C = C;
-    a.max_out = max_out; a.max_shrink = max_shrink; a.like = like; a.seed = seed; a.walker_offset = walker_offset;
-    a.noise_dz = noise_dz; a.hist_x = hist_x; a.n_call = n_call; a.n_move = n_move; a.n_eval = n_eval;
-    const bool rosen = like.id == NNEST_LIKE_ROSENBROCK;
+    const bool rosen = a.like.id == NNEST_LIKE_ROSENBROCK;
     switch (s.NT) {
-        case 1: return rosen ? launch_slice_k<1, NNEST_LIKE_ROSENBROCK>(a, st) : launch_slice_k<1, -1>(a, st);
-        case 2: return rosen ? launch_slice_k<2, NNEST_LIKE_ROSENBROCK>(a, st) : launch_slice_k<2, -1>(a, st);
-        case 3: return rosen ? launch_slice_k<3, NNEST_LIKE_ROSENBROCK>(a, st) : launch_slice_k<3, -1>(a, st);
-        case 4: return rosen ? launch_slice_k<4, NNEST_LIKE_ROSENBROCK>(a, st) : launch_slice_k<4, -1>(a, st);
+        case 1: return rosen ? launch_slice_k<1, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : launch_slice_k<1, -1>(s, packed, a, st);
+        case 2: return rosen ? launch_slice_k<2, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : launch_slice_k<2, -1>(s, packed, a, st);
+        case 3: return rosen ? launch_slice_k<3, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : launch_slice_k<3, -1>(s, packed, a, st);
+        case 4: return rosen ? launch_slice_k<4, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : launch_slice_k<4, -1>(s, packed, a, st);
     }
     return hipErrorInvalidConfiguration;
 }

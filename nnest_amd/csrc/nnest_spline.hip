@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "nnest_internal.h"
+#include "mh_common.h"
 
 using namespace nnest;
 
@@ -365,14 +366,14 @@ int nnest_spline_slice_steps(nnest_spline_t *h, const nnest_like_t *like, float 
     if (rc) return rc;
     LikeSpec lk;
     if ((rc = scheck_like(like, h->s.D, &lk))) return rc;
-    if (steps < 0 || max_stepout < 0 || max_stepout > (1 << 24) || max_shrink < 1 || max_shrink > 60 || !(width > 0.f))
+    if (!slice_params_ok(steps, max_stepout, max_shrink, width))
         return spline_fail(NNEST_E_ARG, "steps=%d max_stepout=%d (0..2^24) max_shrink=%d (1..60) width=%g", steps, max_stepout, max_shrink, (double)width);
     if (flags & ~15) return spline_fail(NNEST_E_ARG, "flags=0x%x: bits 0..3 only (NNEST_SPLINE_SLICE_FORM)", flags);
     if (C > 0 && spline_slice_form(h->s, C, flags, h->num_cu) < 0)
         return spline_fail(NNEST_E_UNSUPPORTED, "spline slice proposal: form %d pinned, x_dim=%d (the pair form needs x_dim > 32)", (flags & 15) - 1, h->s.D);
-    hipError_t e = launch_spline_slice(h->img, h->s, lk, z_dev, x_dev, logl_dev, loglstar, width, steps, C, max_stepout, max_shrink, flags,
-                                       noise_dz_dev, seed, walker_offset, hist_x_dev, n_call_dev, n_move_dev, n_eval_dev, h->num_cu,
-                                       (hipStream_t)stream);
+    const SliceArgs a = {z_dev, x_dev, logl_dev, loglstar, width, steps, C, max_stepout, max_shrink, lk, seed, walker_offset, noise_dz_dev,
+                         hist_x_dev, nullptr, n_call_dev, n_move_dev, n_eval_dev};
+    hipError_t e = launch_spline_slice(SplArgs{h->img, h->s}, a, flags, h->num_cu, (hipStream_t)stream);
     if (e == hipErrorInvalidConfiguration) return spline_fail(NNEST_E_UNSUPPORTED, "spline slice proposal: x_dim=%d hidden_dim=%d not instantiated", h->s.D, h->s.H);
     if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_slice: %s", hipGetErrorString(e));
     return NNEST_OK;

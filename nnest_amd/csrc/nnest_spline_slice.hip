@@ -1,11 +1,6 @@
 // nnest_spline_slice.hip -- the SLICE proposal in latent space with the neural-spline flow (include/nnest_hip.h
-// nnest_spline_slice_steps).  BUILD-DEFINED, parity unpinned: the reference proposes random-walk Metropolis moves only
-// (nnest/sampler.py:310-316).  The definition is the one slice_kernel_solo implements for the NVP (nnest_solo.hip): per update
-// and walker a direction eps (noise_normal4, stream DZ), uniforms u_k = noise_uniform(seed, walker, 64 it + k), the slice level
-// log y = log|det|(z) + log u_1, the bracket [-u_0, 1 - u_0] stepped out to the slice's ends within a budget of 2 max_stepout
-// expansions, restarted with the budget split at random between the sides by u_63 if it does not suffice (slice_stepout_left,
-// Neal 2003 sec. 4.1), then at most max_shrink shrinkage draws; inside(t) := the box holds, log|det| > log y and logL > L*.  Only the flow differs: the spline's inverse
-// (spline_inverse.h) replaces the coupling stack.
+// nnest_spline_slice_steps: the definition and the noise streams; slice_walk.h: the bracket rule of one update).  BUILD-DEFINED, parity
+// unpinned.  Only the flow differs from nnest_slice_steps: the spline's inverse (spline_inverse.h) replaces the coupling stack.
 //
 // Layout: the tiles of the spline proposal kernels -- 16 walkers per wave (WAVE), four waves per 16 walkers (TEAM), or four waves
 // per 8 walkers held twice (PAIR) -- with the state in the parity-class tiles of flow_tile.h.  Slice walkers do not stay in step:
@@ -28,20 +23,6 @@
 namespace nnest {
 
 #include "spline_inverse.h"
-
-struct SplSliceArgs {
-    float *z, *x;
-    double *logl;
-    double loglstar;
-    float width;
-    int steps, C, max_out, max_shrink;
-    LikeSpec like;
-    uint64_t seed, walker_offset;
-    const float *noise_dz;   // recorded directions [steps][C][D] (tests) or NULL
-    float *hist_x;           // [C][steps + 1][D] or NULL
-    float *x0;               // the chains' first x, for the usable-chain test behind the launch (mh_first_x_buffer), or NULL
-    int *n_call, *n_move, *n_eval;
-};
 
 // this lane's part of the direction of (walker, update it): dims 32 tau + 8 g + j are the quads 8 tau + 2 g and 8 tau + 2 g + 1 of
 // noise_normal4 (what nnest_slice_fill_noise exports); padded dims get 0
@@ -68,7 +49,7 @@ __device__ __forceinline__ void slice_direction(uint64_t seed, uint64_t walker, 
 // The round loop.  GW = walkers per tile: 16, or 8 held twice (lanes w and w ^ 8 carry walker w & 7, as in mh_body); counts and
 // stores take the low copy.  `writer`: the wave that stores (every wave of a TEAM / PAIR workgroup computes the same state).
 template <int NT, class Inv, int GW = 16>
-__device__ __forceinline__ void slice_body(const SplSliceArgs &a, int D, int tile, int lane, const Inv &inv, bool writer) {
+__device__ __forceinline__ void slice_body(const SliceArgs &a, int D, int tile, int lane, const Inv &inv, bool writer) {
     static_assert(GW == 16 || GW == 8, "walkers per tile");
     const int w = lane & 15;
     const int row = tile * GW + (w & (GW - 1));
@@ -92,44 +73,22 @@ __device__ __forceinline__ void slice_body(const SplSliceArgs &a, int D, int til
     if (a.x0) store_tile<NT>(a.x0, row, store, D, lane, x);
     if (a.hist_x) store_tile<NT>(a.hist_x, (long)row * (S + 1), store, D, lane, x);
 
-    int it = 0, phase = 0, k = 0;   // phase 0 / 1: stepping out to the left / right (k steps taken); 2: shrinkage (k draws taken)
-    int nl = -1;                    // < 0: the full step-out (at most 2 max_out expansions in all, k counts them over both sides);
-                                    // else the split step-out: at most nl steps left, 2 max_out - nl right
-    float t0 = 0.f;                 // -u_0: the bracket's start
-    float tl = 0.f, tr = 0.f, logy = 0.f, tc = 0.f;   // bracket, slice level, the candidate of the next round
+    SliceWalk sw = {};               // the bracket rule's state (slice_walk.h); sw.tc: the candidate of the next round
+    float logy = 0.f;                // slice level
     int n_call = 0, n_move = 0, n_eval = 0;
     bool active = ok && S > 0;
-    auto shrink_candidate = [&]() {
-        const float uk = noise_uniform(seed, walker, 64u * (uint32_t)it + 2u + (uint32_t)k);
-        return __builtin_fmaf(tr - tl, uk, tl);
-    };
+    auto draw = [&](int k) { return noise_uniform(seed, walker, 64u * (uint32_t)sw.it + (uint32_t)k); };
     auto begin_update = [&]() {   // (divergent: no cross-lane work)
-        it += 1;
-        if (a.noise_dz) load_tile<NT>(a.noise_dz, (long)(it - 1) * C + row, true, D, lane, e);
-        else slice_direction<NT>(seed, walker, (uint32_t)it, D, lane, e);
-        const float u0 = noise_uniform(seed, walker, 64u * (uint32_t)it + 0u), u1 = noise_uniform(seed, walker, 64u * (uint32_t)it + 1u);
-        logy = ld + __logf(u1);   // (u1 = 0: -inf, the whole feasible line is the slice)
-        t0 = -u0;
-        tl = t0;
-        tr = 1.0f - u0;
-        k = 0;
-        nl = -1;
-        phase = max_out > 0 ? 0 : 2;
-        tc = phase == 0 ? tl : shrink_candidate();
-    };
-    auto split_stepout = [&]() {   // the full step-out took more than 2 max_out expansions: restart with the budget split at random
-        tl = t0;
-        tr = 1.0f + t0;
-        k = 0;
-        nl = slice_stepout_left(seed, walker, (uint32_t)it, max_out);
-        phase = nl > 0 ? 0 : (nl < 2 * max_out ? 1 : 2);
-        tc = phase == 0 ? tl : phase == 1 ? tr : shrink_candidate();
+        sw.begin(draw, max_out);
+        if (a.noise_dz) load_tile<NT>(a.noise_dz, (long)(sw.it - 1) * C + row, true, D, lane, e);
+        else slice_direction<NT>(seed, walker, (uint32_t)sw.it, D, lane, e);
+        logy = ld + __logf(draw(1));   // (u1 = 0: -inf, the whole feasible line is the slice)
     };
     if (active) begin_update();
 
     while (__ballot(active) != 0ull) {
         // one evaluation per walker: candidate z + tc * width * eps (an idle walker: tc = 0, its own point)
-        const float tw = tc * width;
+        const float tw = sw.tc * width;
         f32x4 xc[2][NT];
 #pragma unroll
         for (int c = 0; c < 2; ++c)
@@ -143,7 +102,7 @@ __device__ __forceinline__ void slice_body(const SplSliceArgs &a, int D, int til
         const bool pre = inb && (ldc > logy);
         const double lc = loglike_tile<NT>(like, D, lane, xc);
         const bool ins = pre && (lc > loglstar);
-        const bool mv = active && phase == 2 && ins;
+        const bool mv = active && sw.phase == 2 && ins;
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -160,39 +119,11 @@ __device__ __forceinline__ void slice_body(const SplSliceArgs &a, int D, int til
         if (active) {
             n_eval += 1;
             n_call += pre ? 1 : 0;
-            bool done = false;
-            if (phase == 0 && nl < 0) {          // full: while inside(t_l): t_l -= 1 (more than 2 max_out expansions: split)
-                if (ins) { tl -= 1.0f; k += 1; }
-                if (!ins) { phase = 1; tc = tr; }
-                else if (k <= 2 * max_out) tc = tl;
-                else split_stepout();
-            } else if (phase == 1 && nl < 0) {   // full: the same to the right, k counting on
-                if (ins) { tr += 1.0f; k += 1; }
-                if (!ins) { phase = 2; k = 0; tc = shrink_candidate(); }
-                else if (k <= 2 * max_out) tc = tr;
-                else split_stepout();
-            } else if (phase == 0) {             // split: for j < nl: if !inside(t_l) break; t_l -= 1
-                if (ins) { tl -= 1.0f; k += 1; }
-                if (ins && k < nl) tc = tl;
-                else if (nl < 2 * max_out) { phase = 1; k = 0; tc = tr; }
-                else { phase = 2; k = 0; tc = shrink_candidate(); }
-            } else if (phase == 1) {             // split: for j < 2 max_out - nl: the same to the right
-                if (ins) { tr += 1.0f; k += 1; }
-                if (ins && k < 2 * max_out - nl) tc = tr;
-                else { phase = 2; k = 0; tc = shrink_candidate(); }
-            } else if (ins) {            // shrinkage: the walker moves to the candidate
-                n_move += 1;
-                done = true;
-            } else {                     // the bracket's end on the candidate's side becomes the candidate
-                if (tc < 0.f) tl = tc; else tr = tc;
-                k += 1;
-                if (k < max_shrink) tc = shrink_candidate();
-                else done = true;        // after max_shrink draws the walker stays
-            }
-            if (done) {
-                if (a.hist_x) store_tile<NT>(a.hist_x, (long)row * (S + 1) + it, store, D, lane, x);
-                if (it < S) begin_update();
-                else { active = false; tc = 0.f; }
+            if (sw.advance(ins, draw, max_out, max_shrink)) {
+                n_move += ins ? 1 : 0;
+                if (a.hist_x) store_tile<NT>(a.hist_x, (long)row * (S + 1) + sw.it, store, D, lane, x);
+                if (sw.it < S) begin_update();
+                else { active = false; sw.tc = 0.f; }
             }
         }
     }
@@ -209,7 +140,7 @@ __device__ __forceinline__ void slice_body(const SplSliceArgs &a, int D, int til
 
 // WAVE: one wave per 16 walkers, the waves of a workgroup independent
 template <int NT, int NH>
-__global__ void __launch_bounds__(256) spline_slice_kernel_wave(SplSliceArgs a, SplArgs q) {
+__global__ void __launch_bounds__(256) spline_slice_kernel_wave(SliceArgs a, SplArgs q) {
     extern __shared__ __attribute__((aligned(16))) float lds_buf[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     const int tile = blockIdx.x * wpb + wave;
@@ -220,7 +151,7 @@ __global__ void __launch_bounds__(256) spline_slice_kernel_wave(SplSliceArgs a, 
 
 // TEAM: four waves per 16 walkers, the spline evaluations of the inverse divided between them (spline_mh_kernel_team's layout)
 template <int NT, int NH>
-__global__ void __launch_bounds__(256) spline_slice_kernel_team(SplSliceArgs a, SplArgs q) {
+__global__ void __launch_bounds__(256) spline_slice_kernel_team(SliceArgs a, SplArgs q) {
     extern __shared__ __attribute__((aligned(16))) float lds_buf[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     float *bufs = lds_buf;                                                                     // 4 x 16 x (D+1)
@@ -232,7 +163,7 @@ __global__ void __launch_bounds__(256) spline_slice_kernel_team(SplSliceArgs a, 
 
 // PAIR: four waves per 8 walkers held in both halves of the matrix-core columns (spline_mh_kernel_pair's layout); x_dim > 32
 template <int NT, int NH>
-__global__ void __launch_bounds__(256) spline_slice_kernel_pair(SplSliceArgs a, SplArgs q) {
+__global__ void __launch_bounds__(256) spline_slice_kernel_pair(SliceArgs a, SplArgs q) {
     extern __shared__ __attribute__((aligned(16))) float lds_buf[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     float *bufs = lds_buf;                                                                     // 4 x 16 x (D+1)
@@ -260,7 +191,7 @@ int spline_slice_form(const SplineShape &sp, int C, int flags, int num_cu) {
 }
 
 template <int NT, int NH>
-static hipError_t launch_slice_t(const SplSliceArgs &a, const SplArgs &q, int form, int num_cu, hipStream_t st) {
+static hipError_t launch_slice_t(const SliceArgs &a, const SplArgs &q, int form, int num_cu, hipStream_t st) {
     const int D = q.sp.D, ntiles = (a.C + 15) / 16;
     if (form == NNEST_SPLINE_MH_WAVE) {
         int wpb = 1;   // (pick_geometry's rule: the waves of a workgroup share a CU)
@@ -287,20 +218,14 @@ static hipError_t launch_slice_t(const SplSliceArgs &a, const SplArgs &q, int fo
     return hipErrorInvalidConfiguration;
 }
 
-hipError_t launch_spline_slice(const float *img, const SplineShape &sp, const LikeSpec &like, float *z, float *x, double *logl,
-                               double loglstar, float width, int steps, int C, int max_out, int max_shrink, int flags,
-                               const float *noise_dz, uint64_t seed, uint64_t walker_offset, float *hist_x, int *n_call, int *n_move,
-                               int *n_eval, int num_cu, hipStream_t st) {
+hipError_t launch_spline_slice(const SplArgs &q, const SliceArgs &args, int flags, int num_cu, hipStream_t st) {
+    const SplineShape &sp = q.sp;
+    const int C = args.C;
     if (C <= 0) return hipSuccess;
     const int form = spline_slice_form(sp, C, flags, num_cu);
     if (form < 0 || !spline_shape_supported(sp)) return hipErrorInvalidConfiguration;
-    SplSliceArgs a;
-    memset(&a, 0, sizeof(a));
-    a.z = z; a.x = x; a.logl = logl; a.loglstar = loglstar; a.width = width; a.steps = steps; a.C = C;
-    a.max_out = max_out; a.max_shrink = max_shrink; a.like = like; a.seed = seed; a.walker_offset = walker_offset;
-    a.noise_dz = noise_dz; a.hist_x = hist_x; a.n_call = n_call; a.n_move = n_move; a.n_eval = n_eval;
-    if (x && n_move && !(a.x0 = mh_first_x_buffer((size_t)C * sp.D, st))) return hipErrorOutOfMemory;
-    const SplArgs q = {img, sp};
+    SliceArgs a = args;
+    if (a.x && a.n_move && !(a.x0 = mh_first_x_buffer((size_t)C * sp.D, st))) return hipErrorOutOfMemory;
     hipError_t e;
     switch (sp.NTh * 10 + sp.NH) {
         case 11: e = launch_slice_t<1, 1>(a, q, form, num_cu, st); break;
@@ -314,7 +239,7 @@ hipError_t launch_spline_slice(const float *img, const SplineShape &sp, const Li
     if (e != hipSuccess) return e;
     // every coordinate of the chain's last x differs from its first (nested.py:432): the follow-up kernel of the tile forms
     MhArgs m{};
-    m.x0 = a.x0; m.x = x; m.n_accept = n_move; m.C = C; m.s.D = sp.D;
+    m.x0 = a.x0; m.x = a.x; m.n_accept = a.n_move; m.C = C; m.s.D = sp.D;
     return launch_mh_all_moved(m, st);
 }
 

@@ -73,7 +73,7 @@ class _HipFlow(object):
     def _bind(self, family, **named):
         """self._sym: the entry points `<family>_<name>` that the library declares for this family (nnest_chol has neither
         inverse_loglike nor vjp: those names stay out), and the ones whose symbol does not follow the pattern, by name
-        (mh='nnest_mh_constrained_steps')"""
+        (mh='nnest_mh_constrained_steps', slice='nnest_slice_steps'); a name left out is an entry point the family does not have"""
         family_syms = [(n, '%s_%s' % (family, n)) for n in self._FAMILY_ENTRIES]
         self._sym = {n: getattr(self._lib, sym) for n, sym in family_syms if sym in _lib.SIGNATURES}
         self._sym.update((n, getattr(self._lib, sym)) for n, sym in named.items())
@@ -268,14 +268,21 @@ class _HipFlow(object):
         return _MhResult(x=x, n_accept_word=n_acc, n_call=n_call, scale=scale_out, hist_x=hx, hist_logl=hl, sync=sync)
 
     def slice_steps(self, like_id, like_scale, z, logl, loglstar, width, steps, max_stepout=8, max_shrink=32, noise=None, seed=0,
-                    walker_offset=0, history=False, like_params=None):
-        """SLICE proposal in latent space (nnest_slice_steps; BUILD-DEFINED: the reference has none, nnest/sampler.py:310-316 is
-        random-walk Metropolis): `steps` slice-sampling updates (stepping out + shrinkage along a random direction) of every walker
-        under the hard constraint logL > loglstar, the target the reference's Metropolis step leaves invariant.  z [C,D] float32 and
-        logl [C] float64 are updated in place.  noise = dz [steps,C,D] replays recorded directions.  Returns x, n_call (candidates
-        whose likelihood decided), n_move, moved (nested.py:432), n_eval (flow evaluations), hist_x."""
+                    walker_offset=0, history=False, like_params=None, form=None):
+        """SLICE proposal in latent space (the family's `slice` entry point: nnest_slice_steps, nnest_spline_slice_steps; BUILD-DEFINED:
+        the reference has none, nnest/sampler.py:310-316 is random-walk Metropolis): `steps` slice-sampling updates (stepping out +
+        shrinkage along a random direction) of every walker under the hard constraint logL > loglstar, the target the reference's
+        Metropolis step leaves invariant.  z [C,D] float32 and logl [C] float64 are updated in place.  noise = dz [steps,C,D] replays
+        recorded directions (fill_slice_noise exports the in-kernel ones).  form: the kernel form, where the family has several
+        (HipSpline: None = by population | 'wave' | 'team' | 'pair').  Returns x, n_call (candidates whose likelihood decided),
+        n_move, moved (nested.py:432), n_eval (flow evaluations), hist_x.  A family without a fused slice kernel raises
+        NotImplementedError (its handle must not reach another family's): the slice proposal runs it through nnest_amd.slice_rounds."""
+        fn = self._sym.get('slice')
+        if fn is None:
+            raise NotImplementedError('no fused slice kernel for %s: use nnest_amd.slice_rounds' % type(self).__name__)
         assert z.is_cuda and z.dtype == torch.float32 and z.is_contiguous()
         assert logl.is_cuda and logl.dtype == torch.float64 and logl.is_contiguous()
+        form_args = self._slice_form_args(form)
         C, dev = z.shape[0], self.device
         x = torch.empty_like(z)
         n_call = torch.empty(C, dtype=torch.int32, device=dev)
@@ -288,17 +295,22 @@ class _HipFlow(object):
             assert dz.shape[0] == steps * C
         with torch.cuda.device(dev):
             lk = _lib.like_spec(like_id, like_scale, like_params)
-            _lib.check(self._lib.nnest_slice_steps(self._h, ctypes.byref(lk), _lib.ptr(z), _lib.ptr(x), _lib.ptr(logl), float(loglstar),
-                                                   float(width), int(steps), C, int(max_stepout), int(max_shrink), _lib.ptr(dz),
-                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset), _lib.ptr(hx), _lib.ptr(n_call),
-                                                   _lib.ptr(n_move), _lib.ptr(n_eval), _lib.current_stream(dev)))
-        return dict(x=x, n_call=n_call, n_move=n_move & (_lib.MH_ALL_MOVED - 1), moved=(n_move & _lib.MH_ALL_MOVED) != 0, n_eval=n_eval,
-                    hist_x=hx)
+            _lib.check(fn(self._h, ctypes.byref(lk), _lib.ptr(z), _lib.ptr(x), _lib.ptr(logl), float(loglstar), float(width), int(steps), C,
+                          int(max_stepout), int(max_shrink), *form_args, _lib.ptr(dz), int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset),
+                          _lib.ptr(hx), _lib.ptr(n_call), _lib.ptr(n_move), _lib.ptr(n_eval), _lib.current_stream(dev)))
+        n_move, moved = split_move_word(n_move)
+        return dict(x=x, n_call=n_call, n_move=n_move, moved=moved, n_eval=n_eval, hist_x=hx)
+
+    def _slice_form_args(self, form):
+        """what the family's slice entry point takes between max_shrink and noise_dz_dev: nothing, for a kernel with one form"""
+        if form is not None:
+            raise ValueError('form=%r: %s has one slice kernel form' % (form, type(self).__name__))
+        return ()
 
     def supports_fused_slice(self, C):
         """whether `slice_steps` (a fused slice kernel) takes this flow for C walkers; where it does not, the slice proposal runs
         through nnest_amd.slice_rounds (any flow)"""
-        return False
+        return 'slice' in self._sym
 
     def fill_slice_noise(self, steps, C, seed=0, walker_offset=0):
         """the directions nnest_slice_steps draws (Philox normals), exported for the checker: dz [steps, C, D]"""
@@ -353,15 +365,19 @@ class _HipFlow(object):
         return dz, u
 
 
+def split_move_word(word):
+    """the proposal kernels' n_accept / n_move word -> (count, moved): bit NNEST_MH_ALL_MOVED says that every coordinate of the
+    chain's last x differs from its first (the reference's usable-chain test, nested.py:432)"""
+    return word & (_lib.MH_ALL_MOVED - 1), (word & _lib.MH_ALL_MOVED) != 0
+
+
 class _MhResult(dict):
     """what mh_steps returns; 'n_accept' (the count) and 'moved' (the reference's usable-chain test, nested.py:432) are split off
     the kernel's word (NNEST_MH_ALL_MOVED) when first asked for"""
 
     def __missing__(self, key):
         if key in ('n_accept', 'moved'):
-            w = dict.__getitem__(self, 'n_accept_word')
-            self['moved'] = (w & _lib.MH_ALL_MOVED) != 0
-            self['n_accept'] = w & (_lib.MH_ALL_MOVED - 1)
+            self['n_accept'], self['moved'] = split_move_word(dict.__getitem__(self, 'n_accept_word'))
             return dict.__getitem__(self, key)
         raise KeyError(key)
 
@@ -539,7 +555,7 @@ class HipNVP(_PaddedVectors, _HipFlow):
             raise ValueError("scale=%r: expected '', 'translate' or 'constant' (networks.py:330-332)" % (scale,))
         self.scale = scale
         self._lib = _lib.load()
-        self._bind('nnest_nvp', mh='nnest_mh_constrained_steps')
+        self._bind('nnest_nvp', mh='nnest_mh_constrained_steps', slice='nnest_slice_steps')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (_PaddedVectors)
         with torch.cuda.device(self.device):
@@ -552,7 +568,7 @@ class HipNVP(_PaddedVectors, _HipFlow):
 
     def supports_fused_slice(self, C):
         """nnest_slice_steps runs the reference's default coupling shape only (hidden 16, 3 blocks, 1 layer, scale '')"""
-        return self._Hn == 16 and self.B == 3 and self.L == 1 and self.scale == ''
+        return super().supports_fused_slice(C) and self._Hn == 16 and self.B == 3 and self.L == 1 and self.scale == ''
 
     def ensemble_max_walkers(self, like_id):
         """the population nnest_ensemble_steps takes for this flow and likelihood (every workgroup resident); 0 if its shape is not

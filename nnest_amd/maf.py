@@ -33,7 +33,8 @@ class HipMAF(HipNVP):
         self.scale = ''
         self._lib = _lib.load()
         L = self._lib
-        self._bind('nnest_nvp', mh='nnest_mh_constrained_steps')   # the handle is an nnest_nvp_t: HipNVP's entry points
+        self._bind('nnest_nvp', mh='nnest_mh_constrained_steps')   # the handle is an nnest_nvp_t: HipNVP's entry points (no `slice`:
+        # there is no fused slice kernel for the MAF, the slice proposal runs through nnest_amd.slice_rounds)
         self._h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(L.nnest_maf_create(self.D, self.H, self.B, self.L, ctypes.byref(self._h)))
@@ -43,10 +44,6 @@ class HipMAF(HipNVP):
         self.prior = torch.distributions.MultivariateNormal(torch.zeros(self.D, device=self.device),
                                                             torch.eye(self.D, device=self.device))
         self.load_packed(self.default_init(seed))
-
-    def supports_fused_slice(self, C):
-        """no fused slice kernel for the MAF: the slice proposal runs through nnest_amd.slice_rounds"""
-        return False
 
     def _train_epoch(self, rows, epoch, n_train, batch, lr, weight_decay):
         """the epoch's rows in minibatch order, jitter applied: one gather and one draw per epoch, and every minibatch of the epoch

@@ -275,25 +275,33 @@ class Sampler(object):
         p = self._user_prior
         return p is not None and not self._transform_prior and bool(getattr(p, 'is_unit_box', lambda: False)())
 
-    def _slice_rounds(self, z, logl, loglstar, step_size, mcmc_steps, walker_offset, seed, history=False, init_derived=None):
-        """the slice proposal through nnest_amd.slice_rounds: the device likelihood when the kernels know it, else the host
-        protocol (self.loglike on the rows whose likelihood decides, so total_calls grows by exactly sum n_call; the prior in place
-        of the box unless it is the unit box).  Initial bracket: twice the Metropolis step, as the fused slice kernels."""
-        from .slice_rounds import slice_rounds
+    def _slice_batch(self, z, logl, loglstar, step_size, mcmc_steps, walker_offset, seed, history=False, init_derived=None, rounds=False):
+        """One batch of the slice proposal from (z, logl), both updated in place: the fused kernel where the flow has one for this
+        population and the kernels know the likelihood (netG.slice_steps), else -- or with rounds=True, for a caller that needs
+        hist_z / hist_logl -- nnest_amd.slice_rounds: the device likelihood when the kernels know it, else the host protocol
+        (self.loglike on the rows whose likelihood decides, so it counts exactly sum n_call calls itself; the prior in place of the
+        box unless it is the unit box).  Initial bracket: twice the Metropolis step.  Books total_calls / total_accepted /
+        total_rejected; returns (res, ncall).  One small device-to-host copy for the counts."""
         netG = self.trainer.netG
+        C = z.shape[0]
         kw = dict(seed=self._next_seed() if seed is None else seed, walker_offset=walker_offset, history=history)
-        args = (netG, z, logl, float(loglstar), 2.0 * float(step_size), int(mcmc_steps))
-        if self._fused_like_id is not None:
-            res = slice_rounds(*args, like_id=self._fused_like_id, like_scale=self._linear_scale, like_params=self._fused_like_params, **kw)
-            ncall = int(res['n_call'].sum().item())
-            self.total_calls += ncall
-        else:
+        args = (z, logl, float(loglstar), 2.0 * float(step_size), int(mcmc_steps))
+        fused_slice = getattr(netG, 'supports_fused_slice', None)
+        if self._fused_like_id is None:
+            from .slice_rounds import slice_rounds
             prior = None if self._unit_box_prior() else (lambda x: self.prior(x) > -1e30)
-            res = slice_rounds(*args, loglike=self.loglike, prior=prior, num_derived=self.num_derived, init_derived=init_derived, **kw)
-            ncall = int(res['n_call'].sum().item())
-        nmove = int(res['n_move'].sum().item())
+            res = slice_rounds(netG, *args, loglike=self.loglike, prior=prior, num_derived=self.num_derived, init_derived=init_derived, **kw)
+        elif rounds or (fused_slice is not None and not fused_slice(C)):
+            from .slice_rounds import slice_rounds
+            res = slice_rounds(netG, *args, like_id=self._fused_like_id, like_scale=self._linear_scale, like_params=self._fused_like_params, **kw)
+        else:
+            res = netG.slice_steps(self._fused_like_id, self._linear_scale, *args, like_params=self._fused_like_params, **kw)
+        counts = torch.stack([res['n_call'].sum(), res['n_move'].sum()]).cpu()
+        ncall, nmove = int(counts[0]), int(counts[1])
+        if self._fused_like_id is not None:
+            self.total_calls += ncall
         self.total_accepted += nmove
-        self.total_rejected += z.shape[0] * int(mcmc_steps) - nmove
+        self.total_rejected += C * int(mcmc_steps) - nmove
         return res, ncall
 
     def _mcmc_sample_slice(self, mcmc_steps, step_size, init_samples, init_loglikes, init_derived, loglstar, walker_offset, seed):
@@ -310,8 +318,8 @@ class Sampler(object):
             ncall0 = init_samples.shape[0]
         z, _ = netG.forward(init_samples)
         logl = torch.as_tensor(np.asarray(init_loglikes, dtype=np.float64)).to(z.device).contiguous()
-        res, ncall = self._slice_rounds(z, logl, loglstar, step_size, mcmc_steps, walker_offset, seed, history=True,
-                                        init_derived=init_derived)
+        res, ncall = self._slice_batch(z, logl, loglstar, step_size, mcmc_steps, walker_offset, seed, history=True,
+                                       init_derived=init_derived, rounds=True)
         C = z.shape[0]
         derived = res['hist_derived'] if res['hist_derived'] is not None else np.empty((C, int(mcmc_steps) + 1, 0))
         return (res['hist_x'].cpu().numpy(), res['hist_z'].cpu().numpy(), derived, res['hist_logl'].cpu().numpy(), float(step_size),
@@ -410,22 +418,9 @@ class Sampler(object):
                 raise NotImplementedError("mcmc_proposal='slice' samples under the hard constraint logL > loglstar only")
             z, _ = netG.forward(init_samples)
             logl = torch.as_tensor(np.asarray(init_loglikes, dtype=np.float64), device=z.device).contiguous()
-            fused_slice = getattr(netG, 'supports_fused_slice', None)
-            if fused_slice is not None and not fused_slice(C):   # no fused slice kernel for this flow: the round driver
-                res, ncall = self._slice_rounds(z, logl, loglstar, step_size, mcmc_steps, walker_offset, seed, history=self.chain_stats)
-                self._chain_hist = res['hist_x'] if self.chain_stats else None
-                ends = torch.cat([res['x'].double(), logl[:, None], res['moved'][:, None].double()], dim=1)
-                return ends, float(step_size), ncall
-            res = netG.slice_steps(self._fused_like_id, self._linear_scale, z, logl, float(loglstar), 2.0 * float(step_size),
-                                   int(mcmc_steps), seed=self._next_seed() if seed is None else seed, walker_offset=walker_offset,
-                                   like_params=self._fused_like_params, history=self.chain_stats)
+            res, ncall = self._slice_batch(z, logl, loglstar, step_size, mcmc_steps, walker_offset, seed, history=self.chain_stats)
             self._chain_hist = res['hist_x'] if self.chain_stats else None
             ends = torch.cat([res['x'].double(), logl[:, None], res['moved'][:, None].double()], dim=1)
-            counts = torch.stack([res['n_call'].sum(), res['n_move'].sum()]).cpu()
-            ncall, nmove = int(counts[0]), int(counts[1])
-            self.total_calls += ncall
-            self.total_accepted += nmove
-            self.total_rejected += C * int(mcmc_steps) - nmove
             return ends, float(step_size), ncall
         res, z0, z, logl = self._fused_launch(mcmc_steps, step_size, dynamic, init_samples, init_loglikes, loglstar,
                                               walker_offset, seed, form)

@@ -166,5 +166,6 @@ def slice_rounds(flow, z, logl, loglstar, width, steps, loglike=None, like_id=No
             cur[sel] = every[ref[sel, it]]
             hist_derived[:, it + 1] = cur
         derived = cur
-    return dict(x=x, n_call=n_call, n_move=n_move & (_lib.MH_ALL_MOVED - 1), moved=(n_move & _lib.MH_ALL_MOVED) != 0, n_eval=n_eval,
-                hist_x=hx, hist_z=hz, hist_logl=hl, derived=derived, hist_derived=hist_derived, rounds=rounds)
+    n_move, moved = _flow.split_move_word(n_move)
+    return dict(x=x, n_call=n_call, n_move=n_move, moved=moved, n_eval=n_eval, hist_x=hx, hist_z=hz, hist_logl=hl, derived=derived,
+                hist_derived=hist_derived, rounds=rounds)

@@ -32,7 +32,7 @@ class HipSpline(_PaddedVectors, _HipFlow):
         self.nl = self.D - self.nu
         self._lib = _lib.load()
         L = self._lib
-        self._bind('nnest_spline', mh='nnest_spline_mh_constrained_steps')
+        self._bind('nnest_spline', mh='nnest_spline_mh_constrained_steps', slice='nnest_spline_slice_steps')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (flow._PaddedVectors: zero-padded, exact)
         with torch.cuda.device(self.device):
@@ -70,9 +70,17 @@ class HipSpline(_PaddedVectors, _HipFlow):
     SPLINE_SLICE_FORMS = {None: -1, 'wave': 0, 'team': 1, 'pair': 2}
 
     def _slice_flags(self, form):
+        """the flags word of nnest_spline_slice_steps / nnest_spline_slice_form_for"""
         if form not in self.SPLINE_SLICE_FORMS:
             raise ValueError("form=%r: None (the library chooses), 'wave', 'team' or 'pair'" % (form,))
         return (self.SPLINE_SLICE_FORMS[form] + 1) & 15   # NNEST_SPLINE_SLICE_FORM(f); 0 = NNEST_SPLINE_SLICE_AUTO
+
+    def _slice_form_args(self, form):
+        return (self._slice_flags(form),)
+
+    # the spline flow's slice proposal: the shared method on this family's entry point (`slice` in _bind above) with the flags word of
+    # _slice_form_args -- form: None (by population) | 'wave' | 'team' | 'pair'.  Named here so that the class says it has one
+    slice_steps = _HipFlow.slice_steps
 
     def slice_form_for(self, C, form=None):
         """the form of the slice kernel `slice_steps` runs for C walkers (nnest_spline_slice_form_for): 'pair', 'team' or 'wave' as
@@ -81,35 +89,6 @@ class HipSpline(_PaddedVectors, _HipFlow):
 
     def supports_fused_slice(self, C):
         return self.slice_form_for(C) is not None
-
-    def slice_steps(self, like_id, like_scale, z, logl, loglstar, width, steps, max_stepout=8, max_shrink=32, noise=None, seed=0,
-                    walker_offset=0, history=False, like_params=None, form=None):
-        """SLICE proposal in latent space with the spline flow (nnest_spline_slice_steps; BUILD-DEFINED, the reference has none): the
-        definition, streams and return dict of _HipFlow.slice_steps -- x, n_call, n_move, moved (nested.py:432), n_eval, hist_x --
-        with the spline's inverse.  z [C,D] float32 and logl [C] float64 are updated in place; noise = dz [steps,C,D] replays
-        recorded directions (fill_slice_noise exports the in-kernel ones).  form: None (by population) | 'wave' | 'team' | 'pair'."""
-        assert z.is_cuda and z.dtype == torch.float32 and z.is_contiguous()
-        assert logl.is_cuda and logl.dtype == torch.float64 and logl.is_contiguous()
-        flags = self._slice_flags(form)
-        C, dev = z.shape[0], self.device
-        x = torch.empty_like(z)
-        n_call = torch.empty(C, dtype=torch.int32, device=dev)
-        n_move = torch.empty(C, dtype=torch.int32, device=dev)
-        n_eval = torch.empty(C, dtype=torch.int32, device=dev)
-        hx = torch.empty(C, steps + 1, self.D, dtype=torch.float32, device=dev) if history else None
-        dz = None
-        if noise is not None:
-            dz = _as_dev_f32(noise.reshape(-1, self.D), dev)
-            assert dz.shape[0] == steps * C
-        with torch.cuda.device(dev):
-            lk = _lib.like_spec(like_id, like_scale, like_params)
-            _lib.check(self._lib.nnest_spline_slice_steps(self._h, ctypes.byref(lk), _lib.ptr(z), _lib.ptr(x), _lib.ptr(logl),
-                                                          float(loglstar), float(width), int(steps), C, int(max_stepout), int(max_shrink),
-                                                          flags, _lib.ptr(dz), int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset),
-                                                          _lib.ptr(hx), _lib.ptr(n_call), _lib.ptr(n_move), _lib.ptr(n_eval),
-                                                          _lib.current_stream(dev)))
-        return dict(x=x, n_call=n_call, n_move=n_move & (_lib.MH_ALL_MOVED - 1), moved=(n_move & _lib.MH_ALL_MOVED) != 0, n_eval=n_eval,
-                    hist_x=hx)
 
     def train_form_for(self, batch):
         """'rows' (one row of the minibatch per workgroup, nnest_spline_rows.hip) or 'tiles' (nnest_spline_train.hip): what a minibatch

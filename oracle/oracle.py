@@ -389,6 +389,73 @@ def slice_stepout_split(v, max_stepout):
     return J, B - J
 
 
+def slice_bracket(inside, u, max_stepout, max_shrink):
+    """the bracket rule of ONE slice update along a line, as loops (the independent statement of nnest_amd/csrc/slice_walk.h's state
+    machine): inside(t) -> bool evaluates the candidate z + t * width * eps; u[k] are the update's uniforms (float32; 0: the bracket's
+    position, 2 + k: shrinkage draw k, 63: the split).  Stepping out from [-u_0, 1 - u_0] goes to the slice's ends, left then right,
+    if that takes at most B = 2 max_stepout expansions; otherwise it restarts with B split at random (slice_stepout_split); then at
+    most max_shrink shrinkage draws.  All of t in float32.  Returns what it evaluated and decided: candidates (in order), n_left,
+    n_right (expansions of the bracket that counts), split, moved (the last candidate was inside: the walker goes there) and the
+    final bracket tl, tr."""
+    f32 = np.float32
+    cand = []
+
+    def ins(t):
+        cand.append(f32(t))
+        return bool(inside(f32(t)))
+
+    u0 = f32(u[0])
+    t0 = f32(-u0)
+    tl, tr = t0, f32(f32(1.0) - u0)
+    n_left = n_right = 0
+    split = False
+    B = 2 * int(max_stepout)
+    if B:   # the full step-out, at most B expansions in all
+        n = 0
+        while n <= B and ins(tl):
+            tl, n = f32(tl - f32(1.0)), n + 1
+        n_left = n
+        while n <= B and ins(tr):
+            tr, n = f32(tr + f32(1.0)), n + 1
+        n_right = n - n_left
+        if n > B:   # more than B: restart with the budget split at random
+            split = True
+            tl, tr = t0, f32(f32(1.0) + t0)
+            nl, nr = slice_stepout_split(u[63], max_stepout)
+            n_left = n_right = 0
+            for _ in range(nl):
+                if not ins(tl):
+                    break
+                tl = f32(tl - f32(1.0))
+                n_left += 1
+            for _ in range(nr):
+                if not ins(tr):
+                    break
+                tr = f32(tr + f32(1.0))
+                n_right += 1
+    moved = False
+    for k in range(int(max_shrink)):
+        t = f32(np.float64(f32(tr - tl)) * np.float64(f32(u[2 + k])) + np.float64(tl))   # fmaf(tr - tl, uk, tl)
+        if ins(t):
+            moved = True
+            break
+        if t < 0:
+            tl = t
+        else:
+            tr = t
+    return dict(candidates=cand, n_left=n_left, n_right=n_right, split=split, moved=moved, tl=tl, tr=tr)
+
+
+class _SliceUniforms(object):
+    """u[k] of (seed, walker, update it), drawn when asked for"""
+
+    def __init__(self, seed, walker, it):
+        self.key = (seed, walker, 64 * it)
+
+    def __getitem__(self, k):
+        return slice_uniform(self.key[0], self.key[1], self.key[2] + k)
+
+
 def slice_sample(flow, like, like_scale, z0, logl0, loglstar, width, dz, seed, walker_offset=0, max_stepout=8, max_shrink=32,
                  margins=None):
     """[BUILD-DEFINED, parity unpinned: the reference proposes random-walk Metropolis moves only, nnest/sampler.py:310-316]
@@ -412,12 +479,14 @@ def slice_sample(flow, like, like_scale, z0, logl0, loglstar, width, dz, seed, w
         zc, xc, ldc, lc = z[c].copy(), x[c].copy(), np.float32(ld[c]), float(logl[c])
         for it in range(1, S + 1):
             e = dz[it - 1, c].astype(np.float32)
-            u0, u1 = slice_uniform(seed, walker_offset + c, 64 * it), slice_uniform(seed, walker_offset + c, 64 * it + 1)
+            u = _SliceUniforms(seed, walker_offset + c, it)
             with np.errstate(divide='ignore'):
-                logy = np.float32(ldc + np.log(u1, dtype=np.float32))
+                logy = np.float32(ldc + np.log(u[1], dtype=np.float32))
             mg = [np.inf]
+            last = None
 
             def inside(t):
+                nonlocal last
                 tw = np.float32(np.float32(t) * w32)
                 zp = (zc.astype(np.float64) + e.astype(np.float64) * np.float64(tw)).astype(np.float32)   # one fused multiply-add per dim
                 xp, ldp = flow.inverse(zp[None])
@@ -429,46 +498,14 @@ def slice_sample(flow, like, like_scale, z0, logl0, loglstar, width, dz, seed, w
                 n_call[c] += 1 if pre else 0
                 mg[0] = min(mg[0], float(np.min(np.abs(np.abs(xp.astype(np.float64)) - 1.0))), abs(float(ldp) - float(logy)),
                             abs(lp - loglstar) / (1.0 + abs(loglstar)))
-                return (pre and lp > loglstar), zp, xp, ldp, lp
+                last = (zp, xp, ldp, lp)
+                return pre and lp > loglstar
 
-            t0 = np.float32(-u0)
-            tl, tr = t0, np.float32(np.float32(1.0) - u0)
-            B = 2 * int(max_stepout)
-            if B:   # the full step-out, at most B expansions in all
-                n = 0
-                while n <= B and inside(tl)[0]:
-                    tl, n = np.float32(tl - np.float32(1.0)), n + 1
-                n_left[c, it - 1] = n
-                while n <= B and inside(tr)[0]:
-                    tr, n = np.float32(tr + np.float32(1.0)), n + 1
-                n_right[c, it - 1] = n - n_left[c, it - 1]
-                if n > B:   # more than B: restart with the budget split at random
-                    split[c, it - 1] = True
-                    tl, tr = t0, np.float32(np.float32(1.0) + t0)
-                    nl, nr = slice_stepout_split(slice_uniform(seed, walker_offset + c, 64 * it + 63), max_stepout)
-                    n_left[c, it - 1] = n_right[c, it - 1] = 0
-                    for _ in range(nl):
-                        if not inside(tl)[0]:
-                            break
-                        tl = np.float32(tl - np.float32(1.0))
-                        n_left[c, it - 1] += 1
-                    for _ in range(nr):
-                        if not inside(tr)[0]:
-                            break
-                        tr = np.float32(tr + np.float32(1.0))
-                        n_right[c, it - 1] += 1
-            for k in range(max_shrink):
-                uk = slice_uniform(seed, walker_offset + c, 64 * it + 2 + k)
-                t = np.float32(np.float64(np.float32(tr - tl)) * np.float64(uk) + np.float64(tl))   # fmaf(tr - tl, uk, tl)
-                ok, zp, xp, ldp, lp = inside(t)
-                if ok:
-                    zc, xc, ldc, lc = zp, xp, ldp, lp
-                    n_move[c] += 1
-                    break
-                if t < 0:
-                    tl = t
-                else:
-                    tr = t
+            br = slice_bracket(inside, u, max_stepout, max_shrink)
+            n_left[c, it - 1], n_right[c, it - 1], split[c, it - 1] = br['n_left'], br['n_right'], br['split']
+            if br['moved']:   # to the last candidate evaluated
+                zc, xc, ldc, lc = last
+                n_move[c] += 1
             hx[c, it] = xc
             if margins is not None:
                 margins[it - 1, c] = mg[0]
