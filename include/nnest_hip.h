@@ -322,6 +322,26 @@ int nnest_ensemble_rounds_accept(const int *work_dev, int C, int steps, int D, i
                                  const float *hi_dev, float *z_cur_dev, float *x_cur_dev, double *lp_cur_dev, float *hist_z_dev,
                                  float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *acc_rows_dev, int constrained,
                                  double loglstar, void *stream);
+
+/* The stretch move in X SPACE: the run above with f = identity and ld = 0, so the walkers are x_k and
+ *   lp(x) = safe_loglike(T(x)) + prior (constrained = 1: -inf if logL < loglstar, else prior),
+ * T the identity (t_std_dev = t_mean_dev = NULL) or x * t_std + t_mean, the prior the box on T(x) or none.  The split table, the
+ * uniforms, zz, the partner, lnpdiff and the accept rule are the ones above on the same Philox streams, so the run is the one
+ * the round entries compute with an identity map for the flow, and is a function of (seed, step) only.  It is the emcee run
+ * EnsembleSampler.bootstrap starts from (nnest/ensemble.py:111-147).  (Added within ABI 15.)
+ * nnest_ensemble_x_max_walkers: the resident population of nnest_ensemble_x_steps for x_dim D and this likelihood id, by the
+ *   formula of nnest_ensemble_max_walkers applied to the x-space kernel (which has no LDS and few registers: 24 walkers per CU,
+ *   the SGPR term); -1 for D outside 1..128, an unknown id or no device.
+ * nnest_ensemble_x_steps: `steps` steps in one launch, one walker per wave, D <= 128 (NNEST_E_UNSUPPORTED beyond) and a known
+ *   likelihood id.  x_in_dev [C,D] (read only; not x_out_dev), lp_in_dev [C] or NULL; x_out_dev [C,D], lp_out_dev [C] the last
+ *   state, tx_out_dev [C,D] or NULL its T(x); hist_x_dev [C, steps, D], hist_lp_dev [C, steps] the state after every step
+ *   (required: the hand-off channel); n_accept_dev [C] or NULL; work_dev as above.  The argument checks, the residency refusal
+ *   (NNEST_E_UNSUPPORTED) and the bounded hand-off wait are those of nnest_ensemble_steps. */
+int nnest_ensemble_x_max_walkers(int D, int like_id);
+int nnest_ensemble_x_steps(const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev, const float *hi_dev,
+                           const float *x_in_dev, const double *lp_in_dev, float *x_out_dev, float *tx_out_dev, double *lp_out_dev,
+                           float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *work_dev, int C, int D, int steps, uint64_t step0,
+                           uint64_t seed, int constrained, double loglstar, void *stream);
 /* size of sync_dev in 8-byte words for a launch of `steps` steps */
 int nnest_mh_sync_words(int steps);
 /* number of adaptation groups nnest_mh_constrained_steps uses for C walkers (size of scale_out_dev) */
@@ -510,6 +530,16 @@ int nnest_spline_train(nnest_spline_t *spl, const float *xtrain_dev, int n_train
  *   advance -> finish.  nlags: a multiple of 256 up to 2048. */
 enum { NNEST_CHAIN_STATS_ALL_LAGS = 1, NNEST_CHAIN_STATS_NO_ESS = 2, NNEST_CHAIN_STATS_RHAT_AT_MEAN = 4 };
 int nnest_chain_stats_work_words(int C, int T, int D);
+/* emcee's normalised autocorrelation function of walkers x[C, T, D] (emcee 3 autocorr.integrated_time with has_walkers; read in
+ * place through the strides, as above): f_dev [T, D] float64, f(s, d) = SUM_k acf_k(s) / acf_k(0) over the walkers -- the caller
+ * divides by C -- with acf_k(s) = sum_{t < T - s} (x_kt - m_k)(x_k,t+s - m_k), m_k the walker's OWN mean over T, not divided by
+ * T - s.  A direct float64 sum over every lag 0 .. T - 1.  tau = 2 cumsum(f / C) - 1 at Sokal's window is the caller's
+ * (nnest_amd.evaluation.integrated_autocorr_time).  This is NOT the estimator of nnest_chain_stats (global mean, divided by the
+ * standard deviation, global stop).  work_dev: float64 scratch of nnest_chain_autocorr_work_words(C, T, D) words (-1: bad
+ * shape).  (Added within ABI 15.) */
+int nnest_chain_autocorr_work_words(int C, int T, int D);
+int nnest_chain_autocorr(const float *x_dev, int C, int T, int D, long long chain_stride, long long step_stride, double *work_dev,
+                         double *f_dev, void *stream);
 int nnest_chain_stats(const float *x_dev, int C, int T, int D, long long chain_stride, long long step_stride, const double *affine_dev,
                       const double *mean_dev, const double *std_dev, int flags, double *work_dev, double *p_dev, double *out_dev,
                       void *stream);

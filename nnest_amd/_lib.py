@@ -158,12 +158,16 @@ SIGNATURES = {
     'nnest_ensemble_fill_noise': [_vp, _vp, _i, _i, _u64, _u64, _vp],
     'nnest_ensemble_max_walkers': [_vp, _i],
     'nnest_ensemble_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _u64, _u64, _i, _d, _vp],
+    'nnest_ensemble_x_max_walkers': [_i, _i],
+    'nnest_ensemble_x_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _u64, _u64, _i, _d, _vp],
     'nnest_ensemble_rounds_propose': [_vp, _i, _i, _i, _i, _i, _u64, _u64, _vp, _vp, _vp],
     'nnest_ensemble_rounds_accept': [_vp, _i, _i, _i, _i, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _i, _d, _vp],
     'nnest_host_prior_consume': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  ctypes.c_longlong, _d, ctypes.c_longlong, ctypes.c_longlong, _d, _d, _i],
     'nnest_chain_stats_work_words': [_i, _i, _i],
+    'nnest_chain_autocorr_work_words': [_i, _i, _i],
+    'nnest_chain_autocorr': [_vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp],
     'nnest_chain_stats': [_vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     'nnest_chain_stats_chains': [_vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp],
     'nnest_chain_stats_prepare': [_vp, _i, _i, _i, _vp, _vp, _vp, _vp],

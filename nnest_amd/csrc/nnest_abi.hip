@@ -450,6 +450,54 @@ int nnest_ensemble_steps(nnest_nvp_t *h, const nnest_like_t *like, const float *
     return NNEST_OK;
 }
 
+static int ensemble_x_like(int D, int like_id) {
+    if (D < 1) return fail(NNEST_E_ARG, "ensemble_x: x_dim=%d", D);
+    if (D > 128) return fail(NNEST_E_UNSUPPORTED, "ensemble_x: x_dim=%d > 128 (the one-walker-per-wave layout)", D);
+    if (like_id < 0 || like_id >= NNEST_LIKE_COUNT) return fail(NNEST_E_ARG, "unknown likelihood id %d", like_id);
+    return NNEST_OK;
+}
+
+static int current_num_cu(int *num_cu) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(num_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    return NNEST_OK;
+}
+
+int nnest_ensemble_x_max_walkers(int D, int like_id) {
+    int n = 0, num_cu = 0;
+    if (ensemble_x_like(D, like_id) || current_num_cu(&num_cu)) return -1;
+    if (ensemble_x_max_walkers(D, like_id, num_cu, &n) != hipSuccess) return -1;
+    return n;
+}
+
+int nnest_ensemble_x_steps(const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev, const float *hi_dev,
+                           const float *x_in_dev, const double *lp_in_dev, float *x_out_dev, float *tx_out_dev, double *lp_out_dev,
+                           float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *work_dev, int C, int D, int steps, uint64_t step0,
+                           uint64_t seed, int constrained, double loglstar, void *stream) {
+    if (!like) return fail(NNEST_E_ARG, "like is NULL");
+    int rc = ensemble_x_like(D, like->id);
+    if (rc) return rc;
+    if ((rc = ensemble_sizes(C, steps))) return rc;
+    LikeSpec lk;
+    if ((rc = check_like(like, D, &lk))) return rc;
+    lk.scale = 1.0f;
+    if (!x_in_dev || !x_out_dev || !lp_out_dev || !work_dev || (steps > 0 && (!hist_x_dev || !hist_lp_dev)))
+        return fail(NNEST_E_ARG, "NULL device buffer");
+    if (!t_std_dev != !t_mean_dev) return fail(NNEST_E_ARG, "t_std_dev and t_mean_dev: both or neither");
+    if (!lo_dev != !hi_dev) return fail(NNEST_E_ARG, "lo_dev and hi_dev: both or neither");
+    if ((const void *)x_in_dev == (const void *)x_out_dev) return fail(NNEST_E_ARG, "x_in_dev must not be x_out_dev (partners read it during the launch)");
+    int num_cu = 0;
+    if ((rc = current_num_cu(&num_cu))) return rc;
+    char msg[400];
+    msg[0] = 0;
+    rc = launch_ensemble_x(D, lk, t_std_dev, t_mean_dev, lo_dev, hi_dev, x_in_dev, lp_in_dev, x_out_dev, tx_out_dev, lp_out_dev, hist_x_dev,
+                           hist_lp_dev, n_accept_dev, work_dev, C, steps, (uint32_t)step0, seed, constrained ? 1 : 0, loglstar, num_cu,
+                           (hipStream_t)stream, msg, sizeof(msg));
+    if (rc) return fail(rc, "%s", msg);
+    return NNEST_OK;
+}
+
 int nnest_ensemble_rounds_propose(const int *work_dev, int C, int steps, int D, int i, int half, uint64_t step0, uint64_t seed,
                                   const float *z_cur_dev, float *q_dev, void *stream) {
     int rc = ensemble_sizes(C, steps);

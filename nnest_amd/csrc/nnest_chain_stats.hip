@@ -16,6 +16,8 @@
 //   k_advance      p_s = lag sum / (C (T - s) sd), the global stop test and the ESS sum over the block; later blocks are skipped
 //                  on the device once the stop lag is known
 //   k_finish       ESS, R-hat, acceptance, jump -> out
+// emcee's normalised autocorrelation function (a different estimator: per-walker mean and normalisation, every lag, float64) has
+// its own two kernels further down, k_ac_moments and k_ac_lags, and shares k_lag_reduce.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -269,6 +271,134 @@ __global__ __launch_bounds__(LAG_THREADS) void k_lags(const float *__restrict__ 
     }
 }
 
+// ---- emcee's integrated autocorrelation time: the normalised autocorrelation function -------------------------------------------
+// f(s) = mean_k acf_k(s) / acf_k(0), acf_k(s) = sum_{t < T - s} (x_kt - m_k)(x_k,t+s - m_k) with m_k the walker's OWN mean (emcee 3
+// autocorr.integrated_time with has_walkers: include/nnest_hip.h).  Float64 throughout -- the products, the sums and the centred rows
+// in LDS: the window of the estimate compares s with 5 tau(s), and a float32 lag sum could move it.  The sum is direct, all lags
+// 0 .. T - 1 in blocks of A_LB: O(C D T^2 / 2) float64 FMAs, a few ms at the sizes a bootstrap run has.
+//   k_ac_moments   one workgroup per chain: m_k and 1 / acf_k(0) per dimension
+//   k_ac_lags      k_lags' tiling with float64 rows: a workgroup owns a group of chains, A_DT dimensions and A_LB lags; a lane owns
+//                  (8 consecutive lags, one dimension); per chain the lane's sums are scaled by 1 / acf_k(0) and added to its partial
+//   k_lag_reduce   (shared) the partials summed over chain groups in a fixed order
+constexpr int A_LB = 128, A_JT = 64, A_DT = 16, A_NCG = 64, A_MMAX = 8;
+constexpr int A_THREADS = (A_LB / RL) * A_DT;   // 256
+constexpr int A_ROWS = 2 * A_JT + A_LB;
+
+struct AcLayout {
+    size_t mom, lag_sums, partial, total;
+    AcLayout(int C, int D) {
+        const size_t ncg = C < A_NCG ? C : A_NCG;
+        size_t o = 0;
+        mom = o;      o += (size_t)C * 2 * D;
+        lag_sums = o; o += (size_t)A_MMAX * A_LB * D;
+        partial = o;  o += ncg * A_MMAX * A_LB * D;
+        total = o;
+    }
+};
+
+__global__ __launch_bounds__(256) void k_ac_moments(const float *__restrict__ x, int T, int D, long long cs, long long ss,
+                                                     double *__restrict__ mom) {
+    __shared__ double r[256];
+    __shared__ double mean[256];
+    const int i = blockIdx.x, t = threadIdx.x;
+    const float *xc = x + (long long)i * cs;
+    double *row = mom + (size_t)i * 2 * D;
+    const int Dc = D < 256 ? D : 256;
+    const int nsl = 256 / Dc;
+    for (int db = 0; db < D; db += Dc) {
+        const int d = db + t % Dc, sl = t / Dc;
+        const bool live = sl < nsl && d < D;
+        for (int pass = 0; pass < 2; ++pass) {
+            double a = 0.0;
+            if (live) {
+                const double m = pass ? mean[t % Dc] : (double)xc[d];   // (pass 0 sums about the first state)
+                for (int j = sl; j < T; j += nsl) {
+                    const double u = (double)xc[(long long)j * ss + d] - m;
+                    a += pass ? u * u : u;
+                }
+            }
+            r[t] = a;
+            __syncthreads();
+            if (t < Dc && d < D) {
+                double b = 0.0;
+                for (int k = 0; k < nsl; ++k) b += r[k * Dc + t];
+                if (pass == 0) {
+                    mean[t] = (double)xc[d] + b / T;
+                    row[d] = mean[t];
+                } else {
+                    row[D + d] = 1.0 / b;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// grid (ncg, m, ceil(D / A_DT)); partial [ncg][m * A_LB][D]
+__global__ __launch_bounds__(A_THREADS) void k_ac_lags(const float *__restrict__ x, int C, int T, int D, long long cs, long long ss,
+                                                       const double *__restrict__ mom, int lag0, int ncg, double *__restrict__ partial) {
+    __shared__ double lds[A_ROWS * A_DT];
+    const int cg = blockIdx.x, sub = blockIdx.y, m = gridDim.y;
+    const int dbase = blockIdx.z * A_DT;
+    const int Dt = min(A_DT, D - dbase);
+    const int s0 = lag0 + sub * A_LB;
+    const int t = threadIdx.x;
+    const double *A = lds, *B = lds + A_JT * Dt;
+    const int c0 = (int)((long long)cg * C / ncg), c1 = (int)((long long)(cg + 1) * C / ncg);
+    const int g = t / Dt, d = t - g * Dt;   // this lane's lags s0 + g RL .. + RL - 1 and dimension dbase + d
+    const bool live = t < (A_LB / RL) * Dt;
+    const int sg = s0 + g * RL;
+    double accd[RL];
+#pragma unroll
+    for (int r = 0; r < RL; ++r) accd[r] = 0.0;
+    for (int c = c0; c < c1; ++c) {
+        const float *xc = x + (long long)c * cs;
+        const double *mc = mom + (size_t)c * 2 * D;
+        double acc[RL];
+#pragma unroll
+        for (int r = 0; r < RL; ++r) acc[r] = 0.0;
+        for (int j0 = 0; j0 < T - s0; j0 += A_JT) {
+            __syncthreads();
+            for (int el = t; el < A_ROWS * Dt; el += A_THREADS) {
+                const int rl = el / Dt, dl = el - rl * Dt, dd = dbase + dl;
+                const int row = rl < A_JT ? j0 + rl : j0 + s0 + (rl - A_JT);
+                lds[el] = row < T ? (double)xc[(long long)row * ss + dd] - mc[dd] : 0.0;   // zero beyond T: those products drop out
+            }
+            __syncthreads();
+            const int jn = min(A_JT, T - sg - j0);
+            if (!live || jn <= 0) continue;
+            const double *Ap = A + d, *Bp = B + g * RL * Dt + d;
+            double wv[2 * RL];
+#pragma unroll
+            for (int r = 0; r < RL; ++r) wv[r] = Bp[r * Dt];
+            for (int jc = 0; jc < jn; jc += RL) {
+                double a[RL];
+#pragma unroll
+                for (int k2 = 0; k2 < RL; ++k2) {
+                    a[k2] = Ap[(jc + k2) * Dt];
+                    wv[RL + k2] = Bp[(jc + RL + k2) * Dt];
+                }
+#pragma unroll
+                for (int k2 = 0; k2 < RL; ++k2)
+#pragma unroll
+                    for (int r = 0; r < RL; ++r) acc[r] = fma(a[k2], wv[k2 + r], acc[r]);
+#pragma unroll
+                for (int r = 0; r < RL; ++r) wv[r] = wv[RL + r];
+            }
+        }
+        if (live) {
+            const double inv0 = mc[D + dbase + d];
+#pragma unroll
+            for (int r = 0; r < RL; ++r) accd[r] += acc[r] * inv0;
+        }
+    }
+    if (live) {
+        double *p = partial + ((size_t)cg * m * A_LB + (size_t)sub * A_LB + g * RL) * D + dbase + d;
+#pragma unroll
+        for (int r = 0; r < RL; ++r) p[(size_t)r * D] = accd[r];
+    }
+}
+
 // 64 sums per workgroup; the chain groups in 16 fixed segments, one per wave, the segments added in order
 __global__ __launch_bounds__(1024) void k_lag_reduce(const double *__restrict__ partial, int ncg, int n, const double *__restrict__ state,
                                                      int all_lags, double *__restrict__ lag_sums) {
@@ -518,6 +648,40 @@ int nnest_chain_stats(const float *x_dev, int C, int T, int D, long long chain_s
         }
     }
     return nnest_chain_stats_finish(sums, C, T, D, flags, work_dev, out_dev, stream);
+}
+
+int nnest_chain_autocorr_work_words(int C, int T, int D) {
+    if (C < 1 || T < 2 || D < 1 || D > (1 << 20)) return -1;
+    const size_t w = AcLayout(C, D).total;
+    return w > (size_t)0x7fffffff ? -1 : (int)w;
+}
+
+int nnest_chain_autocorr(const float *x_dev, int C, int T, int D, long long chain_stride, long long step_stride, double *work_dev,
+                         double *f_dev, void *stream) {
+    if (!x_dev || !work_dev || !f_dev) return cs_fail(NNEST_E_ARG, "chain_autocorr: NULL x_dev, work_dev or f_dev");
+    if (C < 1 || T < 2 || D < 1) return cs_fail(NNEST_E_ARG, "chain_autocorr: C=%d T=%d D=%d (C >= 1, T >= 2, D >= 1)", C, T, D);
+    if (chain_stride < 0 || step_stride < 0)
+        return cs_fail(NNEST_E_ARG, "chain_autocorr: negative stride (chain %lld, step %lld)", chain_stride, step_stride);
+    if (nnest_chain_autocorr_work_words(C, T, D) < 0) return cs_fail(NNEST_E_ARG, "chain_autocorr: C=%d D=%d: work exceeds 2^31 words", C, D);
+    const AcLayout L(C, D);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_ac_moments, dim3(C), dim3(256), 0, st, x_dev, T, D, chain_stride, step_stride, work_dev + L.mom);
+    CS_TRY(hipGetLastError());
+    const int ncg = C < A_NCG ? C : A_NCG;
+    for (int lag0 = 0; lag0 < T; lag0 += A_MMAX * A_LB) {
+        const int left = (T - lag0 + A_LB - 1) / A_LB;
+        const int m = left < A_MMAX ? left : A_MMAX;
+        hipLaunchKernelGGL(k_ac_lags, dim3(ncg, m, (D + A_DT - 1) / A_DT), dim3(A_THREADS), 0, st, x_dev, C, T, D, chain_stride, step_stride,
+                           work_dev + L.mom, lag0, ncg, work_dev + L.partial);
+        CS_TRY(hipGetLastError());
+        const int n = m * A_LB * D;
+        hipLaunchKernelGGL(k_lag_reduce, dim3((n + 63) / 64), dim3(1024), 0, st, work_dev + L.partial, ncg, n, work_dev + L.mom, 1,
+                           work_dev + L.lag_sums);
+        CS_TRY(hipGetLastError());
+        const int rows = T - lag0 < m * A_LB ? T - lag0 : m * A_LB;
+        CS_TRY(hipMemcpyAsync(f_dev + (size_t)lag0 * D, work_dev + L.lag_sums, (size_t)rows * D * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    return NNEST_OK;
 }
 
 }  // extern "C"

@@ -31,6 +31,11 @@
 //     and the accept kernel applies the rule and writes the history.
 // Both read the split from one table (ensemble_split_kernel), built per chunk for its steps: a run is a function of the seed, not of
 // its chunking or its route.
+//
+// The same move in X SPACE (ensemble_x_kernel; DESIGN.md 3.9: the emcee run EnsembleSampler.bootstrap starts from) is that definition
+// with f = identity and ld = 0.  It is a third caller of the same pieces, not a second protocol: the walk through the steps of a
+// launch -- partner, hand-off, proposal, accept, history, publish -- is ens_walk, which the two fused kernels call with their
+// position -> lp functor; the round kernels run it with an identity map for the flow.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -182,80 +187,15 @@ struct EnsArgs {
     double loglstar;
 };
 
-template <int U, int LK>
-__global__ void __launch_bounds__(256) ensemble_kernel(EnsArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float wlds[];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+// The walk of one walker (one wave) through the S steps of a launch, shared by the two fused kernels: `target` maps a position in
+// place to what the kernel reports beside it (the latent kernel: x = f^-1(z); the x-space kernel: T(x)) and returns lp.  This is the
+// only hand-off protocol in the file.  XH: the mapped rows have a history of their own (hist_x); without it the positions' history
+// (hist_z) is the run's, and x_out may be NULL.
+template <int U, bool XH, class Target>
+__device__ __forceinline__ void ens_walk(const EnsArgs &a, const int row, const int lane, Target &&target) {
     const int D = a.s.D, S = a.S, C = a.C;
-    constexpr bool LDSW = U >= 3;   // (solo_lds_weights<U, 4>: x_dim > 64 keeps the weights in LDS)
-    {
-        if constexpr (!LDSW) {
-            const int n = a.s.nets_params();
-            for (int i = threadIdx.x; i < n; i += blockDim.x) wlds[i] = a.packed[i];
-        } else if (wave < 3) {
-            SoloNet<U> nb;
-            solo_gather<U>(nb, a.packed + (size_t)(wave * 2 + (lane >= 32 ? 1 : 0)) * a.s.net_params, D, (wave + 1) & 1, wave & 1, lane);
-            solo4_store<U>(wlds, wave, nb, lane);
-        }
-    }
-    __syncthreads();
     const int pos = lane & 15;
-    const bool translate_half = lane >= 32, writer_lane = lane < 16;
-    const int row = blockIdx.x * 4 + wave;
-    if (row >= C) return;   // (no barrier behind this point)
-    SoloNet<U> net[LDSW ? 1 : 3];
-    if constexpr (!LDSW) {
-#pragma unroll
-        for (int b = 0; b < 3; ++b)
-            solo_gather<U>(net[b], wlds + (size_t)(b * 2 + (translate_half ? 1 : 0)) * a.s.net_params, D, (b + 1) & 1, b & 1, lane);
-    }
-    const unsigned sel = translate_half ? 0xffffffffu : 0u;
-    const bool h1 = (lane & 16) != 0;
-    auto inverse = [&](float (&xs)[2][U]) {   // NormalizingFlow.inverse (networks.py:34-42), blocks 2, 1, 0
-        if constexpr (LDSW) {
-            float ld = solo_coupling_inverse4<U>(Solo4Lds{wlds + (size_t)2 * SOLO4_NF * 64, lane}, sel, h1, xs[1], xs[0]);
-            ld += solo_coupling_inverse4<U>(Solo4Lds{wlds + (size_t)1 * SOLO4_NF * 64, lane}, sel, h1, xs[0], xs[1]);
-            ld += solo_coupling_inverse4<U>(Solo4Lds{wlds, lane}, sel, h1, xs[1], xs[0]);
-            return ld;
-        } else {
-            float ld;
-            solo_coupling_inverse<U, true>(net[2], sel, h1, xs[1], xs[0], ld);
-            solo_coupling_inverse<U, false>(net[1], sel, h1, xs[0], xs[1], ld);
-            solo_coupling_inverse<U, false>(net[0], sel, h1, xs[1], xs[0], ld);
-            return ld;
-        }
-    };
-    // this lane's dims: T, the box
-    float sd[2][U], mu[2][U], blo[2][U], bhi[2][U];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int d = 2 * U * pos + 2 * u + c;
-            const bool v = d < D;
-            sd[c][u] = v ? a.t_std[d] : 0.f;
-            mu[c][u] = v ? a.t_mean[d] : 0.f;
-            blo[c][u] = v && a.lo ? a.lo[d] : -INFINITY;
-            bhi[c][u] = v && a.hi ? a.hi[d] : INFINITY;
-        }
-    LikeSpec like = a.like;
-    like.scale = 1.0f;
-    // x <- f^-1(x) in place; returns lp
-    auto target = [&](float (&xs)[2][U]) -> double {
-        const float ld = solo_logdet_total(inverse(xs));
-        float tx[2][U];
-        int ok = 1;
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                tx[c][u] = ens_T(xs[c][u], sd[c][u], mu[c][u]);
-                ok &= !(tx[c][u] < blo[c][u] || tx[c][u] > bhi[c][u]);   // (NaN counts as inside: UniformPrior, priors.py)
-            }
-        const bool in_prior = __ballot(ok != 0) == ~0ull;
-        const double logl = solo_loglike<U, LK>(like, D, lane, tx);
-        return ens_target(logl, ld, in_prior, a.constrained, a.loglstar);
-    };
+    const bool writer_lane = lane < 16;
     auto load_row = [&](const float *base, float (&v)[2][U]) {
 #pragma unroll
         for (int u = 0; u < U; ++u)
@@ -338,7 +278,7 @@ __global__ void __launch_bounds__(256) ensemble_kernel(EnsArgs a) {
         const size_t hr = (size_t)row * S + i;
         if (writer_lane) {
             store_row(a.hist_z + hr * D, z);
-            store_row(a.hist_x + hr * D, x);
+            if constexpr (XH) store_row(a.hist_x + hr * D, x);
             if (pos == 0) a.hist_lp[hr] = lp;
         }
         // publish: the wave's stores, then its step count (release: one fence for the whole wave, one relaxed sc1 store)
@@ -347,12 +287,130 @@ __global__ void __launch_bounds__(256) ensemble_kernel(EnsArgs a) {
     }
     if (writer_lane) {
         store_row(a.z_out + (size_t)row * D, z);
-        store_row(a.x_out + (size_t)row * D, x);
+        if (XH || a.x_out) store_row(a.x_out + (size_t)row * D, x);
         if (pos == 0) {
             a.lp_out[row] = lp;
             if (a.n_accept) a.n_accept[row] = n_acc;
         }
     }
+}
+
+template <int U, int LK>
+__global__ void __launch_bounds__(256) ensemble_kernel(EnsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float wlds[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int D = a.s.D, C = a.C;
+    constexpr bool LDSW = U >= 3;   // (solo_lds_weights<U, 4>: x_dim > 64 keeps the weights in LDS)
+    {
+        if constexpr (!LDSW) {
+            const int n = a.s.nets_params();
+            for (int i = threadIdx.x; i < n; i += blockDim.x) wlds[i] = a.packed[i];
+        } else if (wave < 3) {
+            SoloNet<U> nb;
+            solo_gather<U>(nb, a.packed + (size_t)(wave * 2 + (lane >= 32 ? 1 : 0)) * a.s.net_params, D, (wave + 1) & 1, wave & 1, lane);
+            solo4_store<U>(wlds, wave, nb, lane);
+        }
+    }
+    __syncthreads();
+    const int pos = lane & 15;
+    const bool translate_half = lane >= 32;
+    const int row = blockIdx.x * 4 + wave;
+    if (row >= C) return;   // (no barrier behind this point)
+    SoloNet<U> net[LDSW ? 1 : 3];
+    if constexpr (!LDSW) {
+#pragma unroll
+        for (int b = 0; b < 3; ++b)
+            solo_gather<U>(net[b], wlds + (size_t)(b * 2 + (translate_half ? 1 : 0)) * a.s.net_params, D, (b + 1) & 1, b & 1, lane);
+    }
+    const unsigned sel = translate_half ? 0xffffffffu : 0u;
+    const bool h1 = (lane & 16) != 0;
+    auto inverse = [&](float (&xs)[2][U]) {   // NormalizingFlow.inverse (networks.py:34-42), blocks 2, 1, 0
+        if constexpr (LDSW) {
+            float ld = solo_coupling_inverse4<U>(Solo4Lds{wlds + (size_t)2 * SOLO4_NF * 64, lane}, sel, h1, xs[1], xs[0]);
+            ld += solo_coupling_inverse4<U>(Solo4Lds{wlds + (size_t)1 * SOLO4_NF * 64, lane}, sel, h1, xs[0], xs[1]);
+            ld += solo_coupling_inverse4<U>(Solo4Lds{wlds, lane}, sel, h1, xs[1], xs[0]);
+            return ld;
+        } else {
+            float ld;
+            solo_coupling_inverse<U, true>(net[2], sel, h1, xs[1], xs[0], ld);
+            solo_coupling_inverse<U, false>(net[1], sel, h1, xs[0], xs[1], ld);
+            solo_coupling_inverse<U, false>(net[0], sel, h1, xs[1], xs[0], ld);
+            return ld;
+        }
+    };
+    // this lane's dims: T, the box
+    float sd[2][U], mu[2][U], blo[2][U], bhi[2][U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int d = 2 * U * pos + 2 * u + c;
+            const bool v = d < D;
+            sd[c][u] = v ? a.t_std[d] : 0.f;
+            mu[c][u] = v ? a.t_mean[d] : 0.f;
+            blo[c][u] = v && a.lo ? a.lo[d] : -INFINITY;
+            bhi[c][u] = v && a.hi ? a.hi[d] : INFINITY;
+        }
+    LikeSpec like = a.like;
+    like.scale = 1.0f;
+    // x <- f^-1(x) in place; returns lp
+    auto target = [&](float (&xs)[2][U]) -> double {
+        const float ld = solo_logdet_total(inverse(xs));
+        float tx[2][U];
+        int ok = 1;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                tx[c][u] = ens_T(xs[c][u], sd[c][u], mu[c][u]);
+                ok &= !(tx[c][u] < blo[c][u] || tx[c][u] > bhi[c][u]);   // (NaN counts as inside: UniformPrior, priors.py)
+            }
+        const bool in_prior = __ballot(ok != 0) == ~0ull;
+        const double logl = solo_loglike<U, LK>(like, D, lane, tx);
+        return ens_target(logl, ld, in_prior, a.constrained, a.loglstar);
+    };
+    ens_walk<U, true>(a, row, lane, target);
+}
+
+// The x-space run: the same walk with f = identity and ld = 0, so lp(x) = safe logL(T(x)) + prior.  No flow, hence no
+// weights and no LDS; t_std / t_mean NULL: T = identity (x * 1 + 0 in float32, the value the round route computes with an identity
+// flow).  The mapped row is T(x): x_out (optional) receives it.
+template <int U, int LK>
+__global__ void __launch_bounds__(256) ensemble_x_kernel(EnsArgs a) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int D = a.s.D;
+    const int pos = lane & 15;
+    const int row = blockIdx.x * 4 + wave;
+    if (row >= a.C) return;
+    float sd[2][U], mu[2][U], blo[2][U], bhi[2][U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int d = 2 * U * pos + 2 * u + c;
+            const bool v = d < D;
+            sd[c][u] = v ? (a.t_std ? a.t_std[d] : 1.f) : 0.f;
+            mu[c][u] = v && a.t_mean ? a.t_mean[d] : 0.f;
+            blo[c][u] = v && a.lo ? a.lo[d] : -INFINITY;
+            bhi[c][u] = v && a.hi ? a.hi[d] : INFINITY;
+        }
+    LikeSpec like = a.like;
+    like.scale = 1.0f;
+    // x <- T(x) in place; returns lp
+    auto target = [&](float (&xs)[2][U]) -> double {
+        int ok = 1;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                xs[c][u] = ens_T(xs[c][u], sd[c][u], mu[c][u]);
+                ok &= !(xs[c][u] < blo[c][u] || xs[c][u] > bhi[c][u]);   // (NaN counts as inside: UniformPrior, priors.py)
+            }
+        const bool in_prior = __ballot(ok != 0) == ~0ull;
+        const double logl = solo_loglike<U, LK>(like, D, lane, xs);
+        return ens_target(logl, 0.f, in_prior, a.constrained, a.loglstar);
+    };
+    ens_walk<U, false>(a, row, lane, target);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -480,11 +538,8 @@ static size_t ens_lds(const FlowShape &s) {
 // "Residency and cooperative launch").  The runtime does not report a kernel's SGPRs, so the SGPR term is taken at the ceiling a
 // wave can allocate (102 -> 112 in granules of 16): 6 per CU; the kernels use far fewer and their VGPRs bind first.
 constexpr int ENS_SGPR_CEIL = 112;
-template <int U, int LK>
-static hipError_t ens_blocks_per_cu(const FlowShape &s, int *out) {
-    const void *fn = reinterpret_cast<const void *>(ensemble_kernel<U, LK>);
-    const size_t lds = ens_lds<U, LK>(s);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+static hipError_t ens_blocks_per_cu(const void *fn, size_t lds, int *out) {
+    hipError_t e = lds ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
     if (e != hipSuccess) return e;
     int n = 0;
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, lds);
@@ -494,28 +549,41 @@ static hipError_t ens_blocks_per_cu(const FlowShape &s, int *out) {
     return hipSuccess;
 }
 
-template <int U, int LK>
+// X: the x-space kernel (no flow: a.s carries D and NT only, no LDS)
+template <int U, int LK, bool X>
 static hipError_t ens_launch_k(const EnsArgs &a, int num_cu, bool launch, int *max_walkers, hipStream_t st) {
+    const void *fn = X ? reinterpret_cast<const void *>(ensemble_x_kernel<U, LK>) : reinterpret_cast<const void *>(ensemble_kernel<U, LK>);
+    const size_t lds = X ? 0 : ens_lds<U, LK>(a.s);
     int per_cu = 0;
-    hipError_t e = ens_blocks_per_cu<U, LK>(a.s, &per_cu);
+    hipError_t e = ens_blocks_per_cu(fn, lds, &per_cu);
     if (e != hipSuccess) return e;
     *max_walkers = 4 * per_cu * num_cu;
     if (!launch) return hipSuccess;
-    const size_t lds = ens_lds<U, LK>(a.s);
-    hipLaunchKernelGGL((ensemble_kernel<U, LK>), dim3((a.C + 3) / 4), dim3(256), lds, st, a);
+    if constexpr (X) hipLaunchKernelGGL((ensemble_x_kernel<U, LK>), dim3((a.C + 3) / 4), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((ensemble_kernel<U, LK>), dim3((a.C + 3) / 4), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 
 // launch (when `launch` and C fits) or only size: *max_walkers = the resident population of the instantiation the call would run
+template <bool X>
 static hipError_t ens_dispatch(const EnsArgs &a, int num_cu, bool launch, int *max_walkers, hipStream_t st) {
     const bool rosen = a.like.id == NNEST_LIKE_ROSENBROCK;
     switch (a.s.NT) {
-        case 1: return rosen ? ens_launch_k<1, NNEST_LIKE_ROSENBROCK>(a, num_cu, launch, max_walkers, st) : ens_launch_k<1, -1>(a, num_cu, launch, max_walkers, st);
-        case 2: return rosen ? ens_launch_k<2, NNEST_LIKE_ROSENBROCK>(a, num_cu, launch, max_walkers, st) : ens_launch_k<2, -1>(a, num_cu, launch, max_walkers, st);
-        case 3: return rosen ? ens_launch_k<3, NNEST_LIKE_ROSENBROCK>(a, num_cu, launch, max_walkers, st) : ens_launch_k<3, -1>(a, num_cu, launch, max_walkers, st);
-        case 4: return rosen ? ens_launch_k<4, NNEST_LIKE_ROSENBROCK>(a, num_cu, launch, max_walkers, st) : ens_launch_k<4, -1>(a, num_cu, launch, max_walkers, st);
+        case 1: return rosen ? ens_launch_k<1, NNEST_LIKE_ROSENBROCK, X>(a, num_cu, launch, max_walkers, st) : ens_launch_k<1, -1, X>(a, num_cu, launch, max_walkers, st);
+        case 2: return rosen ? ens_launch_k<2, NNEST_LIKE_ROSENBROCK, X>(a, num_cu, launch, max_walkers, st) : ens_launch_k<2, -1, X>(a, num_cu, launch, max_walkers, st);
+        case 3: return rosen ? ens_launch_k<3, NNEST_LIKE_ROSENBROCK, X>(a, num_cu, launch, max_walkers, st) : ens_launch_k<3, -1, X>(a, num_cu, launch, max_walkers, st);
+        case 4: return rosen ? ens_launch_k<4, NNEST_LIKE_ROSENBROCK, X>(a, num_cu, launch, max_walkers, st) : ens_launch_k<4, -1, X>(a, num_cu, launch, max_walkers, st);
     }
     return hipErrorInvalidConfiguration;
+}
+
+// the shape the x-space kernel reads: D and the solo layout's U = NT
+static FlowShape ens_x_shape(int D) {
+    FlowShape s;
+    memset(&s, 0, sizeof(s));
+    s.D = D;
+    s.NT = ((D + 1) / 2 + 15) / 16;
+    return s;
 }
 
 hipError_t ensemble_max_walkers(const FlowShape &s, int like_id, int num_cu, int *out) {
@@ -523,7 +591,48 @@ hipError_t ensemble_max_walkers(const FlowShape &s, int like_id, int num_cu, int
     memset(&a, 0, sizeof(a));
     a.s = s;
     a.like.id = like_id;
-    return ens_dispatch(a, num_cu, false, out, 0);
+    return ens_dispatch<false>(a, num_cu, false, out, 0);
+}
+
+hipError_t ensemble_x_max_walkers(int D, int like_id, int num_cu, int *out) {
+    EnsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.s = ens_x_shape(D);
+    a.like.id = like_id;
+    return ens_dispatch<true>(a, num_cu, false, out, 0);
+}
+
+// the size query, the residency refusal, the split, the launch and the error word, for either fused kernel
+template <bool X>
+static int ens_run(const EnsArgs &a, int num_cu, hipStream_t st, char *msg, size_t msg_len) {
+    const char *name = X ? "ensemble_x_kernel" : "ensemble_kernel";
+    int max_walkers = 0;
+    hipError_t e = ens_dispatch<X>(a, num_cu, false, &max_walkers, st);
+    if (e != hipSuccess) { snprintf(msg, msg_len, "occupancy query: %s", hipGetErrorString(e)); return NNEST_E_HIP; }
+    if (a.C > max_walkers) {
+        snprintf(msg, msg_len, "ensemble: %d walkers > %d resident (one walker per wave, every workgroup resident); the round route takes it",
+                 a.C, max_walkers);
+        return NNEST_E_UNSUPPORTED;
+    }
+    if ((e = launch_ensemble_split(a.work, nullptr, a.C, a.S, a.step0, a.seed, st)) != hipSuccess) {
+        snprintf(msg, msg_len, "split: %s", hipGetErrorString(e));
+        return NNEST_E_HIP;
+    }
+    if ((e = ens_dispatch<X>(a, num_cu, true, &max_walkers, st)) != hipSuccess) {
+        snprintf(msg, msg_len, "%s: %s", name, hipGetErrorString(e));
+        return NNEST_E_HIP;
+    }
+    int host_err = 0;
+    if ((e = hipMemcpyAsync(&host_err, a.work, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess) {
+        snprintf(msg, msg_len, "%s: %s", name, hipGetErrorString(e));
+        return NNEST_E_HIP;
+    }
+    if (host_err) {
+        snprintf(msg, msg_len, "%s: a hand-off wait ran out (a workgroup was not resident?); the outputs are incomplete", name);
+        return NNEST_E_HIP;
+    }
+    return NNEST_OK;
 }
 
 int launch_ensemble(const FlowShape &s, const float *packed, const LikeSpec &like, const float *t_std, const float *t_mean, const float *lo,
@@ -536,33 +645,21 @@ int launch_ensemble(const FlowShape &s, const float *packed, const LikeSpec &lik
     a.z_in = z_in; a.lp_in = lp_in; a.z_out = z_out; a.x_out = x_out; a.lp_out = lp_out;
     a.hist_z = hist_z; a.hist_x = hist_x; a.hist_lp = hist_lp; a.n_accept = n_accept; a.work = work;
     a.C = C; a.S = S; a.constrained = constrained; a.step0 = step0; a.seed = seed; a.loglstar = loglstar;
-    int max_walkers = 0;
-    hipError_t e = ens_dispatch(a, num_cu, false, &max_walkers, st);
-    if (e != hipSuccess) { snprintf(msg, msg_len, "occupancy query: %s", hipGetErrorString(e)); return NNEST_E_HIP; }
-    if (C > max_walkers) {
-        snprintf(msg, msg_len, "ensemble: %d walkers > %d resident (one walker per wave, every workgroup resident); the round route takes it",
-                 C, max_walkers);
-        return NNEST_E_UNSUPPORTED;
-    }
-    if ((e = launch_ensemble_split(work, nullptr, C, S, step0, seed, st)) != hipSuccess) {
-        snprintf(msg, msg_len, "split: %s", hipGetErrorString(e));
-        return NNEST_E_HIP;
-    }
-    if ((e = ens_dispatch(a, num_cu, true, &max_walkers, st)) != hipSuccess) {
-        snprintf(msg, msg_len, "ensemble_kernel: %s", hipGetErrorString(e));
-        return NNEST_E_HIP;
-    }
-    int host_err = 0;
-    if ((e = hipMemcpyAsync(&host_err, work, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess ||
-        (e = hipStreamSynchronize(st)) != hipSuccess) {
-        snprintf(msg, msg_len, "ensemble_kernel: %s", hipGetErrorString(e));
-        return NNEST_E_HIP;
-    }
-    if (host_err) {
-        snprintf(msg, msg_len, "ensemble_kernel: a hand-off wait ran out (a workgroup was not resident?); the outputs are incomplete");
-        return NNEST_E_HIP;
-    }
-    return NNEST_OK;
+    return ens_run<false>(a, num_cu, st, msg, msg_len);
+}
+
+// the x-space run: the positions are x (EnsArgs' z slots), the mapped row is T(x) (tx_out, optional)
+int launch_ensemble_x(int D, const LikeSpec &like, const float *t_std, const float *t_mean, const float *lo, const float *hi,
+                      const float *x_in, const double *lp_in, float *x_out, float *tx_out, double *lp_out, float *hist_x, double *hist_lp,
+                      int *n_accept, int *work, int C, int S, uint32_t step0, uint64_t seed, int constrained, double loglstar, int num_cu,
+                      hipStream_t st, char *msg, size_t msg_len) {
+    EnsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.s = ens_x_shape(D); a.like = like; a.t_std = t_std; a.t_mean = t_mean; a.lo = lo; a.hi = hi;
+    a.z_in = x_in; a.lp_in = lp_in; a.z_out = x_out; a.x_out = tx_out; a.lp_out = lp_out;
+    a.hist_z = hist_x; a.hist_lp = hist_lp; a.n_accept = n_accept; a.work = work;
+    a.C = C; a.S = S; a.constrained = constrained; a.step0 = step0; a.seed = seed; a.loglstar = loglstar;
+    return ens_run<true>(a, num_cu, st, msg, msg_len);
 }
 
 hipError_t launch_ensemble_propose(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const float *z_cur,

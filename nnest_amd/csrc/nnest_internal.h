@@ -89,6 +89,11 @@ hipError_t launch_slice_fill_noise(float *dz, int steps, int C, int D, uint64_t 
 size_t ensemble_work_words(int C, int S);
 bool ensemble_form_eligible(const FlowShape &s);
 hipError_t ensemble_max_walkers(const FlowShape &s, int like_id, int num_cu, int *out);
+hipError_t ensemble_x_max_walkers(int D, int like_id, int num_cu, int *out);
+int launch_ensemble_x(int D, const LikeSpec &like, const float *t_std, const float *t_mean, const float *lo, const float *hi,
+                      const float *x_in, const double *lp_in, float *x_out, float *tx_out, double *lp_out, float *hist_x, double *hist_lp,
+                      int *n_accept, int *work, int C, int S, uint32_t step0, uint64_t seed, int constrained, double loglstar, int num_cu,
+                      hipStream_t st, char *msg, size_t msg_len);
 hipError_t launch_ensemble_split(int *work, float *u, int C, int S, uint32_t step0, uint64_t seed, hipStream_t st);
 int launch_ensemble(const FlowShape &s, const float *packed, const LikeSpec &like, const float *t_std, const float *t_mean, const float *lo,
                     const float *hi, const float *z_in, const double *lp_in, float *z_out, float *x_out, double *lp_out, float *hist_z,

@@ -42,6 +42,16 @@ def _dev_vec(v, D, dev):
     return None if v is None else torch.as_tensor(np.asarray(v, np.float32).reshape(D)).to(dev)
 
 
+class IdentityFlow(object):
+    """the identity as a flow, for the stretch move in x space on the round route: inverse(z) -> (z, zeros)"""
+
+    def __init__(self, device=None):
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+
+    def inverse(self, z):
+        return z, torch.zeros(z.shape[0], dtype=torch.float32, device=z.device)
+
+
 class EnsembleState(object):
     """the walkers between launches: z, x [C, D] float32, lp [C] float64, n_accept [C] int32 (device), derived [C, nd] (host)"""
 

@@ -118,6 +118,58 @@ class ShardedChainStats(object):
         return float(o[0]), o[4:4 + D].copy(), float(o[1])
 
 
+# ---- emcee's integrated autocorrelation time (emcee 3 autocorr.integrated_time, has_walkers=True), restated ------------------------
+class AutocorrError(Exception):
+    """the chain is shorter than `tol` autocorrelation times: `tau` [D] is the estimate, `thresh` the chain length each one
+    would need over tol (emcee's AutocorrError carries the same two)"""
+
+    def __init__(self, tau, thresh, *args):
+        self.tau, self.thresh = tau, thresh
+        super(AutocorrError, self).__init__(*args)
+
+
+def autocorr_function(x):
+    """f [T, D] float64 (device): f(s) = mean_k acf_k(s) / acf_k(0) over the walkers of x [C, T, D], every lag, each walker
+    centred on its own mean (include/nnest_hip.h nnest_chain_autocorr)"""
+    t, cs, ss = _device_chains(x)
+    C, T, D = t.shape
+    dev = t.device
+    lib = _lib.load()
+    words = lib.nnest_chain_autocorr_work_words(C, T, D)
+    if words < 0:
+        raise ValueError('autocorr_function: unsupported shape C=%d T=%d D=%d (C >= 1, T >= 2, D >= 1)' % (C, T, D))
+    with torch.cuda.device(dev):
+        work = torch.empty(words, dtype=torch.float64, device=dev)
+        f = torch.empty(T, D, dtype=torch.float64, device=dev)
+        _lib.check(lib.nnest_chain_autocorr(_lib.ptr(t), C, T, D, cs, ss, _lib.ptr(work), _lib.ptr(f), _lib.current_stream(dev)))
+    return f / C
+
+
+def integrated_autocorr_time(x, c=5, tol=50, quiet=False, return_window=False):
+    """emcee's integrated autocorrelation time tau [D] of walkers x [C, T, D]: taus = 2 cumsum(f) - 1 with f = autocorr_function,
+    cut at Sokal's window: with m = arange(T) < c * taus, argmin(m) if any entry of m is true, else T - 1 (so an all-true m gives
+    window 0, as emcee's auto_window does).  This is NOT auto_correlation_time / effective_sample_size below (the reference's own
+    estimator: global mean, divided by the standard deviation, stopped globally).  If tol * tau > T for any dimension the chain
+    is too short for the estimate: AutocorrError (with tau and thresh), or a warning and the estimate when `quiet`.  The lag sums
+    run on the GPU; the cumulative sum and the window are torch on the [T, D] table."""
+    f = autocorr_function(x)
+    T, D = f.shape
+    taus = 2.0 * torch.cumsum(f, dim=0) - 1.0
+    m = torch.arange(T, device=f.device, dtype=torch.float64)[:, None] < float(c) * taus
+    window = torch.where(m.any(dim=0), torch.argmin(m.to(torch.int8), dim=0), torch.full((D,), T - 1, device=f.device))
+    tau = taus.gather(0, window[None, :])[0].cpu().numpy()
+    window = window.cpu().numpy()
+    flag = tol * tau > T
+    if np.any(flag) and tol > 0:
+        msg = ('The chain is shorter than %d times the integrated autocorrelation time for %d parameter(s). Use this estimate with '
+               'caution and run a longer chain!\nN/%d = %.0f;\ntau: %s' % (tol, int(np.sum(flag)), tol, T / tol, tau))
+        if not quiet:
+            raise AutocorrError(tau, T / tol, msg)
+        import logging
+        logging.getLogger(__name__).warning(msg)
+    return (tau, window) if return_window else tau
+
+
 # ---- the reference's functions (nnest/utils/evaluation.py), same names and signatures ----------------------------------------
 def auto_correlation_time(x, s, mu, var):
     """p_s [D]: (1 / C) sum_i mean_j (x_ij - mu)(x_i,j+s - mu) / var  (evaluation.py:6-14; `var` as the reference divides by it)"""

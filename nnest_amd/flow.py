@@ -802,3 +802,46 @@ def loglike(like_id, x_unit, like_scale, device=None, like_params=None):
         _lib.check(_lib.load().nnest_loglike(ctypes.byref(lk), _lib.ptr(x), _lib.ptr(out), x.shape[0],
                                              x.shape[1], _lib.current_stream(device)))
     return out
+
+
+def ensemble_x_max_walkers(D, like_id, device=None):
+    """the population ensemble_x_steps takes for x_dim D and this likelihood (every workgroup resident); 0 where it takes none"""
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    with torch.cuda.device(device):
+        return max(0, int(_lib.load().nnest_ensemble_x_max_walkers(int(D), int(like_id))))
+
+
+def ensemble_x_steps(like_id, x, steps, t_std=None, t_mean=None, lo=None, hi=None, lp=None, loglstar=None, seed=0, step0=0,
+                     like_params=None, device=None):
+    """`steps` steps of emcee's stretch move in X space, in ONE launch (nnest_ensemble_x_steps: HipNVP.ensemble_steps' run with
+    the identity for the flow; build-defined stream, emcee's move).  x [C, D] float32: the walkers' start (read only); lp [C]
+    float64 or None (evaluated); the target is lp(x) = logL(T(x)) + prior with T(x) = x * t_std + t_mean (both None: the identity),
+    the prior the box lo / hi [D] on T(x) (None: none); loglstar: None, or the hard constraint.  Returns x, tx (= T(x)), lp (the
+    last state), hist_x [C, steps, D], hist_lp [C, steps] and n_accept [C].  Raises NnestHipError (code NNEST_E_UNSUPPORTED) when C
+    exceeds ensemble_x_max_walkers."""
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    x = _as_dev_f32(x, dev).contiguous()
+    (C, D), steps = x.shape, int(steps)
+    if (t_std is None) != (t_mean is None):
+        raise ValueError('ensemble_x_steps: t_std and t_mean: both or neither')
+    f32 = dict(dtype=torch.float32, device=dev)
+    vec = lambda v: None if v is None else _as_dev_f32(np.asarray(v, np.float32).reshape(1, D), dev).reshape(D)
+    t_std, t_mean, lo_t, hi_t = vec(t_std), vec(t_mean), vec(lo), vec(hi)
+    if lp is not None:
+        lp = torch.as_tensor(lp, dtype=torch.float64).to(dev).contiguous()
+    lib = _lib.load()
+    out = dict(x=torch.empty(C, D, **f32), tx=torch.empty(C, D, **f32), lp=torch.empty(C, dtype=torch.float64, device=dev),
+               hist_x=torch.empty(C, steps, D, **f32), hist_lp=torch.empty(C, steps, dtype=torch.float64, device=dev),
+               n_accept=torch.empty(C, dtype=torch.int32, device=dev))
+    words = lib.nnest_ensemble_work_words(C, steps)
+    if words < 0:
+        raise ValueError('ensemble_x_steps: %d walkers x %d steps: the work buffer is too large; launch fewer steps' % (C, steps))
+    work = torch.empty(words, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        lk = _lib.like_spec(like_id, 1.0, like_params)
+        _lib.check(lib.nnest_ensemble_x_steps(
+            ctypes.byref(lk), _lib.ptr(t_std), _lib.ptr(t_mean), _lib.ptr(lo_t), _lib.ptr(hi_t), _lib.ptr(x), _lib.ptr(lp),
+            _lib.ptr(out['x']), _lib.ptr(out['tx']), _lib.ptr(out['lp']), _lib.ptr(out['hist_x']), _lib.ptr(out['hist_lp']),
+            _lib.ptr(out['n_accept']), _lib.ptr(work), C, D, steps, int(step0) & 0xFFFFFFFFFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF,
+            0 if loglstar is None else 1, 0.0 if loglstar is None else float(loglstar), _lib.current_stream(dev)))
+    return out

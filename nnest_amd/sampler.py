@@ -840,6 +840,78 @@ class Sampler(object):
         self.ensemble_route = route
         return samples, latent, derived, loglikes, ncall
 
+    def _ensemble_sample_x(self, mcmc_steps, init_samples, init_loglikes=None, loglstar=None, affine=None, output_interval=None,
+                           seed=None, chunk_steps=None, route=None):
+        """The stretch move in X space: `_ensemble_sample`'s run with the identity for the flow, so the walkers are x and the target
+        is logL(T(x)) + prior -- the emcee run EnsembleSampler.bootstrap starts from (ensemble.py:111-147).  BUILD-DEFINED STREAM,
+        EMCEE'S MOVE (include/nnest_hip.h nnest_ensemble_x_steps).  T is `affine` = (std, mean), None: the identity.  Route 'fused'
+        (nnest_ensemble_x_steps) where the likelihood and the prior run on the device and the population is resident, 'rounds'
+        (ensemble_rounds on an IdentityFlow) otherwise: a Python likelihood, another prior, derived parameters, a larger
+        population; `route` pins one, for tests.  Cut into launches like `_ensemble_sample`.  Returns (samples [N, S, D],
+        loglikes [N, S] (the log target), derived [N, S, nd], ncall)."""
+        from . import flow as _flow
+        from .ensemble_rounds import IdentityFlow, ensemble_rounds
+        S = int(mcmc_steps)
+        init_samples = np.asarray(init_samples)
+        N, D, nd = init_samples.shape[0], self.x_dim, self.num_derived
+        if init_samples.shape != (N, D):
+            raise ValueError('init_samples must be shaped [num_walkers, %d], got %s' % (D, init_samples.shape))
+        if N < 2 * D:   # emcee/moves/red_blue.py
+            raise RuntimeError('It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions.')
+        dev = self.trainer.netG.device
+        if affine is None:
+            affine = (np.ones(D), np.zeros(D))
+        x = _flow._as_dev_f32(init_samples, dev).contiguous()
+        lp0 = None if init_loglikes is None else torch.as_tensor(np.asarray(init_loglikes, np.float64)).to(dev)
+        seed = self._next_seed() if seed is None else int(seed)
+        dlike = self._ensemble_device_like(affine)
+        fused_ok = dlike is not None and D <= 128 and N <= _flow.ensemble_x_max_walkers(D, dlike[0], device=dev)
+        if route is None:
+            route = 'fused' if fused_ok else 'rounds'
+        elif route == 'fused' and not fused_ok:
+            raise ValueError('ensemble: the fused x-space route does not take this likelihood, prior or population')
+        if chunk_steps is None:
+            chunk_steps = max(1, self.ENSEMBLE_HISTORY_BYTES // (N * (8 * D + 8)))
+        chunk_steps = max(1, min(int(chunk_steps), S if S > 0 else 1))
+        if output_interval:
+            chunk_steps = min(chunk_steps, int(output_interval))
+        samples = np.empty((N, S, D), np.float32)
+        loglikes = np.empty((N, S))
+        derived = np.zeros((N, S, nd))
+        ncall = 0 if init_loglikes is not None else N
+        ident = IdentityFlow(dev)
+        state, n_acc, done = None, 0, 0
+        while done < S:
+            k = min(chunk_steps, S - done)
+            if route == 'fused':
+                like_id, params, lo, hi = dlike
+                res = _flow.ensemble_x_steps(like_id, x, k, t_std=affine[0], t_mean=affine[1], lo=lo, hi=hi, lp=lp0, loglstar=loglstar,
+                                             seed=seed, step0=done, like_params=params, device=dev)
+                x, lp0 = res['x'], res['lp']
+                hx, hl = res['hist_x'], res['hist_lp']
+                n_acc += int(res['n_accept'].sum().item())
+            else:
+                kw = dict(loglstar=loglstar, seed=seed, step0=done)
+                if dlike is not None:
+                    kw.update(like_id=dlike[0], like_params=dlike[1], t_std=affine[0], t_mean=affine[1], lo=dlike[2], hi=dlike[3])
+                else:
+                    kw.update(loglike=self.loglike, prior=self.prior if self._user_prior is not None else None, num_derived=nd)
+                acc0 = 0 if state is None else int(state.n_accept.sum().item())
+                state, h = ensemble_rounds(ident, x, k, state=state, lp=lp0, **kw)
+                hx, hl = h['hist_z'], h['hist_lp']
+                n_acc += int(state.n_accept.sum().item()) - acc0
+                derived[:, done:done + k] = h['hist_derived']
+            samples[:, done:done + k] = hx.cpu().numpy()
+            loglikes[:, done:done + k] = hl.cpu().numpy()
+            done += k
+        ncall += N * S
+        if route == 'fused' or dlike is not None:   # (the host protocol counts its own calls in self.loglike)
+            self.total_calls += ncall
+        self.total_accepted += n_acc
+        self.total_rejected += N * S - n_acc
+        self.ensemble_route = route
+        return samples, loglikes, derived, ncall
+
     # ---- chain statistics (sampler.py:474-492) ---------------------------------------------------------------------
     def _chain_stats(self, samples, mean=None, std=None, step=None, affine=None):
         """acceptance rate, ESS [D] and mean jump distance of chains samples [C, T, D] (numpy, or a CUDA tensor read in place), and
