@@ -323,6 +323,29 @@ int nnest_ensemble_rounds_accept(const int *work_dev, int C, int steps, int D, i
                                  float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *acc_rows_dev, int constrained,
                                  double loglstar, void *stream);
 
+/* The FUSED route through the NEURAL-SPLINE flow: the run above with f the spline flow (the split table, the Philox streams 3 and 4,
+ * zz, the partner, q, lnpdiff, lp, T and the box are the ones above), `steps` steps in one launch.  (Added within ABI 15.)
+ * Layout: 16 walkers per workgroup, four waves per tile (the team form of nnest_spline_mh_constrained_steps, and its shapes); a step
+ * is two half-steps, each one evaluation of the tile: in half h the walkers of set h propose, the others evaluate their own point
+ * and the result is discarded.
+ * THE TWO-PUBLISH RULE: a tile holds walkers of both sets, so it publishes TWICE per step -- after half 0 the history rows and the
+ * step counts (t + 1) of its set-0 walkers, after half 1 those of its set-1 walkers.  Half 1 of step t waits for set-0 partners at
+ * count t + 1; with one publish at the end of a step two tiles could wait for each other.  With two, every wait points to an
+ * earlier (step, half), partners in the same tile included, so the launch completes whenever every workgroup is resident.
+ * nnest_spline_ensemble_max_walkers: the population nnest_spline_ensemble_steps takes: 16 walkers per workgroup times the resident
+ *   workgroups by the formula of nnest_ensemble_max_walkers; -1 for a NULL handle, an unknown likelihood id or a shape the kernel
+ *   is not instantiated for.
+ * nnest_spline_ensemble_steps: the argument list, the argument checks, the residency refusal (C > max_walkers:
+ *   NNEST_E_UNSUPPORTED; a grid that is not proven resident is never launched) and the bounded hand-off wait (NNEST_E_HIP) of
+ *   nnest_ensemble_steps.  work_dev: nnest_ensemble_work_words; the draws: nnest_ensemble_fill_noise. */
+struct nnest_spline;
+int nnest_spline_ensemble_max_walkers(struct nnest_spline *spl, int like_id);
+int nnest_spline_ensemble_steps(struct nnest_spline *spl, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                                const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, float *z_out_dev,
+                                float *x_out_dev, double *lp_out_dev, float *hist_z_dev, float *hist_x_dev, double *hist_lp_dev,
+                                int *n_accept_dev, int *work_dev, int C, int steps, uint64_t step0, uint64_t seed, int constrained,
+                                double loglstar, void *stream);
+
 /* The stretch move in X SPACE: the run above with f = identity and ld = 0, so the walkers are x_k and
  *   lp(x) = safe_loglike(T(x)) + prior (constrained = 1: -inf if logL < loglstar, else prior),
  * T the identity (t_std_dev = t_mean_dev = NULL) or x * t_std + t_mean, the prior the box on T(x) or none.  The split table, the

@@ -158,6 +158,8 @@ SIGNATURES = {
     'nnest_ensemble_fill_noise': [_vp, _vp, _i, _i, _u64, _u64, _vp],
     'nnest_ensemble_max_walkers': [_vp, _i],
     'nnest_ensemble_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _u64, _u64, _i, _d, _vp],
+    'nnest_spline_ensemble_max_walkers': [_vp, _i],
+    'nnest_spline_ensemble_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _u64, _u64, _i, _d, _vp],
     'nnest_ensemble_x_max_walkers': [_i, _i],
     'nnest_ensemble_x_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _u64, _u64, _i, _d, _vp],
     'nnest_ensemble_rounds_propose': [_vp, _i, _i, _i, _i, _i, _u64, _u64, _vp, _vp, _vp],

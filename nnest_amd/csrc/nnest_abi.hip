@@ -403,11 +403,13 @@ int nnest_ensemble_work_words(int C, int steps) {
     return w > (size_t)0x7fffffff ? -1 : (int)w;
 }
 
-static int ensemble_sizes(int C, int steps) {
+}  // extern "C"
+int nnest::ensemble_sizes(int C, int steps) {
     if (C < 2 || C > (1 << 16) || steps < 0) return fail(NNEST_E_ARG, "ensemble: C=%d (2..65536 walkers) steps=%d", C, steps);
     if (nnest_ensemble_work_words(C, steps) < 0) return fail(NNEST_E_ARG, "ensemble: C=%d x steps=%d: the work buffer exceeds 2^31 words", C, steps);
     return NNEST_OK;
 }
+extern "C" {
 
 int nnest_ensemble_fill_noise(int *work_dev, float *u_dev, int C, int steps, uint64_t step0, uint64_t seed, void *stream) {
     int rc = ensemble_sizes(C, steps);

@@ -30,7 +30,8 @@
 //     moving set's proposals (rows in ascending walker order), the caller maps them through the flow's inverse and the likelihood,
 //     and the accept kernel applies the rule and writes the history.
 // Both read the split from one table (ensemble_split_kernel), built per chunk for its steps: a run is a function of the seed, not of
-// its chunking or its route.
+// its chunking or its route.  The draws, the move's arithmetic, the work buffer's layout and the two ends of the hand-off live in
+// ensemble_common.h, shared with the spline flow's fused kernel (nnest_spline_ensemble.hip: a third route, 16-walker tiles).
 //
 // The same move in X SPACE (ensemble_x_kernel; DESIGN.md 3.9: the emcee run EnsembleSampler.bootstrap starts from) is that definition
 // with f = identity and ld = 0.  It is a third caller of the same pieces, not a second protocol: the walk through the steps of a
@@ -41,56 +42,13 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "ensemble_common.h"
 #include "flow_tile.h"
 #include "nnest_internal.h"
 #include "solo_loglike.h"
 #include "solo_tile.h"
 
 namespace nnest {
-
-enum { NOISE_STREAM_ENSEMBLE = 3, NOISE_STREAM_ENSEMBLE_SPLIT = 4 };
-constexpr float ENS_A = 2.0f;                  // the stretch scale a (emcee's default)
-constexpr long long ENS_SPIN_TICKS = 200000000;   // a hand-off wait gives up after ~2 s of the 100 MHz wall clock
-constexpr int ENS_CTRL_WORDS = 4;              // work: [error word, pad x 3][tags, padded to 4 words][inds S x N][members S x N]
-
-__host__ __device__ inline int ens_tags_words(int C) { return (C + 3) & ~3; }
-__host__ __device__ inline size_t ens_split_off(int C) { return (size_t)ENS_CTRL_WORDS + ens_tags_words(C); }
-
-// the walker's three uniforms of step t (24-bit fractions: exact in float32)
-struct EnsU { float u1, u2, u3; uint32_t m2; };
-__device__ __forceinline__ EnsU ens_uniforms(uint64_t seed, uint64_t walker, uint32_t t) {
-    u32x4 c;
-    c.x = 0;
-    c.y = (uint32_t)walker;
-    c.z = t;
-    c.w = ((uint32_t)(walker >> 32) & 0x0fffffffu) | ((uint32_t)NOISE_STREAM_ENSEMBLE << 28);
-    const u32x4 r = philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    EnsU u;
-    u.u1 = (float)(r.x >> 8) * 5.9604644775390625e-08f;
-    u.m2 = r.y >> 8;
-    u.u2 = (float)u.m2 * 5.9604644775390625e-08f;
-    u.u3 = (float)(r.z >> 8) * 5.9604644775390625e-08f;
-    return u;
-}
-
-#pragma clang fp contract(off)
-__device__ __forceinline__ float ens_zz(float u1) {
-    const float s = (ENS_A - 1.0f) * u1 + 1.0f;
-    return s * s / ENS_A;
-}
-__device__ __forceinline__ float ens_propose(float zj, float zk, float zz) { return zj - (zj - zk) * zz; }
-__device__ __forceinline__ float ens_T(float x, float sd, float mu) { return x * sd + mu; }
-// the latent log target from logL (already safe), the log-det and the prior's verdict
-__device__ __forceinline__ double ens_target(double logl, float ld, bool in_prior, int constrained, double loglstar) {
-    const double prior = in_prior ? 0.0 : -INFINITY;
-    if (constrained) return logl < loglstar ? -INFINITY : (double)ld + prior;
-    return (logl + (double)ld) + prior;
-}
-__device__ __forceinline__ bool ens_accept(double lp_new, double lp_old, float zz, float u3, int D) {
-    const double lnpdiff = (double)(D - 1) * log((double)zz) + lp_new - lp_old;
-    return lnpdiff > log((double)u3);
-}
-#pragma clang fp contract(fast)
 
 // ---- the split of each step of a chunk: one wave per step, the population shuffled in LDS, one byte per walker (hence at most
 // 65536 walkers: nnest_abi.hip) ----
@@ -167,25 +125,7 @@ __global__ void ensemble_fill_u_kernel(float *__restrict__ u, int C, int S, uint
 // ------------------------------------------------------------------------------------------------
 // FUSED route: one walker per wave (the solo layout of nnest_solo.hip: lane = 32 n + 16 h + p holds dims 2U p + 2u + c; the four
 // (n, h) rows hold copies), four walkers per workgroup.
-struct EnsArgs {
-    FlowShape s;
-    const float *packed;
-    LikeSpec like;                  // scale 1: the likelihood sees T(x)
-    const float *t_std, *t_mean;    // [D]
-    const float *lo, *hi;           // the prior box on T(x) [D], or NULL (no prior)
-    const float *z_in;              // [C][D], read only (a partner may still read it after this walker has finished)
-    const double *lp_in;            // [C] or NULL: evaluate lp(z_in)
-    float *z_out, *x_out;           // [C][D]
-    double *lp_out;                 // [C]
-    float *hist_z, *hist_x;         // [C][S][D]
-    double *hist_lp;                // [C][S]
-    int *n_accept;                  // [C]
-    int *work;
-    int C, S, constrained;
-    uint32_t step0;
-    uint64_t seed;
-    double loglstar;
-};
+// (struct EnsArgs: ensemble_common.h)
 
 // The walk of one walker (one wave) through the S steps of a launch, shared by the two fused kernels: `target` maps a position in
 // place to what the kernel reports beside it (the latent kernel: x = f^-1(z); the x-space kernel: T(x)) and returns lp.  This is the
@@ -237,24 +177,7 @@ __device__ __forceinline__ void ens_walk(const EnsArgs &a, const int row, const 
         const int jr = (int)(((uint64_t)u.m2 * (uint64_t)Nc) >> 24);
         const int j = __builtin_amdgcn_readfirstlane(members[(size_t)i * C + cbase + jr]);
         const unsigned need = set ? (unsigned)i + 1u : (unsigned)i;   // the partner's position after step t - 1 (set 0) or t (set 1)
-        if (need > 0) {
-            int good = 1;
-            if (lane == 0) {
-                unsigned polls = 0;
-                const long long t0 = wall_clock64();
-                while (__hip_atomic_load(&tags[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((++polls & 63) == 0 &&
-                        (wall_clock64() - t0 > ENS_SPIN_TICKS || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-                        __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        good = 0;
-                        break;
-                    }
-                }
-            }
-            if (!__builtin_amdgcn_readfirstlane(good)) return;   // a hand-off wait ran out: the call reports it
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
+        if (need > 0 && !ens_wait(tags, err, j, need, lane == 0)) return;   // a hand-off wait ran out: the call reports it
         float zj[2][U];
         load_row(need == 0 ? a.z_in + (size_t)j * D : a.hist_z + ((size_t)j * S + (need - 1)) * D, zj);
         const float zz = ens_zz(u.u1);
@@ -282,8 +205,7 @@ __device__ __forceinline__ void ens_walk(const EnsArgs &a, const int row, const 
             if (pos == 0) a.hist_lp[hr] = lp;
         }
         // publish: the wave's stores, then its step count (release: one fence for the whole wave, one relaxed sc1 store)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        if (lane == 0) __hip_atomic_store(&tags[row], (unsigned)i + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ens_publish(tags, row, (unsigned)i + 1u, lane == 0);
     }
     if (writer_lane) {
         store_row(a.z_out + (size_t)row * D, z);
@@ -534,21 +456,6 @@ static size_t ens_lds(const FlowShape &s) {
     return U >= 3 ? (size_t)3 * SOLO4_NF * 64 * sizeof(float) : (size_t)s.nets_params() * sizeof(float);
 }
 
-// resident 256-thread workgroups per CU: min(the occupancy API, 8, floor(800 / (SGPR granules + 16))) (MI355X_MICROARCH.md,
-// "Residency and cooperative launch").  The runtime does not report a kernel's SGPRs, so the SGPR term is taken at the ceiling a
-// wave can allocate (102 -> 112 in granules of 16): 6 per CU; the kernels use far fewer and their VGPRs bind first.
-constexpr int ENS_SGPR_CEIL = 112;
-static hipError_t ens_blocks_per_cu(const void *fn, size_t lds, int *out) {
-    hipError_t e = lds ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
-    if (e != hipSuccess) return e;
-    int n = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, lds);
-    if (e != hipSuccess) return e;
-    const int sg = 800 / (ENS_SGPR_CEIL + 16);
-    *out = n < 8 ? (n < sg ? n : sg) : (8 < sg ? 8 : sg);
-    return hipSuccess;
-}
-
 // X: the x-space kernel (no flow: a.s carries D and NT only, no LDS)
 template <int U, int LK, bool X>
 static hipError_t ens_launch_k(const EnsArgs &a, int num_cu, bool launch, int *max_walkers, hipStream_t st) {
@@ -622,17 +529,7 @@ static int ens_run(const EnsArgs &a, int num_cu, hipStream_t st, char *msg, size
         snprintf(msg, msg_len, "%s: %s", name, hipGetErrorString(e));
         return NNEST_E_HIP;
     }
-    int host_err = 0;
-    if ((e = hipMemcpyAsync(&host_err, a.work, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess ||
-        (e = hipStreamSynchronize(st)) != hipSuccess) {
-        snprintf(msg, msg_len, "%s: %s", name, hipGetErrorString(e));
-        return NNEST_E_HIP;
-    }
-    if (host_err) {
-        snprintf(msg, msg_len, "%s: a hand-off wait ran out (a workgroup was not resident?); the outputs are incomplete", name);
-        return NNEST_E_HIP;
-    }
-    return NNEST_OK;
+    return ens_finish(a.work, name, st, msg, msg_len);
 }
 
 int launch_ensemble(const FlowShape &s, const float *packed, const LikeSpec &like, const float *t_std, const float *t_mean, const float *lo,

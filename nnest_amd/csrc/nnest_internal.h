@@ -99,6 +99,11 @@ int launch_ensemble(const FlowShape &s, const float *packed, const LikeSpec &lik
                     const float *hi, const float *z_in, const double *lp_in, float *z_out, float *x_out, double *lp_out, float *hist_z,
                     float *hist_x, double *hist_lp, int *n_accept, int *work, int C, int S, uint32_t step0, uint64_t seed, int constrained,
                     double loglstar, int num_cu, hipStream_t st, char *msg, size_t msg_len);
+int ensemble_sizes(int C, int steps);   // nnest_abi.hip: the argument check of every ensemble entry (sets the error string)
+// the same move through the spline flow (nnest_spline_ensemble.hip; struct EnsArgs: ensemble_common.h)
+struct EnsArgs;
+hipError_t spline_ensemble_max_walkers(const SplArgs &q, int num_cu, int *out);
+int launch_spline_ensemble(const SplArgs &q, const EnsArgs &a, int num_cu, hipStream_t st, char *msg, size_t msg_len);
 hipError_t launch_ensemble_propose(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const float *z_cur,
                                    float *q, int rows, hipStream_t st);
 hipError_t launch_ensemble_accept(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const float *q,

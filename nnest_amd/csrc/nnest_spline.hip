@@ -14,6 +14,7 @@
 #include <string.h>
 #include <vector>
 
+#include "ensemble_common.h"
 #include "nnest_internal.h"
 #include "mh_common.h"
 
@@ -376,6 +377,45 @@ int nnest_spline_slice_steps(nnest_spline_t *h, const nnest_like_t *like, float 
     hipError_t e = launch_spline_slice(SplArgs{h->img, h->s}, a, flags, h->num_cu, (hipStream_t)stream);
     if (e == hipErrorInvalidConfiguration) return spline_fail(NNEST_E_UNSUPPORTED, "spline slice proposal: x_dim=%d hidden_dim=%d not instantiated", h->s.D, h->s.H);
     if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_slice: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+int nnest_spline_ensemble_max_walkers(nnest_spline_t *h, int like_id) {
+    if (!h || like_id < 0 || like_id >= NNEST_LIKE_COUNT) return -1;
+    int n = 0;
+    if (spline_ensemble_max_walkers(SplArgs{h->img, h->s}, h->num_cu, &n) != hipSuccess) return -1;
+    return n;
+}
+
+// (the checks that need no handle come first: they answer on a machine without a GPU, where no handle can exist)
+int nnest_spline_ensemble_steps(nnest_spline_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                                const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, float *z_out_dev,
+                                float *x_out_dev, double *lp_out_dev, float *hist_z_dev, float *hist_x_dev, double *hist_lp_dev,
+                                int *n_accept_dev, int *work_dev, int C, int steps, uint64_t step0, uint64_t seed, int constrained,
+                                double loglstar, void *stream) {
+    if (!like) return spline_fail(NNEST_E_ARG, "like is NULL");
+    if (like->id < 0 || like->id >= NNEST_LIKE_COUNT) return spline_fail(NNEST_E_ARG, "unknown likelihood id %d", like->id);
+    int rc = ensemble_sizes(C, steps);
+    if (rc) return rc;
+    if (!t_std_dev || !t_mean_dev || !z_in_dev || !z_out_dev || !x_out_dev || !lp_out_dev || !work_dev ||
+        (steps > 0 && (!hist_z_dev || !hist_x_dev || !hist_lp_dev)))
+        return spline_fail(NNEST_E_ARG, "NULL device buffer");
+    if (!lo_dev != !hi_dev) return spline_fail(NNEST_E_ARG, "lo_dev and hi_dev: both or neither");
+    if ((const void *)z_in_dev == (const void *)z_out_dev)
+        return spline_fail(NNEST_E_ARG, "z_in_dev must not be z_out_dev (partners read it during the launch)");
+    if (!h) return spline_fail(NNEST_E_ARG, "NULL handle");
+    EnsArgs a;
+    memset(&a, 0, sizeof(a));
+    if ((rc = scheck_like(like, h->s.D, &a.like))) return rc;
+    a.like.scale = 1.0f;
+    a.t_std = t_std_dev; a.t_mean = t_mean_dev; a.lo = lo_dev; a.hi = hi_dev;
+    a.z_in = z_in_dev; a.lp_in = lp_in_dev; a.z_out = z_out_dev; a.x_out = x_out_dev; a.lp_out = lp_out_dev;
+    a.hist_z = hist_z_dev; a.hist_x = hist_x_dev; a.hist_lp = hist_lp_dev; a.n_accept = n_accept_dev; a.work = work_dev;
+    a.C = C; a.S = steps; a.constrained = constrained ? 1 : 0; a.step0 = (uint32_t)step0; a.seed = seed; a.loglstar = loglstar;
+    char msg[400];
+    msg[0] = 0;
+    rc = launch_spline_ensemble(SplArgs{h->img, h->s}, a, h->num_cu, (hipStream_t)stream, msg, sizeof(msg));
+    if (rc) return spline_fail(rc, "%s", msg);
     return NNEST_OK;
 }
 

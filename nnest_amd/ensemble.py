@@ -34,7 +34,7 @@ class EnsembleSampler(Sampler):
     STRETCH_ONLY = ('kde', 'de', 'snooker')   # emcee moves the reference's `moves` dict can name and this build does not have
 
     def bootstrap(self, mcmc_steps, num_walkers, iters=1, thin=10, stats_interval=10, output_interval=None, initial_jitter=0.01,
-                  final_jitter=0.01, init_samples=None, moves=None, seed=None):
+                  final_jitter=0.01, init_samples=None, moves=None, seed=None, route=None):
         """ensemble.py:81-184: from a likelihood and a prior to training samples and a trained flow, without emcee or getdist.
 
         1. The stretch move in x space from `init_samples` (else `num_walkers` draws of the prior) for `mcmc_steps` steps, on
@@ -53,6 +53,8 @@ class EnsembleSampler(Sampler):
            BUILD-DEFINED STREAM: a torch generator seeded from `_next_seed()`.
 
         `seed` (not in the reference): the runs' and the thinning's seeds are seed, seed + 1, ...; None: `_next_seed()`.
+        `route` (not in the reference): forwarded to the latent-space runs of step 3 only (`_ensemble_sample`: None | 'fused' |
+        'rounds'); the x-space run of step 1 keeps its own choice.
         Returns the last training samples [n, D]; leaves samples, latent_samples and loglikes of the last latent
         run, as `run` does."""
         if moves is not None:
@@ -104,7 +106,7 @@ class EnsembleSampler(Sampler):
             self._install_transform(mean, std)
             self.trainer.train((training_samples - mean) / std, jitter=jitter)
             samples, latent_samples, derived_samples, loglikes, ncall = self._ensemble_sample(
-                mcmc_steps, num_walkers, stats_interval=stats_interval, output_interval=output_interval, seed=next_seed())
+                mcmc_steps, num_walkers, stats_interval=stats_interval, output_interval=output_interval, seed=next_seed(), route=route)
             self._chain_stats(samples, affine=(std, mean))
             samples = self.transform(samples)
             self.samples = np.concatenate((samples, derived_samples), axis=2)
@@ -127,9 +129,10 @@ class EnsembleSampler(Sampler):
         self._fused_like_id = None
 
     def run(self, mcmc_steps, num_walkers, training_samples, stats_interval=10, output_interval=None, initial_jitter=0.01,
-            final_jitter=0.01, init_samples=None):
+            final_jitter=0.01, init_samples=None, route=None):
         """ensemble.py:186-231.  As in the reference, `init_samples` is accepted and not forwarded; `stats_interval` is used with
-        chain_stats=True.  Sets samples [N, S, D + num_derived] (T(x), then the derived parameters: zeros, sampler.py:687),
+        chain_stats=True.  `route` (not in the reference) goes to the latent-space run (`_ensemble_sample`): None, or 'fused' /
+        'rounds' to pin one -- with the default spline flow the fused kernel runs on route='fused' only.  Sets samples [N, S, D + num_derived] (T(x), then the derived parameters: zeros, sampler.py:687),
         latent_samples [N, S, D] and loglikes [N, S] -- emcee's log_prob, the latent log target, not logL."""
         mean = np.mean(training_samples, axis=0)
         std = np.std(training_samples, axis=0)
@@ -137,7 +140,7 @@ class EnsembleSampler(Sampler):
         self._install_transform(mean, std)
         self.trainer.train(training_samples, jitter=initial_jitter)
         samples, latent_samples, derived_samples, loglikes, ncall = self._ensemble_sample(
-            mcmc_steps, num_walkers, stats_interval=stats_interval, output_interval=output_interval)
+            mcmc_steps, num_walkers, stats_interval=stats_interval, output_interval=output_interval, route=route)
         if self.chain_stats:
             self._log_chain_stats(samples, (std, mean), mcmc_steps, stats_interval, prefix_offset=0, min_step=1)
         samples = self.transform(samples)

@@ -1,7 +1,7 @@
 """emcee's stretch move in latent space for ANY flow and ANY likelihood (include/nnest_hip.h nnest_ensemble_rounds_*).
 
-BUILD-DEFINED STREAM, EMCEE'S MOVE: the definition is nnest_ensemble_steps's (the fused kernel of the default NVP shape,
-HipNVP.ensemble_steps), with the same draws, so both routes compute the same run.  Per half-step:
+BUILD-DEFINED STREAM, EMCEE'S MOVE: the definition is nnest_ensemble_steps's (the fused kernels of the default NVP shape and of
+the spline flow, `ensemble_steps` of HipNVP / HipSpline), with the same draws, so the routes compute the same run.  Per half-step:
 
 1. the propose kernel writes the moving set's proposals q, one row per walker in ascending walker order;
 2. the flow's own `inverse` maps them (NVP of any shape, spline, MAF, Cholesky, fast/slow);

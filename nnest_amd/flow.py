@@ -73,7 +73,7 @@ class _HipFlow(object):
     def _bind(self, family, **named):
         """self._sym: the entry points `<family>_<name>` that the library declares for this family (nnest_chol has neither
         inverse_loglike nor vjp: those names stay out), and the ones whose symbol does not follow the pattern, by name
-        (mh='nnest_mh_constrained_steps', slice='nnest_slice_steps'); a name left out is an entry point the family does not have"""
+        (mh='nnest_mh_constrained_steps', slice='nnest_slice_steps', ensemble='nnest_ensemble_steps'); a name left out is an entry point the family does not have"""
         family_syms = [(n, '%s_%s' % (family, n)) for n in self._FAMILY_ENTRIES]
         self._sym = {n: getattr(self._lib, sym) for n, sym in family_syms if sym in _lib.SIGNATURES}
         self._sym.update((n, getattr(self._lib, sym)) for n, sym in named.items())
@@ -320,6 +320,59 @@ class _HipFlow(object):
                                                         int(walker_offset), _lib.current_stream(self.device)))
         return dz
 
+    # whether Sampler._ensemble_sample takes the fused ensemble route for this family when the caller names none (route=None).  The
+    # spline's fused kernel is opt-in (route='fused'): DESIGN.md 3.7
+    ensemble_fused_by_default = False
+
+    def ensemble_max_walkers(self, like_id):
+        """the population the family's fused ensemble entry (nnest_ensemble_steps, nnest_spline_ensemble_steps) takes for this flow and
+        likelihood (every workgroup resident); 0 if its shape is not the fused route's, or the family has no such entry"""
+        fn = self._sym.get('ensemble_max_walkers')
+        if fn is None:
+            return 0
+        with torch.cuda.device(self.device):
+            return max(0, int(fn(self._h, int(like_id))))
+
+    def ensemble_steps(self, like_id, z, steps, t_std=None, t_mean=None, lo=None, hi=None, lp=None, loglstar=None, seed=0, step0=0,
+                       like_params=None):
+        """`steps` steps of emcee's stretch move in latent space, in ONE launch (the family's `ensemble` entry point:
+        nnest_ensemble_steps, nnest_spline_ensemble_steps; build-defined stream, emcee's move: include/nnest_hip.h has the definition).  z [C, D] float32 on the device: the walkers' start (read only); lp [C]
+        float64 or None (evaluated); the likelihood `like_id` sees T(x) = x * t_std + t_mean (per dimension; None: identity); lo / hi
+        [D]: the prior box on T(x) (None: no prior); loglstar: None = logL + log|det| + prior, else the hard constraint.  step0: the
+        global index of the first step (the draws depend on it, so a run cut into launches is the same run).  Returns z, x, lp (the
+        last state), hist_z, hist_x [C, steps, D], hist_lp [C, steps] and n_accept [C].  Raises NnestHipError (code
+        NNEST_E_UNSUPPORTED) when C exceeds ensemble_max_walkers, NotImplementedError for a family without a fused ensemble kernel
+        (its handle must not reach another family's): nnest_amd.ensemble_rounds runs those."""
+        fn = self._sym.get('ensemble')
+        if fn is None:
+            raise NotImplementedError('no fused ensemble kernel for %s: use nnest_amd.ensemble_rounds' % type(self).__name__)
+        dev = self.device
+        z = _as_dev_f32(z, dev).contiguous()
+        C, D, steps = z.shape[0], self.D, int(steps)
+        f32 = dict(dtype=torch.float32, device=dev)
+        vec = lambda v, fill: torch.full((D,), fill, **f32) if v is None else _as_dev_f32(np.asarray(v, np.float32).reshape(1, D), dev).reshape(D)
+        t_std, t_mean = vec(t_std, 1.0), vec(t_mean, 0.0)
+        lo_t = None if lo is None else vec(lo, 0.0)
+        hi_t = None if hi is None else vec(hi, 0.0)
+        if lp is not None:
+            lp = torch.as_tensor(lp, dtype=torch.float64).to(dev).contiguous()
+        out = dict(z=torch.empty(C, D, **f32), x=torch.empty(C, D, **f32), lp=torch.empty(C, dtype=torch.float64, device=dev),
+                   hist_z=torch.empty(C, steps, D, **f32), hist_x=torch.empty(C, steps, D, **f32),
+                   hist_lp=torch.empty(C, steps, dtype=torch.float64, device=dev), n_accept=torch.empty(C, dtype=torch.int32, device=dev))
+        words = self._lib.nnest_ensemble_work_words(C, steps)
+        if words < 0:
+            raise ValueError('ensemble_steps: %d walkers x %d steps: the work buffer is too large; launch fewer steps' % (C, steps))
+        work = torch.empty(words, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            lk = _lib.like_spec(like_id, 1.0, like_params)
+            _lib.check(fn(
+                self._h, ctypes.byref(lk), _lib.ptr(t_std), _lib.ptr(t_mean), _lib.ptr(lo_t), _lib.ptr(hi_t), _lib.ptr(z), _lib.ptr(lp),
+                _lib.ptr(out['z']), _lib.ptr(out['x']), _lib.ptr(out['lp']), _lib.ptr(out['hist_z']), _lib.ptr(out['hist_x']),
+                _lib.ptr(out['hist_lp']), _lib.ptr(out['n_accept']), _lib.ptr(work), C, steps, int(step0) & 0xFFFFFFFFFFFFFFFF,
+                int(seed) & 0xFFFFFFFFFFFFFFFF, 0 if loglstar is None else 1, 0.0 if loglstar is None else float(loglstar),
+                _lib.current_stream(dev)))
+        return out
+
     def mh_form_for(self, C, dynamic=False, lag=None, free=False, form=None, warm=0):
         """the K4 form (name) `mh_steps` runs for C walkers under this step rule -- asked of the library
         (nnest_mh_form_for), which knows the shapes each form is built for; None if the launch would be refused.  A caller
@@ -555,7 +608,8 @@ class HipNVP(_PaddedVectors, _HipFlow):
             raise ValueError("scale=%r: expected '', 'translate' or 'constant' (networks.py:330-332)" % (scale,))
         self.scale = scale
         self._lib = _lib.load()
-        self._bind('nnest_nvp', mh='nnest_mh_constrained_steps', slice='nnest_slice_steps')
+        self._bind('nnest_nvp', mh='nnest_mh_constrained_steps', slice='nnest_slice_steps', ensemble='nnest_ensemble_steps',
+                   ensemble_max_walkers='nnest_ensemble_max_walkers')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (_PaddedVectors)
         with torch.cuda.device(self.device):
@@ -566,51 +620,11 @@ class HipNVP(_PaddedVectors, _HipFlow):
                                                             torch.eye(self.D, device=self.device))
         self.load_packed(self.default_init(seed))
 
+    ensemble_fused_by_default = True
+
     def supports_fused_slice(self, C):
         """nnest_slice_steps runs the reference's default coupling shape only (hidden 16, 3 blocks, 1 layer, scale '')"""
         return super().supports_fused_slice(C) and self._Hn == 16 and self.B == 3 and self.L == 1 and self.scale == ''
-
-    def ensemble_max_walkers(self, like_id):
-        """the population nnest_ensemble_steps takes for this flow and likelihood (every workgroup resident); 0 if its shape is not
-        the fused route's"""
-        with torch.cuda.device(self.device):
-            return max(0, int(self._lib.nnest_ensemble_max_walkers(self._h, int(like_id))))
-
-    def ensemble_steps(self, like_id, z, steps, t_std=None, t_mean=None, lo=None, hi=None, lp=None, loglstar=None, seed=0, step0=0,
-                       like_params=None):
-        """`steps` steps of emcee's stretch move in latent space, in ONE launch (nnest_ensemble_steps; build-defined stream, emcee's
-        move: include/nnest_hip.h has the definition).  z [C, D] float32 on the device: the walkers' start (read only); lp [C]
-        float64 or None (evaluated); the likelihood `like_id` sees T(x) = x * t_std + t_mean (per dimension; None: identity); lo / hi
-        [D]: the prior box on T(x) (None: no prior); loglstar: None = logL + log|det| + prior, else the hard constraint.  step0: the
-        global index of the first step (the draws depend on it, so a run cut into launches is the same run).  Returns z, x, lp (the
-        last state), hist_z, hist_x [C, steps, D], hist_lp [C, steps] and n_accept [C].  Raises NnestHipError (code
-        NNEST_E_UNSUPPORTED) when C exceeds ensemble_max_walkers."""
-        dev = self.device
-        z = _as_dev_f32(z, dev).contiguous()
-        C, D, steps = z.shape[0], self.D, int(steps)
-        f32 = dict(dtype=torch.float32, device=dev)
-        vec = lambda v, fill: torch.full((D,), fill, **f32) if v is None else _as_dev_f32(np.asarray(v, np.float32).reshape(1, D), dev).reshape(D)
-        t_std, t_mean = vec(t_std, 1.0), vec(t_mean, 0.0)
-        lo_t = None if lo is None else vec(lo, 0.0)
-        hi_t = None if hi is None else vec(hi, 0.0)
-        if lp is not None:
-            lp = torch.as_tensor(lp, dtype=torch.float64).to(dev).contiguous()
-        out = dict(z=torch.empty(C, D, **f32), x=torch.empty(C, D, **f32), lp=torch.empty(C, dtype=torch.float64, device=dev),
-                   hist_z=torch.empty(C, steps, D, **f32), hist_x=torch.empty(C, steps, D, **f32),
-                   hist_lp=torch.empty(C, steps, dtype=torch.float64, device=dev), n_accept=torch.empty(C, dtype=torch.int32, device=dev))
-        words = self._lib.nnest_ensemble_work_words(C, steps)
-        if words < 0:
-            raise ValueError('ensemble_steps: %d walkers x %d steps: the work buffer is too large; launch fewer steps' % (C, steps))
-        work = torch.empty(words, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            lk = _lib.like_spec(like_id, 1.0, like_params)
-            _lib.check(self._lib.nnest_ensemble_steps(
-                self._h, ctypes.byref(lk), _lib.ptr(t_std), _lib.ptr(t_mean), _lib.ptr(lo_t), _lib.ptr(hi_t), _lib.ptr(z), _lib.ptr(lp),
-                _lib.ptr(out['z']), _lib.ptr(out['x']), _lib.ptr(out['lp']), _lib.ptr(out['hist_z']), _lib.ptr(out['hist_x']),
-                _lib.ptr(out['hist_lp']), _lib.ptr(out['n_accept']), _lib.ptr(work), C, steps, int(step0) & 0xFFFFFFFFFFFFFFFF,
-                int(seed) & 0xFFFFFFFFFFFFFFFF, 0 if loglstar is None else 1, 0.0 if loglstar is None else float(loglstar),
-                _lib.current_stream(dev)))
-        return out
 
     def _init_padding(self):
         """num_params and the packed layout are the USER's (hidden width H); the native vector has width _Hn"""

@@ -22,6 +22,7 @@ class HipMAF(HipNVP):
     steps, like the entries RealNVP's mask never reaches)."""
 
     epoch_chunk = 1 << 30   # Trainer.train hands the whole run to train_epochs (flow.train_epochs_host keeps the early-stopping books)
+    ensemble_fused_by_default = False   # (no fused ensemble kernel: `ensemble` is not bound below)
 
     def __init__(self, num_inputs, num_hidden=16, num_blocks=3, num_layers=1, device=None, seed=None):
         if not torch.cuda.is_available():

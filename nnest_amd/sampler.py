@@ -764,8 +764,9 @@ class Sampler(object):
                          moves=None, seed=None, chunk_steps=None, route=None):
         """emcee's EnsembleSampler with its default stretch move in latent space (sampler.py:632-724).  BUILD-DEFINED STREAM, EMCEE'S
         MOVE: include/nnest_hip.h nnest_ensemble_steps has the definition; parity with emcee is statistical.  The fused kernel runs
-        where it takes the flow, the likelihood and the population (route 'fused'), the round driver otherwise (route 'rounds';
-        `route` pins one, for tests).  The run is cut into launches of `chunk_steps` steps (default: by device memory); the cut does
+        where it takes the flow, the likelihood and the population (route 'fused'), the round driver otherwise (route 'rounds').
+        `route` pins one; None chooses 'fused' for the NVP where it is taken and 'rounds' for every other flow -- the spline flow's
+        fused kernel (nnest_spline_ensemble_steps) runs on route='fused' only, which raises ValueError where it is not taken.  The run is cut into launches of `chunk_steps` steps (default: by device memory); the cut does
         not change it.  Returns (samples [N, S, D] (x, before the transform), latent_samples [N, S, D], derived_samples [N, S, nd],
         loglikes [N, S] (the latent log target, emcee's log_prob), ncall)."""
         if moves is not None:
@@ -786,10 +787,11 @@ class Sampler(object):
         seed = self._next_seed() if seed is None else int(seed)
         affine = self._ensemble_affine()
         dlike = self._ensemble_device_like(affine)
-        fused_ok = (dlike is not None and getattr(netG, 'ensemble_steps', None) is not None
+        # the fused kernel takes the flow (its family binds an `ensemble` entry: HipNVP, HipSpline), the likelihood and the population
+        fused_ok = (dlike is not None and 'ensemble' in getattr(netG, '_sym', ())
                     and N <= netG.ensemble_max_walkers(dlike[0]))
-        if route is None:
-            route = 'fused' if fused_ok else 'rounds'
+        if route is None:   # (the spline's fused kernel is opt-in, route='fused': DESIGN.md 3.7)
+            route = 'fused' if fused_ok and getattr(netG, 'ensemble_fused_by_default', False) else 'rounds'
         elif route == 'fused' and not fused_ok:
             raise ValueError('ensemble: the fused route does not take this flow, likelihood or population')
         if chunk_steps is None:

@@ -32,7 +32,8 @@ class HipSpline(_PaddedVectors, _HipFlow):
         self.nl = self.D - self.nu
         self._lib = _lib.load()
         L = self._lib
-        self._bind('nnest_spline', mh='nnest_spline_mh_constrained_steps', slice='nnest_spline_slice_steps')
+        self._bind('nnest_spline', mh='nnest_spline_mh_constrained_steps', slice='nnest_spline_slice_steps',
+                   ensemble='nnest_spline_ensemble_steps', ensemble_max_walkers='nnest_spline_ensemble_max_walkers')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (flow._PaddedVectors: zero-padded, exact)
         with torch.cuda.device(self.device):
