@@ -365,6 +365,69 @@ int nnest_ensemble_x_steps(const nnest_like_t *like, const float *t_std_dev, con
                            const float *x_in_dev, const double *lp_in_dev, float *x_out_dev, float *tx_out_dev, double *lp_out_dev,
                            float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *work_dev, int C, int D, int steps, uint64_t step0,
                            uint64_t seed, int constrained, double loglstar, void *stream);
+/* MOVE MIXTURES: emcee's differential-evolution (DE) move beside the stretch move, one move chosen per step by weight, as
+ * emcee 3.1's EnsembleSampler.sample does with a weighted list of moves (RedBlueMove, DEMove).  BUILD-DEFINED STREAM, EMCEE'S MOVE:
+ * the definition below is RESTATED FROM EMCEE'S DOCUMENTED BEHAVIOUR (emcee is not available to check against); parity with emcee
+ * is statistical.  (All added within ABI 15.)  The split, the halves, lp, u1 u2 u3 and the 24-bit conventions are those of
+ * nnest_ensemble_steps above; in addition, at global step t:
+ *   move of step t: every walker takes the same move in both halves.  m_t = the top 24 bits of word 0 of Philox(key seed; counter
+ *      (0, t, 1, 4 << 28)) (the split draws from counter word 2 = 0 of that stream).  The step is a stretch step iff m_t < thr,
+ *      thr = floor(p_stretch 2^24) in float64 from the normalised weights, p_stretch = w_stretch / (w_stretch + w_de): thr = 2^24
+ *      is always the stretch move, 0 always the DE move.
+ *   stretch step: as above, bit for bit.
+ *   DE step, walker k of the moving set, Nc walkers in the other set (Nc >= 2, hence C >= 4: NNEST_E_ARG below):
+ *      partner a = member ja = (m2 Nc) >> 24, the stretch partner's draw and rule;
+ *      partner b = member jb = (mw (Nc - 1)) >> 24, then jb += (jb >= ja), mw the top 24 bits of word 3 of the walker's block: an
+ *        ordered pair of distinct members;
+ *      n = sqrt(-2 ln((mx + 1) / 2^24)) cos(2 pi my / 2^24) (float64), mx, my the top 24 bits of words 0, 1 of
+ *        Philox(key seed; counter (1, k, t, 3 << 28 | k >> 32));
+ *      gamma = (float)(g0 (1 + sigma n)) (float64 inside), g0 = de_gamma0 or 2.38 / sqrt(2 D) for 0, sigma = de_sigma or 1e-5 for 0
+ *        (emcee's defaults);
+ *      q = z_k + (z_b - z_a) gamma (float32, each operation rounded);  lnpdiff = lp(q) - lp(z_k) (float64, no factor);  the
+ *        walker moves to q iff lnpdiff > log u3.
+ * A run stays a function of the seed and the weights, not of its cut into launches or its route.  The snooker and KDE moves are not
+ * built.
+ * nnest_ens_moves_t: the weights (non-negative, finite, not both 0: NNEST_E_ARG otherwise) and the DE scale.  A NULL `moves` is the
+ *   stretch move alone: nnest_ensemble_steps, _x_steps, _max_walkers, _x_max_walkers and _rounds_propose / _accept ARE the entries
+ *   below with NULL.
+ * nnest_ensemble_moves_threshold: thr of these weights; -1 if they are refused.
+ * nnest_ensemble_moves_steps, nnest_ensemble_x_moves_steps: the fused entries above with one trailing `moves`.  A run with a DE step
+ *   in it (thr < 2^24) launches a kernel instantiation of its own, which waits for two partners per DE step through the same
+ *   hand-off, at the same step counts; its resident population is nnest_ensemble_moves_max_walkers / _x_moves_max_walkers (the same
+ *   formula on that instantiation), beyond which the call is refused with NNEST_E_UNSUPPORTED.  thr = 2^24 runs the stretch move's
+ *   own instantiation.
+ * nnest_ensemble_rounds_moves_propose / _accept: the round entries above with one trailing `moves` (the same for both calls).
+ * nnest_ensemble_fill_moves: the moves' draws of steps step0 .. step0 + steps - 1, through the kernels' own functions, for tests:
+ *   move_dev [steps] int32 (0 stretch, 1 DE), b_dev [steps, C] int32 (jb after the shift: an index into the other set's member
+ *   list) and gamma_dev [steps, C] float32, each or NULL.  work_dev: as nnest_ensemble_fill_noise wrote it for the same C, steps,
+ *   step0 and seed (jb depends on the size of the walker's other set).  moves NULL: every step a stretch step, the default scale. */
+typedef struct nnest_ens_moves {
+    float w_stretch, w_de;        /* the weights of the stretch and the DE move */
+    float de_gamma0, de_sigma;    /* the DE scale g0 and its relative spread sigma; 0: emcee's defaults */
+} nnest_ens_moves_t;
+int nnest_ensemble_moves_threshold(const nnest_ens_moves_t *moves);
+int nnest_ensemble_moves_max_walkers(nnest_nvp_t *nvp, int like_id, const nnest_ens_moves_t *moves);
+int nnest_ensemble_x_moves_max_walkers(int D, int like_id, const nnest_ens_moves_t *moves);
+int nnest_ensemble_moves_steps(nnest_nvp_t *nvp, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                               const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, float *z_out_dev,
+                               float *x_out_dev, double *lp_out_dev, float *hist_z_dev, float *hist_x_dev, double *hist_lp_dev,
+                               int *n_accept_dev, int *work_dev, int C, int steps, uint64_t step0, uint64_t seed, int constrained,
+                               double loglstar, void *stream, const nnest_ens_moves_t *moves);
+int nnest_ensemble_x_moves_steps(const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                                 const float *hi_dev, const float *x_in_dev, const double *lp_in_dev, float *x_out_dev, float *tx_out_dev,
+                                 double *lp_out_dev, float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *work_dev, int C, int D,
+                                 int steps, uint64_t step0, uint64_t seed, int constrained, double loglstar, void *stream,
+                                 const nnest_ens_moves_t *moves);
+int nnest_ensemble_rounds_moves_propose(const int *work_dev, int C, int steps, int D, int i, int half, uint64_t step0, uint64_t seed,
+                                        const float *z_cur_dev, float *q_dev, void *stream, const nnest_ens_moves_t *moves);
+int nnest_ensemble_rounds_moves_accept(const int *work_dev, int C, int steps, int D, int i, int half, uint64_t step0, uint64_t seed,
+                                       const float *q_dev, const float *x_dev, const float *ld_dev, const double *logl_dev,
+                                       const double *lprior_dev, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                                       const float *hi_dev, float *z_cur_dev, float *x_cur_dev, double *lp_cur_dev, float *hist_z_dev,
+                                       float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *acc_rows_dev, int constrained,
+                                       double loglstar, void *stream, const nnest_ens_moves_t *moves);
+int nnest_ensemble_fill_moves(const int *work_dev, int *move_dev, int *b_dev, float *gamma_dev, int C, int D, int steps, uint64_t step0,
+                              uint64_t seed, const nnest_ens_moves_t *moves, void *stream);
 /* size of sync_dev in 8-byte words for a launch of `steps` steps */
 int nnest_mh_sync_words(int steps);
 /* number of adaptation groups nnest_mh_constrained_steps uses for C walkers (size of scale_out_dev) */

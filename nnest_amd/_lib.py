@@ -62,6 +62,46 @@ def like_spec(like_id, scale, params=None):
     return lk
 
 
+class EnsMoves(ctypes.Structure):
+    """nnest_ens_moves_t (include/nnest_hip.h): the weights of the stretch and the DE move, the DE scale (0: emcee's defaults)"""
+    _fields_ = [('w_stretch', ctypes.c_float), ('w_de', ctypes.c_float), ('de_gamma0', ctypes.c_float), ('de_sigma', ctypes.c_float)]
+
+
+def ens_moves(moves, what='ensemble'):
+    """the reference's `moves` dict (nnest/ensemble.py:113-127: names case-insensitive, weights) as an EnsMoves: {'stretch': w, 'de': w}.
+    None stays None (the stretch move alone); an EnsMoves passes through.  'kde' and 'snooker' are emcee moves this build does not
+    have (NotImplementedError); any other name, a negative or non-finite weight and weights that are all 0 are ValueError."""
+    if moves is None or isinstance(moves, EnsMoves):
+        return moves
+    w = {'stretch': 0.0, 'de': 0.0}
+    for k, v in dict(moves).items():
+        name = str(k).lower()
+        if name in ('kde', 'snooker'):
+            raise NotImplementedError("%s: the '%s' move is not built (emcee's 'stretch' and 'de' moves are)" % (what, k))
+        if name not in w:
+            raise ValueError("%s: unknown move '%s'" % (what, k))
+        v = float(v)
+        if not (v >= 0.0 and v != float('inf')):
+            raise ValueError("%s: the weight of move '%s' is %r (finite and not negative)" % (what, k, v))
+        w[name] += v
+    if w['stretch'] + w['de'] <= 0.0:
+        raise ValueError('%s: the weights of the moves are all 0' % what)
+    return EnsMoves(w['stretch'], w['de'], 0.0, 0.0)
+
+
+def ens_moves_mix(mv, C=None, what='ensemble'):
+    """whether a run with these (parsed) moves has a DE step in it; with C, the DE move's own need: two partners in either set"""
+    mix = mv is not None and mv.w_de > 0.0
+    if mix and C is not None and C < 4:
+        raise ValueError('%s: %d walkers: the DE move needs two partners in either set (at least 4 walkers)' % (what, C))
+    return mix
+
+
+def moves_ref(mv):
+    """the `moves` argument of a C entry: a pointer to the struct, or NULL"""
+    return None if mv is None else ctypes.byref(mv)
+
+
 class TrainResult(ctypes.Structure):
     _fields_ = [('epochs_run', ctypes.c_int), ('best_epoch', ctypes.c_int),
                 ('best_validation_loss', ctypes.c_float), ('last_train_loss', ctypes.c_float),
@@ -165,6 +205,17 @@ SIGNATURES = {
     'nnest_ensemble_rounds_propose': [_vp, _i, _i, _i, _i, _i, _u64, _u64, _vp, _vp, _vp],
     'nnest_ensemble_rounds_accept': [_vp, _i, _i, _i, _i, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _i, _d, _vp],
+    'nnest_ensemble_moves_threshold': [_vp],
+    'nnest_ensemble_moves_max_walkers': [_vp, _i, _vp],
+    'nnest_ensemble_x_moves_max_walkers': [_i, _i, _vp],
+    'nnest_ensemble_moves_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _u64, _u64, _i, _d, _vp,
+                                   _vp],
+    'nnest_ensemble_x_moves_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _u64, _u64, _i, _d, _vp,
+                                     _vp],
+    'nnest_ensemble_rounds_moves_propose': [_vp, _i, _i, _i, _i, _i, _u64, _u64, _vp, _vp, _vp, _vp],
+    'nnest_ensemble_rounds_moves_accept': [_vp, _i, _i, _i, _i, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp],
+    'nnest_ensemble_fill_moves': [_vp, _vp, _vp, _vp, _i, _i, _i, _u64, _u64, _vp, _vp],
     'nnest_host_prior_consume': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  ctypes.c_longlong, _d, ctypes.c_longlong, ctypes.c_longlong, _d, _d, _i],
     'nnest_chain_stats_work_words': [_i, _i, _i],

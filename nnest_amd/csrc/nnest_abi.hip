@@ -7,6 +7,7 @@
 
 #include "nnest_internal.h"
 #include "mh_common.h"
+#include "ensemble_common.h"
 
 using namespace nnest;
 
@@ -409,7 +410,45 @@ int nnest::ensemble_sizes(int C, int steps) {
     if (nnest_ensemble_work_words(C, steps) < 0) return fail(NNEST_E_ARG, "ensemble: C=%d x steps=%d: the work buffer exceeds 2^31 words", C, steps);
     return NNEST_OK;
 }
+// the moves of a run from the caller's weights (NULL: the stretch move alone): the step threshold thr = floor(p_stretch 2^24), float64,
+// and the DE scale with emcee's defaults for 0.  A DE step needs two distinct partners in either set: C >= 4
+static int ens_resolve_moves(const nnest_ens_moves_t *m, int C, int D, EnsMoves *out) {
+    out->thr = ENS_THR_ALWAYS;
+    out->g0 = out->sigma = 0.f;
+    if (!m) return NNEST_OK;
+    const double ws = (double)m->w_stretch, wd = (double)m->w_de;
+    if (!(isfinite(ws) && isfinite(wd)) || ws < 0.0 || wd < 0.0 || ws + wd <= 0.0)
+        return fail(NNEST_E_ARG, "ensemble moves: weights stretch=%g de=%g (finite, >= 0, not both 0)", ws, wd);
+    if (!(isfinite(m->de_gamma0) && isfinite(m->de_sigma)) || m->de_gamma0 < 0.f || m->de_sigma < 0.f)
+        return fail(NNEST_E_ARG, "ensemble moves: de_gamma0=%g de_sigma=%g (finite, >= 0; 0: emcee's default)", (double)m->de_gamma0, (double)m->de_sigma);
+    if (wd > 0.0 && C < 4) return fail(NNEST_E_ARG, "ensemble moves: C=%d walkers: the DE move needs two partners in either set (C >= 4)", C);
+    if (D < 1) return fail(NNEST_E_ARG, "ensemble moves: D=%d", D);
+    out->thr = (uint32_t)floor(ws / (ws + wd) * 16777216.0);
+    out->g0 = m->de_gamma0 != 0.f ? m->de_gamma0 : (float)(2.38 / sqrt(2.0 * (double)D));
+    out->sigma = m->de_sigma != 0.f ? m->de_sigma : 1e-5f;
+    return NNEST_OK;
+}
+
 extern "C" {
+
+int nnest_ensemble_moves_threshold(const nnest_ens_moves_t *moves) {
+    EnsMoves mv;
+    if (ens_resolve_moves(moves, 4, 1, &mv)) return -1;
+    return (int)mv.thr;
+}
+
+int nnest_ensemble_fill_moves(const int *work_dev, int *move_dev, int *b_dev, float *gamma_dev, int C, int D, int steps, uint64_t step0,
+                              uint64_t seed, const nnest_ens_moves_t *moves, void *stream) {
+    int rc = ensemble_sizes(C, steps);
+    if (rc) return rc;
+    if (!work_dev) return fail(NNEST_E_ARG, "NULL work_dev");
+    if (C < 4) return fail(NNEST_E_ARG, "ensemble moves: C=%d walkers: the DE move needs two partners in either set (C >= 4)", C);
+    EnsMoves mv;
+    const nnest_ens_moves_t dflt = {1.f, 0.f, 0.f, 0.f};   // (no weights: every step a stretch step, the DE draws at emcee's default scale)
+    if ((rc = ens_resolve_moves(moves ? moves : &dflt, C, D, &mv))) return rc;
+    HIP_TRY(launch_ensemble_fill_moves(work_dev, move_dev, b_dev, gamma_dev, C, steps, (uint32_t)step0, seed, mv, (hipStream_t)stream));
+    return NNEST_OK;
+}
 
 int nnest_ensemble_fill_noise(int *work_dev, float *u_dev, int C, int steps, uint64_t step0, uint64_t seed, void *stream) {
     int rc = ensemble_sizes(C, steps);
@@ -419,23 +458,30 @@ int nnest_ensemble_fill_noise(int *work_dev, float *u_dev, int C, int steps, uin
     return NNEST_OK;
 }
 
-int nnest_ensemble_max_walkers(nnest_nvp_t *h, int like_id) {
+int nnest_ensemble_moves_max_walkers(nnest_nvp_t *h, int like_id, const nnest_ens_moves_t *moves) {
     if (!h || !ensemble_form_eligible(h->s)) return -1;
+    EnsMoves mv;
+    if (ens_resolve_moves(moves, 4, h->s.D, &mv)) return -1;
     int n = 0;
-    if (ensemble_max_walkers(h->s, like_id, h->num_cu, &n) != hipSuccess) return -1;
+    if (ensemble_max_walkers(h->s, like_id, mv, h->num_cu, &n) != hipSuccess) return -1;
     return n;
 }
 
-int nnest_ensemble_steps(nnest_nvp_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
-                         const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, float *z_out_dev, float *x_out_dev,
-                         double *lp_out_dev, float *hist_z_dev, float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *work_dev,
-                         int C, int steps, uint64_t step0, uint64_t seed, int constrained, double loglstar, void *stream) {
+int nnest_ensemble_max_walkers(nnest_nvp_t *h, int like_id) { return nnest_ensemble_moves_max_walkers(h, like_id, nullptr); }
+
+int nnest_ensemble_moves_steps(nnest_nvp_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                               const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, float *z_out_dev,
+                               float *x_out_dev, double *lp_out_dev, float *hist_z_dev, float *hist_x_dev, double *hist_lp_dev,
+                               int *n_accept_dev, int *work_dev, int C, int steps, uint64_t step0, uint64_t seed, int constrained,
+                               double loglstar, void *stream, const nnest_ens_moves_t *moves) {
     if (!h) return fail(NNEST_E_ARG, "NULL handle");
     int rc = ensemble_sizes(C, steps);
     if (rc) return rc;
     LikeSpec lk;
     if ((rc = check_like(like, h->s.D, &lk))) return rc;
     lk.scale = 1.0f;
+    EnsMoves mv;
+    if ((rc = ens_resolve_moves(moves, C, h->s.D, &mv))) return rc;
     if (!t_std_dev || !t_mean_dev || !z_in_dev || !z_out_dev || !x_out_dev || !lp_out_dev || !work_dev ||
         (steps > 0 && (!hist_z_dev || !hist_x_dev || !hist_lp_dev)))
         return fail(NNEST_E_ARG, "NULL device buffer");
@@ -447,9 +493,18 @@ int nnest_ensemble_steps(nnest_nvp_t *h, const nnest_like_t *like, const float *
     msg[0] = 0;
     rc = launch_ensemble(h->s, h->w, lk, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, z_out_dev, x_out_dev, lp_out_dev,
                          hist_z_dev, hist_x_dev, hist_lp_dev, n_accept_dev, work_dev, C, steps, (uint32_t)step0, seed, constrained ? 1 : 0,
-                         loglstar, h->num_cu, (hipStream_t)stream, msg, sizeof(msg));
+                         loglstar, mv, h->num_cu, (hipStream_t)stream, msg, sizeof(msg));
     if (rc) return fail(rc, "%s", msg);
     return NNEST_OK;
+}
+
+int nnest_ensemble_steps(nnest_nvp_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                         const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, float *z_out_dev, float *x_out_dev,
+                         double *lp_out_dev, float *hist_z_dev, float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *work_dev,
+                         int C, int steps, uint64_t step0, uint64_t seed, int constrained, double loglstar, void *stream) {
+    return nnest_ensemble_moves_steps(h, like, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, z_out_dev, x_out_dev, lp_out_dev,
+                                      hist_z_dev, hist_x_dev, hist_lp_dev, n_accept_dev, work_dev, C, steps, step0, seed, constrained,
+                                      loglstar, stream, nullptr);
 }
 
 static int ensemble_x_like(int D, int like_id) {
@@ -466,21 +521,27 @@ static int current_num_cu(int *num_cu) {
     return NNEST_OK;
 }
 
-int nnest_ensemble_x_max_walkers(int D, int like_id) {
+int nnest_ensemble_x_moves_max_walkers(int D, int like_id, const nnest_ens_moves_t *moves) {
     int n = 0, num_cu = 0;
-    if (ensemble_x_like(D, like_id) || current_num_cu(&num_cu)) return -1;
-    if (ensemble_x_max_walkers(D, like_id, num_cu, &n) != hipSuccess) return -1;
+    EnsMoves mv;
+    if (ensemble_x_like(D, like_id) || ens_resolve_moves(moves, 4, D, &mv) || current_num_cu(&num_cu)) return -1;
+    if (ensemble_x_max_walkers(D, like_id, mv, num_cu, &n) != hipSuccess) return -1;
     return n;
 }
 
-int nnest_ensemble_x_steps(const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev, const float *hi_dev,
-                           const float *x_in_dev, const double *lp_in_dev, float *x_out_dev, float *tx_out_dev, double *lp_out_dev,
-                           float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *work_dev, int C, int D, int steps, uint64_t step0,
-                           uint64_t seed, int constrained, double loglstar, void *stream) {
+int nnest_ensemble_x_max_walkers(int D, int like_id) { return nnest_ensemble_x_moves_max_walkers(D, like_id, nullptr); }
+
+int nnest_ensemble_x_moves_steps(const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                                 const float *hi_dev, const float *x_in_dev, const double *lp_in_dev, float *x_out_dev, float *tx_out_dev,
+                                 double *lp_out_dev, float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *work_dev, int C, int D,
+                                 int steps, uint64_t step0, uint64_t seed, int constrained, double loglstar, void *stream,
+                                 const nnest_ens_moves_t *moves) {
     if (!like) return fail(NNEST_E_ARG, "like is NULL");
     int rc = ensemble_x_like(D, like->id);
     if (rc) return rc;
     if ((rc = ensemble_sizes(C, steps))) return rc;
+    EnsMoves mv;
+    if ((rc = ens_resolve_moves(moves, C, D, &mv))) return rc;
     LikeSpec lk;
     if ((rc = check_like(like, D, &lk))) return rc;
     lk.scale = 1.0f;
@@ -494,20 +555,60 @@ int nnest_ensemble_x_steps(const nnest_like_t *like, const float *t_std_dev, con
     char msg[400];
     msg[0] = 0;
     rc = launch_ensemble_x(D, lk, t_std_dev, t_mean_dev, lo_dev, hi_dev, x_in_dev, lp_in_dev, x_out_dev, tx_out_dev, lp_out_dev, hist_x_dev,
-                           hist_lp_dev, n_accept_dev, work_dev, C, steps, (uint32_t)step0, seed, constrained ? 1 : 0, loglstar, num_cu,
+                           hist_lp_dev, n_accept_dev, work_dev, C, steps, (uint32_t)step0, seed, constrained ? 1 : 0, loglstar, mv, num_cu,
                            (hipStream_t)stream, msg, sizeof(msg));
     if (rc) return fail(rc, "%s", msg);
     return NNEST_OK;
 }
 
-int nnest_ensemble_rounds_propose(const int *work_dev, int C, int steps, int D, int i, int half, uint64_t step0, uint64_t seed,
-                                  const float *z_cur_dev, float *q_dev, void *stream) {
+int nnest_ensemble_x_steps(const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev, const float *hi_dev,
+                           const float *x_in_dev, const double *lp_in_dev, float *x_out_dev, float *tx_out_dev, double *lp_out_dev,
+                           float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *work_dev, int C, int D, int steps, uint64_t step0,
+                           uint64_t seed, int constrained, double loglstar, void *stream) {
+    return nnest_ensemble_x_moves_steps(like, t_std_dev, t_mean_dev, lo_dev, hi_dev, x_in_dev, lp_in_dev, x_out_dev, tx_out_dev, lp_out_dev,
+                                        hist_x_dev, hist_lp_dev, n_accept_dev, work_dev, C, D, steps, step0, seed, constrained, loglstar,
+                                        stream, nullptr);
+}
+
+int nnest_ensemble_rounds_moves_propose(const int *work_dev, int C, int steps, int D, int i, int half, uint64_t step0, uint64_t seed,
+                                        const float *z_cur_dev, float *q_dev, void *stream, const nnest_ens_moves_t *moves) {
     int rc = ensemble_sizes(C, steps);
     if (rc) return rc;
+    EnsMoves mv;
+    if ((rc = ens_resolve_moves(moves, C, D, &mv))) return rc;
     if (!work_dev || !z_cur_dev || !q_dev) return fail(NNEST_E_ARG, "NULL device buffer");
     if (D < 1 || i < 0 || i >= steps || (half != 0 && half != 1)) return fail(NNEST_E_ARG, "D=%d i=%d (steps %d) half=%d", D, i, steps, half);
     const int rows = half ? C / 2 : (C + 1) / 2;
-    HIP_TRY(launch_ensemble_propose(work_dev, C, steps, D, i, half, (uint32_t)step0, seed, z_cur_dev, q_dev, rows, (hipStream_t)stream));
+    HIP_TRY(launch_ensemble_propose(work_dev, C, steps, D, i, half, (uint32_t)step0, seed, mv, z_cur_dev, q_dev, rows, (hipStream_t)stream));
+    return NNEST_OK;
+}
+
+int nnest_ensemble_rounds_propose(const int *work_dev, int C, int steps, int D, int i, int half, uint64_t step0, uint64_t seed,
+                                  const float *z_cur_dev, float *q_dev, void *stream) {
+    return nnest_ensemble_rounds_moves_propose(work_dev, C, steps, D, i, half, step0, seed, z_cur_dev, q_dev, stream, nullptr);
+}
+
+int nnest_ensemble_rounds_moves_accept(const int *work_dev, int C, int steps, int D, int i, int half, uint64_t step0, uint64_t seed,
+                                       const float *q_dev, const float *x_dev, const float *ld_dev, const double *logl_dev,
+                                       const double *lprior_dev, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                                       const float *hi_dev, float *z_cur_dev, float *x_cur_dev, double *lp_cur_dev, float *hist_z_dev,
+                                       float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *acc_rows_dev, int constrained,
+                                       double loglstar, void *stream, const nnest_ens_moves_t *moves) {
+    int rc = ensemble_sizes(C, steps);
+    if (rc) return rc;
+    EnsMoves mv;
+    if ((rc = ens_resolve_moves(moves, C, D, &mv))) return rc;
+    if (D < 1 || half < -1 || half > 1 || (half >= 0 && (i < 0 || i >= steps))) return fail(NNEST_E_ARG, "D=%d i=%d (steps %d) half=%d", D, i, steps, half);
+    if (!work_dev || !q_dev || !x_dev || !ld_dev || !logl_dev || !z_cur_dev || !x_cur_dev || !lp_cur_dev ||
+        (half >= 0 && (!hist_z_dev || !hist_x_dev || !hist_lp_dev)))
+        return fail(NNEST_E_ARG, "NULL device buffer");
+    if (!lo_dev != !hi_dev) return fail(NNEST_E_ARG, "lo_dev and hi_dev: both or neither");
+    if (lo_dev && !lprior_dev && (!t_std_dev || !t_mean_dev)) return fail(NNEST_E_ARG, "the box needs t_std_dev and t_mean_dev");
+    const int rows = half < 0 ? C : half ? C / 2 : (C + 1) / 2;
+    HIP_TRY(launch_ensemble_accept(work_dev, C, steps, D, half < 0 ? 0 : i, half, (uint32_t)step0, seed, mv, q_dev, x_dev, ld_dev, logl_dev,
+                                   lprior_dev, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_cur_dev, x_cur_dev, lp_cur_dev, hist_z_dev,
+                                   hist_x_dev, hist_lp_dev, n_accept_dev, acc_rows_dev, constrained ? 1 : 0, loglstar, rows,
+                                   (hipStream_t)stream));
     return NNEST_OK;
 }
 
@@ -517,20 +618,9 @@ int nnest_ensemble_rounds_accept(const int *work_dev, int C, int steps, int D, i
                                  const float *hi_dev, float *z_cur_dev, float *x_cur_dev, double *lp_cur_dev, float *hist_z_dev,
                                  float *hist_x_dev, double *hist_lp_dev, int *n_accept_dev, int *acc_rows_dev, int constrained,
                                  double loglstar, void *stream) {
-    int rc = ensemble_sizes(C, steps);
-    if (rc) return rc;
-    if (D < 1 || half < -1 || half > 1 || (half >= 0 && (i < 0 || i >= steps))) return fail(NNEST_E_ARG, "D=%d i=%d (steps %d) half=%d", D, i, steps, half);
-    if (!work_dev || !q_dev || !x_dev || !ld_dev || !logl_dev || !z_cur_dev || !x_cur_dev || !lp_cur_dev ||
-        (half >= 0 && (!hist_z_dev || !hist_x_dev || !hist_lp_dev)))
-        return fail(NNEST_E_ARG, "NULL device buffer");
-    if (!lo_dev != !hi_dev) return fail(NNEST_E_ARG, "lo_dev and hi_dev: both or neither");
-    if (lo_dev && !lprior_dev && (!t_std_dev || !t_mean_dev)) return fail(NNEST_E_ARG, "the box needs t_std_dev and t_mean_dev");
-    const int rows = half < 0 ? C : half ? C / 2 : (C + 1) / 2;
-    HIP_TRY(launch_ensemble_accept(work_dev, C, steps, D, half < 0 ? 0 : i, half, (uint32_t)step0, seed, q_dev, x_dev, ld_dev, logl_dev,
-                                   lprior_dev, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_cur_dev, x_cur_dev, lp_cur_dev, hist_z_dev,
-                                   hist_x_dev, hist_lp_dev, n_accept_dev, acc_rows_dev, constrained ? 1 : 0, loglstar, rows,
-                                   (hipStream_t)stream));
-    return NNEST_OK;
+    return nnest_ensemble_rounds_moves_accept(work_dev, C, steps, D, i, half, step0, seed, q_dev, x_dev, ld_dev, logl_dev, lprior_dev,
+                                              t_std_dev, t_mean_dev, lo_dev, hi_dev, z_cur_dev, x_cur_dev, lp_cur_dev, hist_z_dev,
+                                              hist_x_dev, hist_lp_dev, n_accept_dev, acc_rows_dev, constrained, loglstar, stream, nullptr);
 }
 
 int nnest_mh_form_for(const nnest_nvp_t *h, int C, int flags) {

@@ -37,6 +37,11 @@
 // with f = identity and ld = 0.  It is a third caller of the same pieces, not a second protocol: the walk through the steps of a
 // launch -- partner, hand-off, proposal, accept, history, publish -- is ens_walk, which the two fused kernels call with their
 // position -> lp functor; the round kernels run it with an identity map for the flow.
+//
+// MOVE MIXTURES (include/nnest_hip.h nnest_ensemble_moves_steps): with weights on emcee's differential-evolution move
+// a step is either a stretch step or a DE step, q = z_k + (z_b - z_a) gamma with two partners of the other set and no factor in
+// lnpdiff; the move of a step is a draw of (seed, t).  The fused kernels know it in their MIX instantiations only (the others are
+// the stretch move's code as it was), the round kernels through the EnsMoves block of their arguments.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -122,6 +127,23 @@ __global__ void ensemble_fill_u_kernel(float *__restrict__ u, int C, int S, uint
     }
 }
 
+// the moves' draws, exported for the checker through the kernels' own functions: move [S] (ENS_MOVE_*), jb [S][C] (the DE step's
+// second partner: its index in the other set's member list, after the shift past ja) and gamma [S][C].  work: the split of these steps
+__global__ void ensemble_fill_moves_kernel(const int *__restrict__ work, int *__restrict__ move, int *__restrict__ jb,
+                                           float *__restrict__ gamma, int C, int S, uint32_t step0, uint64_t seed, EnsMoves mv) {
+    const long n = (long)S * C;
+    const int n0 = (C + 1) / 2;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        const int k = (int)(e % C), i = (int)(e / C);
+        const uint32_t t = step0 + (uint32_t)i;
+        if (k == 0 && move) move[i] = ens_move_of_step(seed, t, mv.thr);
+        const int set = work[ens_split_off(C) + e];
+        const EnsDe de = ens_de_draws(seed, (uint64_t)k, t, ens_uniforms(seed, (uint64_t)k, t), set ? n0 : C - n0, mv);
+        if (jb) jb[e] = de.jb;
+        if (gamma) gamma[e] = de.gamma;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // FUSED route: one walker per wave (the solo layout of nnest_solo.hip: lane = 32 n + 16 h + p holds dims 2U p + 2u + c; the four
 // (n, h) rows hold copies), four walkers per workgroup.
@@ -130,8 +152,10 @@ __global__ void ensemble_fill_u_kernel(float *__restrict__ u, int C, int S, uint
 // The walk of one walker (one wave) through the S steps of a launch, shared by the two fused kernels: `target` maps a position in
 // place to what the kernel reports beside it (the latent kernel: x = f^-1(z); the x-space kernel: T(x)) and returns lp.  This is the
 // only hand-off protocol in the file.  XH: the mapped rows have a history of their own (hist_x); without it the positions' history
-// (hist_z) is the run's, and x_out may be NULL.
-template <int U, bool XH, class Target>
+// (hist_z) is the run's, and x_out may be NULL.  MIX: the run mixes the stretch move with the DE move (a.mv; the move of a step is
+// wave-uniform): a DE step waits for two partners instead of one, through the same ens_wait, at the same `need`; without MIX the
+// code is the stretch move's alone.
+template <int U, bool XH, bool MIX, class Target>
 __device__ __forceinline__ void ens_walk(const EnsArgs &a, const int row, const int lane, Target &&target) {
     const int D = a.s.D, S = a.S, C = a.C;
     const int pos = lane & 15;
@@ -177,20 +201,39 @@ __device__ __forceinline__ void ens_walk(const EnsArgs &a, const int row, const 
         const int jr = (int)(((uint64_t)u.m2 * (uint64_t)Nc) >> 24);
         const int j = __builtin_amdgcn_readfirstlane(members[(size_t)i * C + cbase + jr]);
         const unsigned need = set ? (unsigned)i + 1u : (unsigned)i;   // the partner's position after step t - 1 (set 0) or t (set 1)
-        if (need > 0 && !ens_wait(tags, err, j, need, lane == 0)) return;   // a hand-off wait ran out: the call reports it
-        float zj[2][U];
-        load_row(need == 0 ? a.z_in + (size_t)j * D : a.hist_z + ((size_t)j * S + (need - 1)) * D, zj);
-        const float zz = ens_zz(u.u1);
-        float q[2][U], xq[2][U];
+        int move = ENS_MOVE_STRETCH;
+        if constexpr (MIX) move = __builtin_amdgcn_readfirstlane(ens_move_of_step(a.seed, t, a.mv.thr));
+        // (the partner's row is written out at each load: behind a lambda or a helper the compiler spills more SGPRs in the MIX = false
+        // instantiations than it did before there was a MIX)
+        float zj[2][U], q[2][U], xq[2][U];
+        float zz = 1.0f;
+        if (MIX && move == ENS_MOVE_DE) {
+            // partners a = j and b: lanes 0 and 1 poll one tag each, one acquire, then the two rows (the difference as b's is loaded)
+            const EnsDe de = ens_de_draws(a.seed, (uint64_t)row, t, u, Nc, a.mv);
+            const int jb = __builtin_amdgcn_readfirstlane(members[(size_t)i * C + cbase + de.jb]);
+            if (need > 0 && !ens_wait(tags, err, lane == 0 ? j : jb, need, lane < 2)) return;
+            load_row(need == 0 ? a.z_in + (size_t)j * D : a.hist_z + ((size_t)j * S + (need - 1)) * D, zj);
+            load_row(need == 0 ? a.z_in + (size_t)jb * D : a.hist_z + ((size_t)jb * S + (need - 1)) * D, q);
+#pragma unroll
+            for (int uu = 0; uu < U; ++uu)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) q[c][uu] = ens_de_propose(z[c][uu], zj[c][uu], q[c][uu], de.gamma);
+        } else {
+            if (need > 0 && !ens_wait(tags, err, j, need, lane == 0)) return;   // a hand-off wait ran out: the call reports it
+            load_row(need == 0 ? a.z_in + (size_t)j * D : a.hist_z + ((size_t)j * S + (need - 1)) * D, zj);
+            zz = ens_zz(u.u1);
+#pragma unroll
+            for (int uu = 0; uu < U; ++uu)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) q[c][uu] = ens_propose(zj[c][uu], z[c][uu], zz);
+        }
 #pragma unroll
         for (int uu = 0; uu < U; ++uu)
 #pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                q[c][uu] = ens_propose(zj[c][uu], z[c][uu], zz);
-                xq[c][uu] = q[c][uu];
-            }
+            for (int c = 0; c < 2; ++c) xq[c][uu] = q[c][uu];
         const double lpq = target(xq);
-        if (ens_accept(lpq, lp, zz, u.u3, D)) {
+        // (the stretch factor (D - 1) log zz; a DE step has none)
+        if ((MIX && move == ENS_MOVE_DE) ? ens_accept_factor(lpq, lp, 0.0, u.u3) : ens_accept(lpq, lp, zz, u.u3, D)) {
 #pragma unroll
             for (int uu = 0; uu < U; ++uu)
 #pragma unroll
@@ -217,7 +260,7 @@ __device__ __forceinline__ void ens_walk(const EnsArgs &a, const int row, const 
     }
 }
 
-template <int U, int LK>
+template <int U, int LK, bool MIX>
 __global__ void __launch_bounds__(256) ensemble_kernel(EnsArgs a) {
     extern __shared__ __attribute__((aligned(16))) float wlds[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -291,13 +334,13 @@ __global__ void __launch_bounds__(256) ensemble_kernel(EnsArgs a) {
         const double logl = solo_loglike<U, LK>(like, D, lane, tx);
         return ens_target(logl, ld, in_prior, a.constrained, a.loglstar);
     };
-    ens_walk<U, true>(a, row, lane, target);
+    ens_walk<U, true, MIX>(a, row, lane, target);
 }
 
 // The x-space run: the same walk with f = identity and ld = 0, so lp(x) = safe logL(T(x)) + prior.  No flow, hence no
 // weights and no LDS; t_std / t_mean NULL: T = identity (x * 1 + 0 in float32, the value the round route computes with an identity
 // flow).  The mapped row is T(x): x_out (optional) receives it.
-template <int U, int LK>
+template <int U, int LK, bool MIX>
 __global__ void __launch_bounds__(256) ensemble_x_kernel(EnsArgs a) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int D = a.s.D;
@@ -332,7 +375,7 @@ __global__ void __launch_bounds__(256) ensemble_x_kernel(EnsArgs a) {
         const double logl = solo_loglike<U, LK>(like, D, lane, xs);
         return ens_target(logl, 0.f, in_prior, a.constrained, a.loglstar);
     };
-    ens_walk<U, false>(a, row, lane, target);
+    ens_walk<U, false, MIX>(a, row, lane, target);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -342,6 +385,7 @@ struct EnsRoundArgs {
     int C, S, D, i, half;   // chunk step i (global step step0 + i); half 0 / 1 (-1: the initial evaluation, rows = walkers)
     uint32_t step0;
     uint64_t seed;
+    EnsMoves mv;
 };
 
 __device__ __forceinline__ int ens_row_walker(const EnsRoundArgs &a, int r) {
@@ -358,7 +402,16 @@ __global__ void __launch_bounds__(256) ensemble_propose_kernel(EnsRoundArgs a, c
     const int Nc = a.half ? n0 : C - n0, cbase = a.half ? 0 : n0;
     const EnsU u = ens_uniforms(a.seed, (uint64_t)k, a.step0 + (uint32_t)a.i);
     const int jr = (int)(((uint64_t)u.m2 * (uint64_t)Nc) >> 24);
-    const int j = a.work[ens_split_off(C) + (size_t)a.S * C + (size_t)a.i * C + cbase + jr];
+    const int *others = a.work + ens_split_off(C) + (size_t)a.S * C + (size_t)a.i * C + cbase;
+    const int j = others[jr];
+    const uint32_t t = a.step0 + (uint32_t)a.i;
+    if (ens_move_of_step(a.seed, t, a.mv.thr) == ENS_MOVE_DE) {
+        const EnsDe de = ens_de_draws(a.seed, (uint64_t)k, t, u, Nc, a.mv);
+        const int jb = others[de.jb];
+        for (int d = lane; d < D; d += 64)
+            q[(size_t)r * D + d] = ens_de_propose(z_cur[(size_t)k * D + d], z_cur[(size_t)j * D + d], z_cur[(size_t)jb * D + d], de.gamma);
+        return;
+    }
     const float zz = ens_zz(u.u1);
     for (int d = lane; d < D; d += 64) q[(size_t)r * D + d] = ens_propose(z_cur[(size_t)j * D + d], z_cur[(size_t)k * D + d], zz);
 }
@@ -402,7 +455,9 @@ __global__ void __launch_bounds__(256) ensemble_accept_kernel(EnsRoundArgs a, En
         moved = true;
     } else {
         const EnsU u = ens_uniforms(a.seed, (uint64_t)k, a.step0 + (uint32_t)a.i);
-        moved = ens_accept(lp_new, b.lp_cur[k], ens_zz(u.u1), u.u3, D);
+        moved = ens_move_of_step(a.seed, a.step0 + (uint32_t)a.i, a.mv.thr) == ENS_MOVE_DE
+                    ? ens_accept_factor(lp_new, b.lp_cur[k], 0.0, u.u3)
+                    : ens_accept(lp_new, b.lp_cur[k], ens_zz(u.u1), u.u3, D);
     }
     const float *qr = b.q + (size_t)r * D;
     if (moved) {
@@ -449,6 +504,13 @@ hipError_t launch_ensemble_split(int *work, float *u, int C, int S, uint32_t ste
     return e;
 }
 
+hipError_t launch_ensemble_fill_moves(const int *work, int *move, int *jb, float *gamma, int C, int S, uint32_t step0, uint64_t seed,
+                                      const EnsMoves &mv, hipStream_t st) {
+    if (S <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ensemble_fill_moves_kernel, dim3(256), dim3(256), 0, st, work, move, jb, gamma, C, S, step0, seed, mv);
+    return hipGetLastError();
+}
+
 bool ensemble_form_eligible(const FlowShape &s) { return slice_form_eligible(s); }
 
 template <int U, int LK>
@@ -456,32 +518,39 @@ static size_t ens_lds(const FlowShape &s) {
     return U >= 3 ? (size_t)3 * SOLO4_NF * 64 * sizeof(float) : (size_t)s.nets_params() * sizeof(float);
 }
 
-// X: the x-space kernel (no flow: a.s carries D and NT only, no LDS)
-template <int U, int LK, bool X>
+// X: the x-space kernel (no flow: a.s carries D and NT only, no LDS); MIX: the instantiation that knows the DE move
+template <int U, int LK, bool X, bool MIX>
 static hipError_t ens_launch_k(const EnsArgs &a, int num_cu, bool launch, int *max_walkers, hipStream_t st) {
-    const void *fn = X ? reinterpret_cast<const void *>(ensemble_x_kernel<U, LK>) : reinterpret_cast<const void *>(ensemble_kernel<U, LK>);
+    const void *fn = X ? reinterpret_cast<const void *>(ensemble_x_kernel<U, LK, MIX>) : reinterpret_cast<const void *>(ensemble_kernel<U, LK, MIX>);
     const size_t lds = X ? 0 : ens_lds<U, LK>(a.s);
     int per_cu = 0;
     hipError_t e = ens_blocks_per_cu(fn, lds, &per_cu);
     if (e != hipSuccess) return e;
     *max_walkers = 4 * per_cu * num_cu;
     if (!launch) return hipSuccess;
-    if constexpr (X) hipLaunchKernelGGL((ensemble_x_kernel<U, LK>), dim3((a.C + 3) / 4), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((ensemble_kernel<U, LK>), dim3((a.C + 3) / 4), dim3(256), lds, st, a);
+    if constexpr (X) hipLaunchKernelGGL((ensemble_x_kernel<U, LK, MIX>), dim3((a.C + 3) / 4), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((ensemble_kernel<U, LK, MIX>), dim3((a.C + 3) / 4), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 
 // launch (when `launch` and C fits) or only size: *max_walkers = the resident population of the instantiation the call would run
-template <bool X>
-static hipError_t ens_dispatch(const EnsArgs &a, int num_cu, bool launch, int *max_walkers, hipStream_t st) {
+template <bool X, bool MIX>
+static hipError_t ens_dispatch_m(const EnsArgs &a, int num_cu, bool launch, int *max_walkers, hipStream_t st) {
     const bool rosen = a.like.id == NNEST_LIKE_ROSENBROCK;
     switch (a.s.NT) {
-        case 1: return rosen ? ens_launch_k<1, NNEST_LIKE_ROSENBROCK, X>(a, num_cu, launch, max_walkers, st) : ens_launch_k<1, -1, X>(a, num_cu, launch, max_walkers, st);
-        case 2: return rosen ? ens_launch_k<2, NNEST_LIKE_ROSENBROCK, X>(a, num_cu, launch, max_walkers, st) : ens_launch_k<2, -1, X>(a, num_cu, launch, max_walkers, st);
-        case 3: return rosen ? ens_launch_k<3, NNEST_LIKE_ROSENBROCK, X>(a, num_cu, launch, max_walkers, st) : ens_launch_k<3, -1, X>(a, num_cu, launch, max_walkers, st);
-        case 4: return rosen ? ens_launch_k<4, NNEST_LIKE_ROSENBROCK, X>(a, num_cu, launch, max_walkers, st) : ens_launch_k<4, -1, X>(a, num_cu, launch, max_walkers, st);
+        case 1: return rosen ? ens_launch_k<1, NNEST_LIKE_ROSENBROCK, X, MIX>(a, num_cu, launch, max_walkers, st) : ens_launch_k<1, -1, X, MIX>(a, num_cu, launch, max_walkers, st);
+        case 2: return rosen ? ens_launch_k<2, NNEST_LIKE_ROSENBROCK, X, MIX>(a, num_cu, launch, max_walkers, st) : ens_launch_k<2, -1, X, MIX>(a, num_cu, launch, max_walkers, st);
+        case 3: return rosen ? ens_launch_k<3, NNEST_LIKE_ROSENBROCK, X, MIX>(a, num_cu, launch, max_walkers, st) : ens_launch_k<3, -1, X, MIX>(a, num_cu, launch, max_walkers, st);
+        case 4: return rosen ? ens_launch_k<4, NNEST_LIKE_ROSENBROCK, X, MIX>(a, num_cu, launch, max_walkers, st) : ens_launch_k<4, -1, X, MIX>(a, num_cu, launch, max_walkers, st);
     }
     return hipErrorInvalidConfiguration;
+}
+
+// a run with a DE step in it (a.mv.thr < 2^24) takes the MIX instantiation; every other run the stretch move's own, as before
+template <bool X>
+static hipError_t ens_dispatch(const EnsArgs &a, int num_cu, bool launch, int *max_walkers, hipStream_t st) {
+    return a.mv.thr < ENS_THR_ALWAYS ? ens_dispatch_m<X, true>(a, num_cu, launch, max_walkers, st)
+                                     : ens_dispatch_m<X, false>(a, num_cu, launch, max_walkers, st);
 }
 
 // the shape the x-space kernel reads: D and the solo layout's U = NT
@@ -493,17 +562,19 @@ static FlowShape ens_x_shape(int D) {
     return s;
 }
 
-hipError_t ensemble_max_walkers(const FlowShape &s, int like_id, int num_cu, int *out) {
+hipError_t ensemble_max_walkers(const FlowShape &s, int like_id, const EnsMoves &mv, int num_cu, int *out) {
     EnsArgs a;
     memset(&a, 0, sizeof(a));
+    a.mv = mv;
     a.s = s;
     a.like.id = like_id;
     return ens_dispatch<false>(a, num_cu, false, out, 0);
 }
 
-hipError_t ensemble_x_max_walkers(int D, int like_id, int num_cu, int *out) {
+hipError_t ensemble_x_max_walkers(int D, int like_id, const EnsMoves &mv, int num_cu, int *out) {
     EnsArgs a;
     memset(&a, 0, sizeof(a));
+    a.mv = mv;
     a.s = ens_x_shape(D);
     a.like.id = like_id;
     return ens_dispatch<true>(a, num_cu, false, out, 0);
@@ -535,9 +606,10 @@ static int ens_run(const EnsArgs &a, int num_cu, hipStream_t st, char *msg, size
 int launch_ensemble(const FlowShape &s, const float *packed, const LikeSpec &like, const float *t_std, const float *t_mean, const float *lo,
                     const float *hi, const float *z_in, const double *lp_in, float *z_out, float *x_out, double *lp_out, float *hist_z,
                     float *hist_x, double *hist_lp, int *n_accept, int *work, int C, int S, uint32_t step0, uint64_t seed, int constrained,
-                    double loglstar, int num_cu, hipStream_t st, char *msg, size_t msg_len) {
+                    double loglstar, const EnsMoves &mv, int num_cu, hipStream_t st, char *msg, size_t msg_len) {
     EnsArgs a;
     memset(&a, 0, sizeof(a));
+    a.mv = mv;
     a.s = s; a.packed = packed; a.like = like; a.t_std = t_std; a.t_mean = t_mean; a.lo = lo; a.hi = hi;
     a.z_in = z_in; a.lp_in = lp_in; a.z_out = z_out; a.x_out = x_out; a.lp_out = lp_out;
     a.hist_z = hist_z; a.hist_x = hist_x; a.hist_lp = hist_lp; a.n_accept = n_accept; a.work = work;
@@ -548,10 +620,11 @@ int launch_ensemble(const FlowShape &s, const float *packed, const LikeSpec &lik
 // the x-space run: the positions are x (EnsArgs' z slots), the mapped row is T(x) (tx_out, optional)
 int launch_ensemble_x(int D, const LikeSpec &like, const float *t_std, const float *t_mean, const float *lo, const float *hi,
                       const float *x_in, const double *lp_in, float *x_out, float *tx_out, double *lp_out, float *hist_x, double *hist_lp,
-                      int *n_accept, int *work, int C, int S, uint32_t step0, uint64_t seed, int constrained, double loglstar, int num_cu,
-                      hipStream_t st, char *msg, size_t msg_len) {
+                      int *n_accept, int *work, int C, int S, uint32_t step0, uint64_t seed, int constrained, double loglstar,
+                      const EnsMoves &mv, int num_cu, hipStream_t st, char *msg, size_t msg_len) {
     EnsArgs a;
     memset(&a, 0, sizeof(a));
+    a.mv = mv;
     a.s = ens_x_shape(D); a.like = like; a.t_std = t_std; a.t_mean = t_mean; a.lo = lo; a.hi = hi;
     a.z_in = x_in; a.lp_in = lp_in; a.z_out = x_out; a.x_out = tx_out; a.lp_out = lp_out;
     a.hist_z = hist_x; a.hist_lp = hist_lp; a.n_accept = n_accept; a.work = work;
@@ -559,21 +632,21 @@ int launch_ensemble_x(int D, const LikeSpec &like, const float *t_std, const flo
     return ens_run<true>(a, num_cu, st, msg, msg_len);
 }
 
-hipError_t launch_ensemble_propose(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const float *z_cur,
-                                   float *q, int rows, hipStream_t st) {
+hipError_t launch_ensemble_propose(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const EnsMoves &mv,
+                                   const float *z_cur, float *q, int rows, hipStream_t st) {
     if (rows <= 0) return hipSuccess;
-    EnsRoundArgs a = {work, C, S, D, i, half, step0, seed};
+    EnsRoundArgs a = {work, C, S, D, i, half, step0, seed, mv};
     hipLaunchKernelGGL(ensemble_propose_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, a, z_cur, q, rows);
     return hipGetLastError();
 }
 
-hipError_t launch_ensemble_accept(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const float *q,
-                                  const float *x, const float *ld, const double *logl, const double *lprior, const float *t_std,
+hipError_t launch_ensemble_accept(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const EnsMoves &mv,
+                                  const float *q, const float *x, const float *ld, const double *logl, const double *lprior, const float *t_std,
                                   const float *t_mean, const float *lo, const float *hi, float *z_cur, float *x_cur, double *lp_cur,
                                   float *hist_z, float *hist_x, double *hist_lp, int *n_accept, int *acc_rows, int constrained,
                                   double loglstar, int rows, hipStream_t st) {
     if (rows <= 0) return hipSuccess;
-    EnsRoundArgs a = {work, C, S, D, i, half, step0, seed};
+    EnsRoundArgs a = {work, C, S, D, i, half, step0, seed, mv};
     EnsAcceptArgs b = {q, x, ld, logl, lprior, t_std, t_mean, lo, hi, z_cur, x_cur, lp_cur, hist_z, hist_x, hist_lp, n_accept, acc_rows,
                        constrained, loglstar};
     hipLaunchKernelGGL(ensemble_accept_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, a, b, rows);

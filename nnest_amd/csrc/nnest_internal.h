@@ -88,26 +88,29 @@ hipError_t launch_slice_fill_noise(float *dz, int steps, int C, int D, uint64_t 
 // ensemble sampler, emcee's stretch move in latent space (nnest_ensemble.hip)
 size_t ensemble_work_words(int C, int S);
 bool ensemble_form_eligible(const FlowShape &s);
-hipError_t ensemble_max_walkers(const FlowShape &s, int like_id, int num_cu, int *out);
-hipError_t ensemble_x_max_walkers(int D, int like_id, int num_cu, int *out);
+struct EnsMoves;   // ensemble_common.h: the moves of a run, resolved (the stretch / DE threshold, the DE scale)
+hipError_t ensemble_max_walkers(const FlowShape &s, int like_id, const EnsMoves &mv, int num_cu, int *out);
+hipError_t ensemble_x_max_walkers(int D, int like_id, const EnsMoves &mv, int num_cu, int *out);
+hipError_t launch_ensemble_fill_moves(const int *work, int *move, int *jb, float *gamma, int C, int S, uint32_t step0, uint64_t seed,
+                                      const EnsMoves &mv, hipStream_t st);
 int launch_ensemble_x(int D, const LikeSpec &like, const float *t_std, const float *t_mean, const float *lo, const float *hi,
                       const float *x_in, const double *lp_in, float *x_out, float *tx_out, double *lp_out, float *hist_x, double *hist_lp,
-                      int *n_accept, int *work, int C, int S, uint32_t step0, uint64_t seed, int constrained, double loglstar, int num_cu,
-                      hipStream_t st, char *msg, size_t msg_len);
+                      int *n_accept, int *work, int C, int S, uint32_t step0, uint64_t seed, int constrained, double loglstar,
+                      const EnsMoves &mv, int num_cu, hipStream_t st, char *msg, size_t msg_len);
 hipError_t launch_ensemble_split(int *work, float *u, int C, int S, uint32_t step0, uint64_t seed, hipStream_t st);
 int launch_ensemble(const FlowShape &s, const float *packed, const LikeSpec &like, const float *t_std, const float *t_mean, const float *lo,
                     const float *hi, const float *z_in, const double *lp_in, float *z_out, float *x_out, double *lp_out, float *hist_z,
                     float *hist_x, double *hist_lp, int *n_accept, int *work, int C, int S, uint32_t step0, uint64_t seed, int constrained,
-                    double loglstar, int num_cu, hipStream_t st, char *msg, size_t msg_len);
+                    double loglstar, const EnsMoves &mv, int num_cu, hipStream_t st, char *msg, size_t msg_len);
 int ensemble_sizes(int C, int steps);   // nnest_abi.hip: the argument check of every ensemble entry (sets the error string)
 // the same move through the spline flow (nnest_spline_ensemble.hip; struct EnsArgs: ensemble_common.h)
 struct EnsArgs;
 hipError_t spline_ensemble_max_walkers(const SplArgs &q, int num_cu, int *out);
 int launch_spline_ensemble(const SplArgs &q, const EnsArgs &a, int num_cu, hipStream_t st, char *msg, size_t msg_len);
-hipError_t launch_ensemble_propose(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const float *z_cur,
-                                   float *q, int rows, hipStream_t st);
-hipError_t launch_ensemble_accept(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const float *q,
-                                  const float *x, const float *ld, const double *logl, const double *lprior, const float *t_std,
+hipError_t launch_ensemble_propose(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const EnsMoves &mv,
+                                   const float *z_cur, float *q, int rows, hipStream_t st);
+hipError_t launch_ensemble_accept(const int *work, int C, int S, int D, int i, int half, uint32_t step0, uint64_t seed, const EnsMoves &mv,
+                                  const float *q, const float *x, const float *ld, const double *logl, const double *lprior, const float *t_std,
                                   const float *t_mean, const float *lo, const float *hi, float *z_cur, float *x_cur, double *lp_cur,
                                   float *hist_z, float *hist_x, double *hist_lp, int *n_accept, int *acc_rows, int constrained,
                                   double loglstar, int rows, hipStream_t st);

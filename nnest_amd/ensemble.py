@@ -31,10 +31,12 @@ class EnsembleSampler(Sampler):
                                               param_names=param_names, chain_stats=chain_stats)
         self.sampler = 'ensemble'
 
-    STRETCH_ONLY = ('kde', 'de', 'snooker')   # emcee moves the reference's `moves` dict can name and this build does not have
+    # emcee moves the reference's `moves` dict can name and bootstrap's x-space run refuses ('de' is built for the latent-space runs:
+    # `latent_moves`)
+    STRETCH_ONLY = ('kde', 'de', 'snooker')
 
     def bootstrap(self, mcmc_steps, num_walkers, iters=1, thin=10, stats_interval=10, output_interval=None, initial_jitter=0.01,
-                  final_jitter=0.01, init_samples=None, moves=None, seed=None, route=None):
+                  final_jitter=0.01, init_samples=None, moves=None, seed=None, route=None, latent_moves=None):
         """ensemble.py:81-184: from a likelihood and a prior to training samples and a trained flow, without emcee or getdist.
 
         1. The stretch move in x space from `init_samples` (else `num_walkers` draws of the prior) for `mcmc_steps` steps, on
@@ -55,6 +57,9 @@ class EnsembleSampler(Sampler):
         `seed` (not in the reference): the runs' and the thinning's seeds are seed, seed + 1, ...; None: `_next_seed()`.
         `route` (not in the reference): forwarded to the latent-space runs of step 3 only (`_ensemble_sample`: None | 'fused' |
         'rounds'); the x-space run of step 1 keeps its own choice.
+        `latent_moves` (not in the reference): the moves of the latent-space runs of step 3, {'stretch': w, 'de': w}
+        (`_ensemble_sample`: emcee's differential-evolution move beside the stretch move, one move per step by weight); the
+        x-space run of step 1 keeps the stretch move, and `moves` its check above.
         Returns the last training samples [n, D]; leaves samples, latent_samples and loglikes of the last latent
         run, as `run` does."""
         if moves is not None:
@@ -64,6 +69,8 @@ class EnsembleSampler(Sampler):
                                               "'stretch' move is)" % k)
                 if str(k).lower() != 'stretch':
                     raise ValueError("EnsembleSampler.bootstrap: unknown move '%s'" % k)
+        from . import _lib
+        latent_moves = _lib.ens_moves(latent_moves, 'EnsembleSampler.bootstrap')   # (refused before the x-space run, not after it)
         if init_samples is None:
             if self.sample_prior is None:
                 raise ValueError('Prior does not have sample method')
@@ -106,7 +113,8 @@ class EnsembleSampler(Sampler):
             self._install_transform(mean, std)
             self.trainer.train((training_samples - mean) / std, jitter=jitter)
             samples, latent_samples, derived_samples, loglikes, ncall = self._ensemble_sample(
-                mcmc_steps, num_walkers, stats_interval=stats_interval, output_interval=output_interval, seed=next_seed(), route=route)
+                mcmc_steps, num_walkers, stats_interval=stats_interval, output_interval=output_interval, seed=next_seed(), route=route,
+                moves=latent_moves)
             self._chain_stats(samples, affine=(std, mean))
             samples = self.transform(samples)
             self.samples = np.concatenate((samples, derived_samples), axis=2)
@@ -129,10 +137,12 @@ class EnsembleSampler(Sampler):
         self._fused_like_id = None
 
     def run(self, mcmc_steps, num_walkers, training_samples, stats_interval=10, output_interval=None, initial_jitter=0.01,
-            final_jitter=0.01, init_samples=None, route=None):
+            final_jitter=0.01, init_samples=None, route=None, moves=None):
         """ensemble.py:186-231.  As in the reference, `init_samples` is accepted and not forwarded; `stats_interval` is used with
         chain_stats=True.  `route` (not in the reference) goes to the latent-space run (`_ensemble_sample`): None, or 'fused' /
-        'rounds' to pin one -- with the default spline flow the fused kernel runs on route='fused' only.  Sets samples [N, S, D + num_derived] (T(x), then the derived parameters: zeros, sampler.py:687),
+        'rounds' to pin one -- with the default spline flow the fused kernel runs on route='fused' only.  `moves` (not in the
+        reference's `run`) goes there too: {'stretch': w, 'de': w}, emcee's differential-evolution move beside the stretch move, one
+        move per step by weight; with a DE step the spline flow runs the round route (route='fused': ValueError).  Sets samples [N, S, D + num_derived] (T(x), then the derived parameters: zeros, sampler.py:687),
         latent_samples [N, S, D] and loglikes [N, S] -- emcee's log_prob, the latent log target, not logL."""
         mean = np.mean(training_samples, axis=0)
         std = np.std(training_samples, axis=0)
@@ -140,7 +150,7 @@ class EnsembleSampler(Sampler):
         self._install_transform(mean, std)
         self.trainer.train(training_samples, jitter=initial_jitter)
         samples, latent_samples, derived_samples, loglikes, ncall = self._ensemble_sample(
-            mcmc_steps, num_walkers, stats_interval=stats_interval, output_interval=output_interval, route=route)
+            mcmc_steps, num_walkers, stats_interval=stats_interval, output_interval=output_interval, route=route, moves=moves)
         if self.chain_stats:
             self._log_chain_stats(samples, (std, mean), mcmc_steps, stats_interval, prefix_offset=0, min_step=1)
         samples = self.transform(samples)

@@ -8,6 +8,10 @@ the spline flow, `ensemble_steps` of HipNVP / HipSpline), with the same draws, s
 3. the likelihood runs on those rows: the device likelihood kernel (nnest_loglike) on T(x) for a known id, or else the caller's
    callables on the host;
 4. the accept kernel applies the rule and writes the step's history rows.
+
+With `moves` the run mixes the stretch move with emcee's differential-evolution move, one move per step by weight
+(nnest_ensemble_rounds_moves_*; the definition: include/nnest_hip.h nnest_ensemble_moves_steps): on a DE step the propose kernel
+writes the DE proposal and the accept kernel applies the rule without the stretch factor.
 """
 import numpy as np
 import torch
@@ -38,6 +42,27 @@ def fill_noise(C, steps, seed=0, step0=0, device=None):
     return inds, u
 
 
+def fill_moves(C, D, steps, moves=None, seed=0, step0=0, device=None):
+    """the moves' draws of steps step0 .. step0 + steps - 1 (nnest_ensemble_fill_moves), exported for the checker beside
+    fill_noise's: move [steps] int32 (0: a stretch step, 1: a DE step), jb [steps, C] int32 (the DE step's second partner, an
+    index into the other set's members in ascending walker order, already shifted past the first partner's) and gamma
+    [steps, C] float32 (the DE scale).  moves: {'stretch': w, 'de': w} (None: every step a stretch step)"""
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    lib = _lib.load()
+    mv = _lib.ens_moves(moves, 'fill_moves')
+    seed, step0 = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0) & 0xFFFFFFFFFFFFFFFF
+    with torch.cuda.device(dev):
+        sp = _lib.current_stream(dev)
+        work = work_buffer(lib, C, steps, dev)
+        _lib.check(lib.nnest_ensemble_fill_noise(_lib.ptr(work), None, int(C), int(steps), step0, seed, sp))
+        move = torch.empty(steps, dtype=torch.int32, device=dev)
+        jb = torch.empty(steps, C, dtype=torch.int32, device=dev)
+        gamma = torch.empty(steps, C, dtype=torch.float32, device=dev)
+        _lib.check(lib.nnest_ensemble_fill_moves(_lib.ptr(work), _lib.ptr(move), _lib.ptr(jb), _lib.ptr(gamma), int(C), int(D), int(steps),
+                                                 step0, seed, _lib.moves_ref(mv), sp))
+    return move, jb, gamma
+
+
 def _dev_vec(v, D, dev):
     return None if v is None else torch.as_tensor(np.asarray(v, np.float32).reshape(D)).to(dev)
 
@@ -60,8 +85,9 @@ class EnsembleState(object):
 
 
 def ensemble_rounds(flow, z, steps, state=None, lp=None, t_std=None, t_mean=None, lo=None, hi=None, like_id=None, like_params=None,
-                    loglike=None, prior=None, num_derived=0, init_derived=None, loglstar=None, seed=0, step0=0):
-    """`steps` steps of the stretch move, global steps step0 .. step0 + steps - 1.
+                    loglike=None, prior=None, num_derived=0, init_derived=None, loglstar=None, seed=0, step0=0, moves=None):
+    """`steps` steps of the stretch move (moves=None), or of a mixture {'stretch': w, 'de': w} with emcee's DE move (_lib.ens_moves),
+    global steps step0 .. step0 + steps - 1.
 
     flow: any object with inverse(z) -> (x, log|det dx/dz|) on the device and a `device`.
     Start: `state` (an EnsembleState from the previous call), else z [C, D] with lp [C] (None: evaluated here, C likelihood calls).
@@ -77,6 +103,7 @@ def ensemble_rounds(flow, z, steps, state=None, lp=None, t_std=None, t_mean=None
         raise ValueError('ensemble_rounds: give exactly one of loglike (host callable) and like_id (device likelihood)')
     dev = flow.device
     lib = _lib.load()
+    mv = _lib.ens_moves(moves, 'ensemble_rounds')
     steps, nd = int(steps), int(num_derived)
     constrained = 0 if loglstar is None else 1
     star = 0.0 if loglstar is None else float(loglstar)
@@ -90,6 +117,11 @@ def ensemble_rounds(flow, z, steps, state=None, lp=None, t_std=None, t_mean=None
         else:
             z = _flow._as_dev_f32(z, dev).contiguous()
             C, D = z.shape
+        _lib.ens_moves_mix(mv, C, 'ensemble_rounds')
+        # (moves=None: the stretch move's own entries, which are the moves entries with NULL)
+        propose_fn = lib.nnest_ensemble_rounds_propose if mv is None else lib.nnest_ensemble_rounds_moves_propose
+        accept_fn = lib.nnest_ensemble_rounds_accept if mv is None else lib.nnest_ensemble_rounds_moves_accept
+        mv_arg = () if mv is None else (_lib.moves_ref(mv),)
         if like_id is not None:
             t_std_t = _dev_vec(np.ones(D) if t_std is None else t_std, D, dev)
             t_mean_t = _dev_vec(np.zeros(D) if t_mean is None else t_mean, D, dev)
@@ -115,11 +147,11 @@ def ensemble_rounds(flow, z, steps, state=None, lp=None, t_std=None, t_mean=None
             return (x, ld, torch.from_numpy(lv).to(dev), torch.from_numpy(np.ascontiguousarray(lpr)).to(dev), dv)
 
         def accept(i, half, q, x, ld, logl, lprior, st, hist, acc_rows=None):
-            _lib.check(lib.nnest_ensemble_rounds_accept(
+            _lib.check(accept_fn(
                 _lib.ptr(work), C, steps, D, i, half, step0, seed, _lib.ptr(q), _lib.ptr(x), _lib.ptr(ld), _lib.ptr(logl),
                 _lib.ptr(lprior), _lib.ptr(t_std_t), _lib.ptr(t_mean_t), _lib.ptr(lo_t), _lib.ptr(hi_t), _lib.ptr(st.z), _lib.ptr(st.x),
                 _lib.ptr(st.lp), _lib.ptr(hist.get('hist_z')), _lib.ptr(hist.get('hist_x')), _lib.ptr(hist.get('hist_lp')),
-                _lib.ptr(st.n_accept), _lib.ptr(acc_rows), constrained, star, sp))
+                _lib.ptr(st.n_accept), _lib.ptr(acc_rows), constrained, star, sp, *mv_arg))
 
         if state is None:
             st = EnsembleState(z.clone(), torch.empty_like(z), torch.empty(C, dtype=torch.float64, device=dev),
@@ -149,8 +181,7 @@ def ensemble_rounds(flow, z, steps, state=None, lp=None, t_std=None, t_mean=None
         for i in range(steps):
             for half in (0, 1):
                 n = n0 if half == 0 else C - n0
-                _lib.check(lib.nnest_ensemble_rounds_propose(_lib.ptr(work), C, steps, D, i, half, step0, seed, _lib.ptr(st.z),
-                                                             _lib.ptr(q), sp))
+                _lib.check(propose_fn(_lib.ptr(work), C, steps, D, i, half, step0, seed, _lib.ptr(st.z), _lib.ptr(q), sp, *mv_arg))
                 x, ld, logl, lprior, dv = evaluate(q, n)
                 accept(i, half, q, x, ld, logl, lprior, st, hist, acc)
                 if acc is not None:   # the derived parameters of the accepted proposals (host)

@@ -324,17 +324,21 @@ class _HipFlow(object):
     # spline's fused kernel is opt-in (route='fused'): DESIGN.md 3.7
     ensemble_fused_by_default = False
 
-    def ensemble_max_walkers(self, like_id):
+    def ensemble_max_walkers(self, like_id, moves=None):
         """the population the family's fused ensemble entry (nnest_ensemble_steps, nnest_spline_ensemble_steps) takes for this flow and
-        likelihood (every workgroup resident); 0 if its shape is not the fused route's, or the family has no such entry"""
-        fn = self._sym.get('ensemble_max_walkers')
+        likelihood (every workgroup resident); 0 if its shape is not the fused route's, or the family has no such entry.  moves
+        (_lib.ens_moves): with a DE step in the run, the population of the entry that knows the move (nnest_ensemble_moves_steps:
+        another kernel instantiation); 0 for a family without one"""
+        mv = _lib.ens_moves(moves)
+        mix = _lib.ens_moves_mix(mv)
+        fn = self._sym.get('ensemble_moves_max_walkers' if mix else 'ensemble_max_walkers')
         if fn is None:
             return 0
         with torch.cuda.device(self.device):
-            return max(0, int(fn(self._h, int(like_id))))
+            return max(0, int(fn(self._h, int(like_id), _lib.moves_ref(mv)) if mix else fn(self._h, int(like_id))))
 
     def ensemble_steps(self, like_id, z, steps, t_std=None, t_mean=None, lo=None, hi=None, lp=None, loglstar=None, seed=0, step0=0,
-                       like_params=None):
+                       like_params=None, moves=None):
         """`steps` steps of emcee's stretch move in latent space, in ONE launch (the family's `ensemble` entry point:
         nnest_ensemble_steps, nnest_spline_ensemble_steps; build-defined stream, emcee's move: include/nnest_hip.h has the definition).  z [C, D] float32 on the device: the walkers' start (read only); lp [C]
         float64 or None (evaluated); the likelihood `like_id` sees T(x) = x * t_std + t_mean (per dimension; None: identity); lo / hi
@@ -342,13 +346,22 @@ class _HipFlow(object):
         global index of the first step (the draws depend on it, so a run cut into launches is the same run).  Returns z, x, lp (the
         last state), hist_z, hist_x [C, steps, D], hist_lp [C, steps] and n_accept [C].  Raises NnestHipError (code
         NNEST_E_UNSUPPORTED) when C exceeds ensemble_max_walkers, NotImplementedError for a family without a fused ensemble kernel
-        (its handle must not reach another family's): nnest_amd.ensemble_rounds runs those."""
-        fn = self._sym.get('ensemble')
+        (its handle must not reach another family's): nnest_amd.ensemble_rounds runs those.  moves: None (the stretch move alone, the
+        family's `ensemble` entry), or {'stretch': w, 'de': w} (_lib.ens_moves): a mixture with emcee's DE move, one move per step by
+        weight, through the family's `ensemble_moves` entry (nnest_ensemble_moves_steps; with a DE step in the run
+        NotImplementedError for a family without one: the spline flow)."""
+        mv = _lib.ens_moves(moves, 'ensemble_steps')
+        mix = _lib.ens_moves_mix(mv)
+        fn = None if mv is None else self._sym.get('ensemble_moves')
+        if fn is None and not mix:   # (weights on the stretch move alone are that run: the family's `ensemble` entry takes it)
+            fn, mv = self._sym.get('ensemble'), None
         if fn is None:
-            raise NotImplementedError('no fused ensemble kernel for %s: use nnest_amd.ensemble_rounds' % type(self).__name__)
+            raise NotImplementedError('no fused ensemble kernel for %s%s: use nnest_amd.ensemble_rounds' % (
+                type(self).__name__, ' with a move other than the stretch move' if mix else ''))
         dev = self.device
         z = _as_dev_f32(z, dev).contiguous()
         C, D, steps = z.shape[0], self.D, int(steps)
+        _lib.ens_moves_mix(mv, C, 'ensemble_steps')
         f32 = dict(dtype=torch.float32, device=dev)
         vec = lambda v, fill: torch.full((D,), fill, **f32) if v is None else _as_dev_f32(np.asarray(v, np.float32).reshape(1, D), dev).reshape(D)
         t_std, t_mean = vec(t_std, 1.0), vec(t_mean, 0.0)
@@ -370,7 +383,7 @@ class _HipFlow(object):
                 _lib.ptr(out['z']), _lib.ptr(out['x']), _lib.ptr(out['lp']), _lib.ptr(out['hist_z']), _lib.ptr(out['hist_x']),
                 _lib.ptr(out['hist_lp']), _lib.ptr(out['n_accept']), _lib.ptr(work), C, steps, int(step0) & 0xFFFFFFFFFFFFFFFF,
                 int(seed) & 0xFFFFFFFFFFFFFFFF, 0 if loglstar is None else 1, 0.0 if loglstar is None else float(loglstar),
-                _lib.current_stream(dev)))
+                _lib.current_stream(dev), *(() if mv is None else (_lib.moves_ref(mv),))))
         return out
 
     def mh_form_for(self, C, dynamic=False, lag=None, free=False, form=None, warm=0):
@@ -609,7 +622,8 @@ class HipNVP(_PaddedVectors, _HipFlow):
         self.scale = scale
         self._lib = _lib.load()
         self._bind('nnest_nvp', mh='nnest_mh_constrained_steps', slice='nnest_slice_steps', ensemble='nnest_ensemble_steps',
-                   ensemble_max_walkers='nnest_ensemble_max_walkers')
+                   ensemble_max_walkers='nnest_ensemble_max_walkers', ensemble_moves='nnest_ensemble_moves_steps',
+                   ensemble_moves_max_walkers='nnest_ensemble_moves_max_walkers')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (_PaddedVectors)
         with torch.cuda.device(self.device):
@@ -818,24 +832,30 @@ def loglike(like_id, x_unit, like_scale, device=None, like_params=None):
     return out
 
 
-def ensemble_x_max_walkers(D, like_id, device=None):
-    """the population ensemble_x_steps takes for x_dim D and this likelihood (every workgroup resident); 0 where it takes none"""
+def ensemble_x_max_walkers(D, like_id, device=None, moves=None):
+    """the population ensemble_x_steps takes for x_dim D, this likelihood and these moves (every workgroup resident); 0 where it
+    takes none"""
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    mv = _lib.ens_moves(moves)
     with torch.cuda.device(device):
-        return max(0, int(_lib.load().nnest_ensemble_x_max_walkers(int(D), int(like_id))))
+        if mv is None:
+            return max(0, int(_lib.load().nnest_ensemble_x_max_walkers(int(D), int(like_id))))
+        return max(0, int(_lib.load().nnest_ensemble_x_moves_max_walkers(int(D), int(like_id), _lib.moves_ref(mv))))
 
 
 def ensemble_x_steps(like_id, x, steps, t_std=None, t_mean=None, lo=None, hi=None, lp=None, loglstar=None, seed=0, step0=0,
-                     like_params=None, device=None):
+                     like_params=None, device=None, moves=None):
     """`steps` steps of emcee's stretch move in X space, in ONE launch (nnest_ensemble_x_steps: HipNVP.ensemble_steps' run with
     the identity for the flow; build-defined stream, emcee's move).  x [C, D] float32: the walkers' start (read only); lp [C]
     float64 or None (evaluated); the target is lp(x) = logL(T(x)) + prior with T(x) = x * t_std + t_mean (both None: the identity),
     the prior the box lo / hi [D] on T(x) (None: none); loglstar: None, or the hard constraint.  Returns x, tx (= T(x)), lp (the
     last state), hist_x [C, steps, D], hist_lp [C, steps] and n_accept [C].  Raises NnestHipError (code NNEST_E_UNSUPPORTED) when C
-    exceeds ensemble_x_max_walkers."""
+    exceeds ensemble_x_max_walkers.  moves: as HipNVP.ensemble_steps (nnest_ensemble_x_moves_steps)."""
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     x = _as_dev_f32(x, dev).contiguous()
     (C, D), steps = x.shape, int(steps)
+    mv = _lib.ens_moves(moves, 'ensemble_x_steps')
+    _lib.ens_moves_mix(mv, C, 'ensemble_x_steps')
     if (t_std is None) != (t_mean is None):
         raise ValueError('ensemble_x_steps: t_std and t_mean: both or neither')
     f32 = dict(dtype=torch.float32, device=dev)
@@ -853,9 +873,11 @@ def ensemble_x_steps(like_id, x, steps, t_std=None, t_mean=None, lo=None, hi=Non
     work = torch.empty(words, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         lk = _lib.like_spec(like_id, 1.0, like_params)
-        _lib.check(lib.nnest_ensemble_x_steps(
+        fn = lib.nnest_ensemble_x_steps if mv is None else lib.nnest_ensemble_x_moves_steps
+        _lib.check(fn(
             ctypes.byref(lk), _lib.ptr(t_std), _lib.ptr(t_mean), _lib.ptr(lo_t), _lib.ptr(hi_t), _lib.ptr(x), _lib.ptr(lp),
             _lib.ptr(out['x']), _lib.ptr(out['tx']), _lib.ptr(out['lp']), _lib.ptr(out['hist_x']), _lib.ptr(out['hist_lp']),
             _lib.ptr(out['n_accept']), _lib.ptr(work), C, D, steps, int(step0) & 0xFFFFFFFFFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF,
-            0 if loglstar is None else 1, 0.0 if loglstar is None else float(loglstar), _lib.current_stream(dev)))
+            0 if loglstar is None else 1, 0.0 if loglstar is None else float(loglstar), _lib.current_stream(dev),
+            *(() if mv is None else (_lib.moves_ref(mv),))))
     return out

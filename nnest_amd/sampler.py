@@ -768,15 +768,21 @@ class Sampler(object):
         `route` pins one; None chooses 'fused' for the NVP where it is taken and 'rounds' for every other flow -- the spline flow's
         fused kernel (nnest_spline_ensemble_steps) runs on route='fused' only, which raises ValueError where it is not taken.  The run is cut into launches of `chunk_steps` steps (default: by device memory); the cut does
         not change it.  Returns (samples [N, S, D] (x, before the transform), latent_samples [N, S, D], derived_samples [N, S, nd],
-        loglikes [N, S] (the latent log target, emcee's log_prob), ncall)."""
-        if moves is not None:
-            raise NotImplementedError('ensemble: only the default stretch move is built (moves=None)')
+        loglikes [N, S] (the latent log target, emcee's log_prob), ncall).
+        `moves`: None, or the reference's dict (sampler.py:693-707) with 'stretch' and 'de' (_lib.ens_moves: 'kde' and 'snooker' are
+        not built, NotImplementedError): one move per step by weight (include/nnest_hip.h nnest_ensemble_moves_steps).  With a DE
+        step in the run the NVP's fused route is taken where its population fits the kernel that knows the move; the spline flow's
+        fused kernel does not know it: rounds at route=None, ValueError at route='fused'."""
+        from . import _lib
+        mv = _lib.ens_moves(moves)
         S = int(mcmc_steps)
         if init_samples is not None:
             num_walkers = init_samples.shape[0]
         N, D, nd = int(num_walkers), self.x_dim, self.num_derived
         if N < 2 * D:   # emcee/moves/red_blue.py
             raise RuntimeError('It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions.')
+        mix = _lib.ens_moves_mix(mv, N)
+        mkw = {} if mv is None else {'moves': mv}
         netG = self.trainer.netG
         if init_samples is not None:
             z, _ = netG.forward(init_samples)
@@ -788,12 +794,13 @@ class Sampler(object):
         affine = self._ensemble_affine()
         dlike = self._ensemble_device_like(affine)
         # the fused kernel takes the flow (its family binds an `ensemble` entry: HipNVP, HipSpline), the likelihood and the population
-        fused_ok = (dlike is not None and 'ensemble' in getattr(netG, '_sym', ())
-                    and N <= netG.ensemble_max_walkers(dlike[0]))
+        # (with a DE step in the run: an `ensemble_moves` entry, and the population of the kernel that knows the move)
+        fused_ok = (dlike is not None and ('ensemble_moves' if mix else 'ensemble') in getattr(netG, '_sym', ())
+                    and N <= (netG.ensemble_max_walkers(dlike[0], moves=mv) if mix else netG.ensemble_max_walkers(dlike[0])))
         if route is None:   # (the spline's fused kernel is opt-in, route='fused': DESIGN.md 3.7)
             route = 'fused' if fused_ok and getattr(netG, 'ensemble_fused_by_default', False) else 'rounds'
         elif route == 'fused' and not fused_ok:
-            raise ValueError('ensemble: the fused route does not take this flow, likelihood or population')
+            raise ValueError('ensemble: the fused route does not take this flow, likelihood, population or move')
         if chunk_steps is None:
             chunk_steps = max(1, self.ENSEMBLE_HISTORY_BYTES // (N * (8 * D + 8)))
         chunk_steps = max(1, min(int(chunk_steps), S if S > 0 else 1))
@@ -811,12 +818,12 @@ class Sampler(object):
             if route == 'fused':
                 like_id, params, lo, hi = dlike
                 res = netG.ensemble_steps(like_id, z, k, t_std=affine[0], t_mean=affine[1], lo=lo, hi=hi, lp=lp0, loglstar=loglstar,
-                                          seed=seed, step0=done, like_params=params)
+                                          seed=seed, step0=done, like_params=params, **mkw)
                 z, lp0 = res['z'], res['lp']
                 hz, hx, hl = res['hist_z'], res['hist_x'], res['hist_lp']
                 n_acc += int(res['n_accept'].sum().item())
             else:
-                kw = dict(loglstar=loglstar, seed=seed, step0=done)
+                kw = dict(loglstar=loglstar, seed=seed, step0=done, **mkw)
                 if dlike is not None:
                     kw.update(like_id=dlike[0], like_params=dlike[1], t_std=affine[0], t_mean=affine[1], lo=dlike[2], hi=dlike[3])
                 else:
@@ -843,15 +850,17 @@ class Sampler(object):
         return samples, latent, derived, loglikes, ncall
 
     def _ensemble_sample_x(self, mcmc_steps, init_samples, init_loglikes=None, loglstar=None, affine=None, output_interval=None,
-                           seed=None, chunk_steps=None, route=None):
+                           seed=None, chunk_steps=None, route=None, moves=None):
         """The stretch move in X space: `_ensemble_sample`'s run with the identity for the flow, so the walkers are x and the target
         is logL(T(x)) + prior -- the emcee run EnsembleSampler.bootstrap starts from (ensemble.py:111-147).  BUILD-DEFINED STREAM,
         EMCEE'S MOVE (include/nnest_hip.h nnest_ensemble_x_steps).  T is `affine` = (std, mean), None: the identity.  Route 'fused'
         (nnest_ensemble_x_steps) where the likelihood and the prior run on the device and the population is resident, 'rounds'
         (ensemble_rounds on an IdentityFlow) otherwise: a Python likelihood, another prior, derived parameters, a larger
         population; `route` pins one, for tests.  Cut into launches like `_ensemble_sample`.  Returns (samples [N, S, D],
-        loglikes [N, S] (the log target), derived [N, S, nd], ncall)."""
+        loglikes [N, S] (the log target), derived [N, S, nd], ncall).  `moves`: as `_ensemble_sample` (nnest_ensemble_x_moves_steps)."""
+        from . import _lib
         from . import flow as _flow
+        mv = _lib.ens_moves(moves)
         from .ensemble_rounds import IdentityFlow, ensemble_rounds
         S = int(mcmc_steps)
         init_samples = np.asarray(init_samples)
@@ -860,6 +869,8 @@ class Sampler(object):
             raise ValueError('init_samples must be shaped [num_walkers, %d], got %s' % (D, init_samples.shape))
         if N < 2 * D:   # emcee/moves/red_blue.py
             raise RuntimeError('It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions.')
+        _lib.ens_moves_mix(mv, N)
+        mkw = {} if mv is None else {'moves': mv}
         dev = self.trainer.netG.device
         if affine is None:
             affine = (np.ones(D), np.zeros(D))
@@ -867,7 +878,7 @@ class Sampler(object):
         lp0 = None if init_loglikes is None else torch.as_tensor(np.asarray(init_loglikes, np.float64)).to(dev)
         seed = self._next_seed() if seed is None else int(seed)
         dlike = self._ensemble_device_like(affine)
-        fused_ok = dlike is not None and D <= 128 and N <= _flow.ensemble_x_max_walkers(D, dlike[0], device=dev)
+        fused_ok = dlike is not None and D <= 128 and N <= _flow.ensemble_x_max_walkers(D, dlike[0], device=dev, **mkw)
         if route is None:
             route = 'fused' if fused_ok else 'rounds'
         elif route == 'fused' and not fused_ok:
@@ -888,12 +899,12 @@ class Sampler(object):
             if route == 'fused':
                 like_id, params, lo, hi = dlike
                 res = _flow.ensemble_x_steps(like_id, x, k, t_std=affine[0], t_mean=affine[1], lo=lo, hi=hi, lp=lp0, loglstar=loglstar,
-                                             seed=seed, step0=done, like_params=params, device=dev)
+                                             seed=seed, step0=done, like_params=params, device=dev, **mkw)
                 x, lp0 = res['x'], res['lp']
                 hx, hl = res['hist_x'], res['hist_lp']
                 n_acc += int(res['n_accept'].sum().item())
             else:
-                kw = dict(loglstar=loglstar, seed=seed, step0=done)
+                kw = dict(loglstar=loglstar, seed=seed, step0=done, **mkw)
                 if dlike is not None:
                     kw.update(like_id=dlike[0], like_params=dlike[1], t_std=affine[0], t_mean=affine[1], lo=dlike[2], hi=dlike[3])
                 else:
