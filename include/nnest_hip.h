@@ -478,6 +478,12 @@ int nnest_nvp_train(nnest_nvp_t *nvp, const float *xtrain_dev, int n_train, cons
                     const int *perm_dev, const float *noise_dev, uint64_t seed, float jitter, int batch,
                     int max_epochs, int patience, float lr, float weight_decay, int epoch_offset, int flags,
                     float *losses_dev, nnest_train_result_t *result_dev, void *stream);
+/* nnest_nvp_train_form (added within ABI 15): the kernel nnest_nvp_train runs the epoch loop in for minibatches of `batch` rows and
+ * these `flags`, from the predicates of the launch itself -- 0: train_kernel, one workgroup (*detail = how many of its two fragment
+ * images live in LDS: 2, 1 or 0); 1: train_kernel_grid, eight workgroups (*detail = 10 NT + L, NT = ceil(x_dim / 32), L = num_layers);
+ * 2: train_kernel_rows, one workgroup per four rows (*detail = U = NT).  -1: nnest_nvp_train refuses the call (batch outside
+ * [1, 128], a MAF handle).  detail may be NULL. */
+int nnest_nvp_train_form(const nnest_nvp_t *nvp, int batch, int flags, int *detail);
 
 /* One minibatch: loss and dloss/dw (before weight decay) into grad_dev [num_params], no update.
  * For tests (reference: loss.backward(), trainer.py:400). x_dev [M,D]. loss_dev float32[1]. */

@@ -178,6 +178,7 @@ SIGNATURES = {
     'nnest_chol_adam_step': [_vp, _vp, _f, _f, _vp],
     'nnest_mh_num_groups': [_vp, _i],
     'nnest_mh_fill_noise': [_vp, _vp, _i, _i, _i, _u64, _u64, _vp],
+    'nnest_nvp_train_form': [_vp, _i, _i, _vp],
     'nnest_nvp_train': [_vp, _vp, _i, _vp, _i, _vp, _vp, _u64, _f, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp],
     'nnest_nvp_loss_grad': [_vp, _vp, _i, _vp, _vp, _vp],
     'nnest_training_jitter': [_vp, _i, _i, _vp, _vp],

@@ -659,6 +659,11 @@ int nnest_nvp_train(nnest_nvp_t *h, const float *xtrain_dev, int n_train, const 
     return NNEST_OK;
 }
 
+int nnest_nvp_train_form(const nnest_nvp_t *h, int batch, int flags, int *detail) {
+    if (!h || batch < 1 || batch > 128 || h->s.kind == FLOW_KIND_MAF) return -1;
+    return train_form_for(h->s, batch, flags, detail);
+}
+
 int nnest_nvp_loss_grad(nnest_nvp_t *h, const float *x_dev, int M, float *grad_dev, float *loss_dev, void *stream) {
     if (!h || !x_dev || !grad_dev || !loss_dev) return fail(NNEST_E_ARG, "NULL argument");
     if (M < 1 || M > 128) return fail(NNEST_E_UNSUPPORTED, "M=%d outside [1,128]", M);

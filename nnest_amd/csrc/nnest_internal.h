@@ -70,6 +70,8 @@ hipError_t launch_train(float *packed, float *adam_m, float *adam_v, float *best
                         int patience, float lr, float wd, int epoch_offset, int flags, float *losses, nnest_train_result_t *result,
                         float *workspace, const int *fwd_pos, const int *bwd_pos,
                         hipStream_t st);
+// the form launch_train runs a minibatch of `batch` rows in (nnest_nvp_train_form, include/nnest_hip.h)
+int train_form_for(const FlowShape &s, int batch, int flags, int *detail);
 hipError_t launch_build_pos(int *fwd_pos, int *bwd_pos, const FlowShape &s, hipStream_t st);
 // masked autoregressive flow (maf_train.h inside nnest_train.hip)
 size_t maf_workspace_floats(const FlowShape &s);

@@ -969,32 +969,53 @@ static hipError_t launch_train_tt(const TrainArgs &a, size_t lds, hipStream_t st
     return hipGetLastError();
 }
 
+// which of the two fragment images of train_kernel live in LDS next to the staging area (its IMGLDS), and the LDS bytes that takes.
+// The staging area is sized for TRAIN_MAX_ROWS rows; where that alone is more than a CU has (hidden 64 with two or three hidden
+// layers) it is sized for the rows of the launch's largest minibatch, which is all the kernel indexes (rows_pad).
 template <int NT, int NH, int L>
-static hipError_t launch_train_t(const TrainArgs &a, hipStream_t st) {
+static int train_imglds(const FlowShape &s, int rows, size_t &lds) {
     typedef StageMap<NT, NH, L> SM;
     const size_t stage = (size_t)SM::count * TRAIN_MAX_ROWS * 16 * sizeof(float);
-    const size_t with_img = stage + 2 * (size_t)a.s.image_floats * sizeof(float);
-    const size_t with_fwd = stage + (size_t)a.s.image_floats * sizeof(float);
-    if (with_img <= 160 * 1024 - 256) return launch_train_tt<NT, NH, L, 2>(a, with_img, st);
-    if (with_fwd <= 160 * 1024 - 256) return launch_train_tt<NT, NH, L, 1>(a, with_fwd, st);
-    return launch_train_tt<NT, NH, L, 0>(a, stage, st);
+    const size_t with_img = stage + 2 * (size_t)s.image_floats * sizeof(float);
+    const size_t with_fwd = stage + (size_t)s.image_floats * sizeof(float);
+    if (with_img <= 160 * 1024 - 256) { lds = with_img; return 2; }
+    if (with_fwd <= 160 * 1024 - 256) { lds = with_fwd; return 1; }
+    lds = stage <= 160 * 1024 ? stage : (size_t)SM::count * (size_t)((min(max(rows, 1), TRAIN_MAX_ROWS) + 15) & ~15) * 16 * sizeof(float);
+    return 0;
 }
+
+template <int NT, int NH, int L>
+static hipError_t launch_train_t(const TrainArgs &a, hipStream_t st) {
+    size_t lds;
+    switch (train_imglds<NT, NH, L>(a.s, min(a.batch, a.n_train), lds)) {
+        case 2: return launch_train_tt<NT, NH, L, 2>(a, lds, st);
+        case 1: return launch_train_tt<NT, NH, L, 1>(a, lds, st);
+    }
+    return launch_train_tt<NT, NH, L, 0>(a, lds, st);
+}
+
+// the instantiated (NT, NH, L); round 6 added the rest of what the reference's Trainer(hidden_dim, num_layers) can ask for inside the
+// instantiated tile shapes (nnest/networks.py:253-287 takes any num_layers): three hidden layers, and the wide nets without / with two of them
+#define TRAIN_SHAPES(X) \
+    X(1, 1, 0) X(2, 1, 0) X(3, 1, 0) X(4, 1, 0) X(1, 1, 1) X(2, 1, 1) X(3, 1, 1) X(4, 1, 1) X(1, 1, 2) X(2, 1, 2) X(3, 1, 2) X(4, 1, 2) \
+    X(1, 2, 1) X(2, 2, 1) X(1, 2, 2) X(2, 2, 2) X(1, 4, 1) \
+    X(1, 1, 3) X(2, 1, 3) X(3, 1, 3) X(4, 1, 3) X(1, 2, 0) X(2, 2, 0) X(1, 2, 3) X(2, 2, 3) X(1, 4, 0) X(1, 4, 2) X(1, 4, 3)
 
 static hipError_t dispatch_train(const TrainArgs &a, hipStream_t st) {
     const FlowShape &s = a.s;
-#define TRY_SHAPE(nt, nh, l) if (s.NT == nt && s.NH == nh && s.L == l) return launch_train_t<nt, nh, l>(a, st)
-    TRY_SHAPE(1, 1, 0); TRY_SHAPE(2, 1, 0); TRY_SHAPE(3, 1, 0); TRY_SHAPE(4, 1, 0);
-    TRY_SHAPE(1, 1, 1); TRY_SHAPE(2, 1, 1); TRY_SHAPE(3, 1, 1); TRY_SHAPE(4, 1, 1);
-    TRY_SHAPE(1, 1, 2); TRY_SHAPE(2, 1, 2); TRY_SHAPE(3, 1, 2); TRY_SHAPE(4, 1, 2);
-    TRY_SHAPE(1, 2, 1); TRY_SHAPE(2, 2, 1); TRY_SHAPE(1, 2, 2); TRY_SHAPE(2, 2, 2);
-    TRY_SHAPE(1, 4, 1);
-    // round 6: the rest of what the reference's Trainer(hidden_dim, num_layers) can ask for inside the instantiated tile shapes
-    // (nnest/networks.py:253-287 takes any num_layers): three hidden layers, and the wide nets without / with two of them
-    TRY_SHAPE(1, 1, 3); TRY_SHAPE(2, 1, 3); TRY_SHAPE(3, 1, 3); TRY_SHAPE(4, 1, 3);
-    TRY_SHAPE(1, 2, 0); TRY_SHAPE(2, 2, 0); TRY_SHAPE(1, 2, 3); TRY_SHAPE(2, 2, 3);
-    TRY_SHAPE(1, 4, 0); TRY_SHAPE(1, 4, 2); TRY_SHAPE(1, 4, 3);
+#define TRY_SHAPE(nt, nh, l) if (s.NT == nt && s.NH == nh && s.L == l) return launch_train_t<nt, nh, l>(a, st);
+    TRAIN_SHAPES(TRY_SHAPE)
 #undef TRY_SHAPE
     return hipErrorInvalidConfiguration;
+}
+
+// IMGLDS of the train_kernel instantiation dispatch_train launches for this shape; -1: none
+static int train_imglds_for(const FlowShape &s) {
+    size_t lds;
+#define TRY_SHAPE(nt, nh, l) if (s.NT == nt && s.NH == nh && s.L == l) return train_imglds<nt, nh, l>(s, TRAIN_MAX_ROWS, lds);
+    TRAIN_SHAPES(TRY_SHAPE)
+#undef TRY_SHAPE
+    return -1;
 }
 
 #include "nnest_train_grid.h"
@@ -1096,6 +1117,14 @@ hipError_t launch_adam_packed(float *w, const float *grad, float *m, float *v, i
     return hipGetLastError();
 }
 
+// the kernel form of the epoch loop (nnest_nvp_train_form reports it): train_kernel_rows<U = NT>, train_kernel_grid<NT,1,L>, else
+// train_kernel on one workgroup
+enum { TRAIN_FORM_SINGLE = 0, TRAIN_FORM_GRID = 1, TRAIN_FORM_ROWS = 2 };
+static int epoch_form(const TrainArgs &a) {
+    if (!grid_eligible(a)) return TRAIN_FORM_SINGLE;
+    return rows_eligible(a) ? TRAIN_FORM_ROWS : TRAIN_FORM_GRID;
+}
+
 hipError_t launch_train(float *packed, float *adam_m, float *adam_v, float *best_w, float *img, int *adam_step_dev,
                         const FlowShape &s, const float *xtrain, int n_train, const float *xvalid, int n_valid,
                         const int *perm, const float *noise, uint64_t seed, float jitter, int batch, int max_epochs,
@@ -1118,9 +1147,23 @@ hipError_t launch_train(float *packed, float *adam_m, float *adam_v, float *best
     a.losses = losses; a.result = result;
     a.epoch_offset = epoch_offset; a.flags = flags;
     a.mode = TRAIN_MODE_EPOCHS;
-    if (grid_eligible(a) && rows_eligible(a)) return dispatch_train_rows(a, workspace + ((single_workspace_floats(s) + 63) & ~(size_t)63), st);
-    if (grid_eligible(a)) return dispatch_train_grid(a, workspace + ((single_workspace_floats(s) + 63) & ~(size_t)63), st);
+    float *gridws = workspace + ((single_workspace_floats(s) + 63) & ~(size_t)63);
+    switch (epoch_form(a)) {
+        case TRAIN_FORM_ROWS: return dispatch_train_rows(a, gridws, st);
+        case TRAIN_FORM_GRID: return dispatch_train_grid(a, gridws, st);
+    }
     return dispatch_train(a, st);
+}
+
+int train_form_for(const FlowShape &s, int batch, int flags, int *detail) {
+    TrainArgs a;
+    memset(&a, 0, sizeof(a));
+    a.s = s; a.batch = batch; a.flags = flags;
+    a.mode = TRAIN_MODE_EPOCHS;
+    const int form = epoch_form(a);
+    if (detail)
+        *detail = form == TRAIN_FORM_ROWS ? s.NT : form == TRAIN_FORM_GRID ? 10 * s.NT + s.L : train_imglds_for(s);
+    return form;
 }
 
 }  // namespace nnest

@@ -780,6 +780,15 @@ class HipNVP(_PaddedVectors, _HipFlow):
                                                      v.ctypes.data_as(ctypes.c_void_p), _lib.current_stream(self.device)))
             _lib.check(self._lib.nnest_nvp_adam_state(self._h, None, int(step), 0, _lib.current_stream(self.device)))
 
+    def train_form_for(self, batch, one_cu=False):
+        """(name, detail) of the kernel train_epochs runs minibatches of `batch` rows in (nnest_nvp_train_form): ('single', how many
+        of the two fragment images live in LDS), ('grid', 10 NT + L) or ('rows', U)"""
+        detail = ctypes.c_int(-1)
+        form = self._lib.nnest_nvp_train_form(self._h, int(batch), _lib.TRAIN_ONE_CU if one_cu else 0, ctypes.byref(detail))
+        if form < 0:
+            raise _lib.NnestHipError('nnest_nvp_train_form: no training kernel takes batch=%d on this handle' % int(batch))
+        return ('single', 'grid', 'rows')[form], detail.value
+
     def train_epochs(self, xtrain, xvalid, perm, noise=None, seed=0, jitter=0.0, batch=100, max_epochs=1, patience=50,
                      lr=1e-3, weight_decay=1e-6, epoch_offset=0, resume=False, finalize=True, result=None, one_cu=False):
         """K5: Trainer.train's epoch loop (trainer.py:198-241) in one launch.  perm int32 [max_epochs, n_train];
