@@ -205,9 +205,10 @@ def jittered(xtrain, perm, noise, jitter=JITTER):
 KINK = 1e-5
 
 
-def away_from_kinks(c, w, s):
-    """the step's inputs with every row at a relu kink (at weights w) replaced by a spare row; most often s itself"""
-    ev = make_oracle(c, w)
+def away_from_kinks(c, w, s, evaluator=None):
+    """the step's inputs with every row at a relu kink (at weights w) replaced by a spare row; most often s itself.  evaluator(w):
+    the oracle at weights w (default: the RealNVP of the case, make_oracle(c, w))"""
+    ev = make_oracle(c, w) if evaluator is None else evaluator(w)
 
     def disagree(rows):
         g64, g32 = ev.loss_grad(rows, f64=True)[1], ev.loss_grad(rows)[1]
@@ -291,19 +292,29 @@ def tensor_bounds(g64, rtol, layer_shapes, bounds=BOUNDS):
     return [(name, s, rtol * float(np.max(np.abs(g64[s]))) + floor) for name, s in tensor_slices(layer_shapes)]
 
 
-def check_step(pre, post, data, oracle, lr, wd, layer_shapes, bounds=BOUNDS, what=''):
+def rebuilt(oracle):
+    """the default evaluator factory: w -> an oracle of `oracle`'s class, shape, scale variant and base at weights w (a RealNVP)"""
+    return lambda w: type(oracle)(oracle.D, oracle.H, oracle.B, oracle.L, w, scale=oracle.scale, base_beta=oracle.base_beta)
+
+
+def check_step(pre, post, data, oracle, lr, wd, layer_shapes, bounds=BOUNDS, what='', evaluator=None, masked=None):
     """One optimizer step: pre / post = (w, m, v, t) as float32 arrays (t an int), data the float32 rows of the minibatch, oracle an
     orc.NVP of the flow's shape (its own weights are not touched).  Raises AssertionError naming the tensor and the element; returns
-    the worst error / bound per check and the float64 batch loss."""
+    the worst error / bound per check and the float64 batch loss.
+    Another flow with the same packed layout supplies evaluator(w) -> its oracle at weights w (default rebuilt(oracle)) and masked,
+    the parameters whose gradient is zero by construction: a bool [n] array or a callable (layer_shapes, n, D) -> one (default
+    masked_elements, RealNVP's rule)."""
     w, m, v, t = pre
     w1, m1, v1, t1 = post
     n = w.size
-    ev = type(oracle)(oracle.D, oracle.H, oracle.B, oracle.L, w, scale=oracle.scale, base_beta=oracle.base_beta)
+    ev = (rebuilt(oracle) if evaluator is None else evaluator)(w)
     loss64, g64 = ev.loss_grad(data, f64=True)
     _, g32 = ev.loss_grad(data)
     assert g64.size == n and all(np.asarray(a).size == n for a in (m, v, w1, m1, v1))
     assert int(t1) == int(t) + 1, '%s: step count %d after %d' % (what, t1, t)
-    masked = masked_elements(layer_shapes, n, oracle.D)
+    masked = masked_elements if masked is None else masked
+    masked = np.asarray(masked(layer_shapes, n, oracle.D) if callable(masked) else masked, bool)
+    assert masked.shape == (n,)
     assert np.all(g64[masked] == 0) and np.any(g64[~masked] != 0)
     wd32 = float(np.float32(wd))
     w_, m_, v_ = (np.asarray(a, np.float64) for a in (w, m, v))
@@ -376,9 +387,9 @@ def check_train_loss(logged, n_train, loss64, bounds=BOUNDS, what=''):
     return abs(got - loss64) / (bounds['loss'] * (1 + abs(loss64)))
 
 
-def check_valid_loss(logged, xvalid, w_post, oracle, bounds=BOUNDS, what=''):
-    """losses[0, 1] n_valid against -mean(log_probs(xvalid)) in float64 at the weights after the step"""
-    ev = type(oracle)(oracle.D, oracle.H, oracle.B, oracle.L, w_post, scale=oracle.scale, base_beta=oracle.base_beta)
+def check_valid_loss(logged, xvalid, w_post, oracle, bounds=BOUNDS, what='', evaluator=None):
+    """losses[0, 1] n_valid against -mean(log_probs(xvalid)) in float64 at the weights after the step (evaluator: as check_step)"""
+    ev = (rebuilt(oracle) if evaluator is None else evaluator)(w_post)
     want = -float(np.mean(ev.log_probs(xvalid, f64=True)))
     got = float(logged) * xvalid.shape[0]
     assert abs(got - want) < bounds['loss'] * (1 + abs(want)), '%s: validation loss %.9g vs float64 %.9g' % (what, got, want)

@@ -38,7 +38,8 @@ def pair(hip, D, B=3, L=1, seed=0, scale=1.0):
     return m, orc.NVP(D, 16, B, L, m.store_packed(), kind='maf')
 
 
-@pytest.mark.parametrize('D,B,L', [(2, 3, 1), (5, 3, 1), (50, 3, 1), (100, 3, 1), (33, 2, 0), (64, 4, 2), (128, 1, 1)])
+@pytest.mark.parametrize('D,B,L', [(2, 3, 1), (5, 3, 1), (50, 3, 1), (100, 3, 1), (33, 2, 0), (64, 4, 2), (128, 1, 1), (70, 3, 1),
+                                   (96, 2, 2)])
 @pytest.mark.parametrize('N', [1, 37, 1000])
 def test_maf_passes_vs_oracle(hip, D, B, L, N):
     """[UNPINNED]  forward (one pass), inverse (group by group), log_probs against the oracle; the reference's flow criteria
@@ -73,7 +74,27 @@ def test_maf_empty_and_ragged(hip):
         assert rel(cpu(z), zo) < 2e-5 and rel(cpu(ld), ldo) < 2e-5
 
 
-@pytest.mark.parametrize('D,like,scale', [(2, 'rosenbrock', 5.0), (20, 'gaussmix', 10.0), (50, 'rosenbrock', 5.0), (100, 'rosenbrock', 5.0)])
+@pytest.mark.parametrize('N', [37, 1000])
+def test_maf_generalised_normal_base_vs_oracle(hip, N):
+    """[UNPINNED]  GeneralisedNormal(0, 1, 8) as the base (networks.py:47-59): log_probs reads base_beta in maf_pass_kernel, the
+    forward log-det does not depend on it; against the oracle with the same base, at the tolerances of the passes above"""
+    from nnest_amd.distributions import GeneralisedNormal
+    D = 50
+    m, _ = pair(hip, D, seed=6)
+    x = np.random.RandomState(N).uniform(-1, 1, size=(N, D)).astype(np.float32)
+    lp_normal = cpu(m.log_probs(x))
+    m.set_base(GeneralisedNormal(torch.zeros(D), torch.ones(D), torch.tensor(8.0)))
+    o = orc.NVP(D, 16, 3, 1, m.store_packed(), base_beta=8, kind='maf')
+    z, ld = m.forward(x)
+    zo, ldo = o.forward(x)
+    assert rel(cpu(z), zo) < 2e-5 and rel(cpu(ld), ldo) < 2e-5
+    lp = cpu(m.log_probs(x))
+    assert rel(lp, o.log_probs(x)) < 3e-5
+    assert np.max(np.abs(lp - lp_normal)) > 1.0      # (the base did change what is computed)
+
+
+@pytest.mark.parametrize('D,like,scale', [(2, 'rosenbrock', 5.0), (20, 'gaussmix', 10.0), (50, 'rosenbrock', 5.0), (100, 'rosenbrock', 5.0),
+                                          (70, 'rosenbrock', 5.0)])
 def test_maf_fused_eval_vs_oracle(hip, D, like, scale):
     """[UNPINNED]  K3 with the MAF: x = f^-1(z), box prior, likelihood in one launch"""
     m, o = pair(hip, D, seed=3)
@@ -124,7 +145,7 @@ def test_maf_adam_steps_follow_the_oracle(hip):
     assert rel(cpu(z), zo) < 2e-5
 
 
-@pytest.mark.parametrize('D,L', [(7, 1), (50, 1), (100, 2)])
+@pytest.mark.parametrize('D,L', [(7, 1), (50, 1), (100, 2), (70, 1)])
 def test_maf_epoch_call_equals_the_stepwise_loop(hip, D, L):
     """[UNPINNED]  nnest_maf_train_epoch (gradient kernel + ONE kernel that reduces, steps Adam and rewrites both fragment images
     through position maps) against the same minibatches driven step by step (nnest_nvp_loss_grad + nnest_nvp_adam_step, whose
@@ -161,7 +182,8 @@ def test_maf_epoch_call_equals_the_stepwise_loop(hip, D, L):
     assert torch.equal(ga, gb) and torch.equal(la, lb)
 
 
-@pytest.mark.parametrize('D,C,S,dyn', [(50, 200, 12, False), (100, 64, 6, False), (5, 37, 30, True), (20, 1000, 8, True)])
+@pytest.mark.parametrize('D,C,S,dyn', [(50, 200, 12, False), (100, 64, 6, False), (5, 37, 30, True), (20, 1000, 8, True),
+                                       (70, 48, 6, True)])
 def test_maf_metropolis_kernel_vs_oracle(hip, D, C, S, dyn):
     """[UNPINNED]  K4 (Sampler._mcmc_sample, sampler.py:229-463) with the MAF's grouped inverse inside the persistent kernel:
     the kernel's own noise replayed through the oracle, per 16-walker adaptation group"""
