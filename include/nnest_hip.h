@@ -428,6 +428,49 @@ int nnest_ensemble_rounds_moves_accept(const int *work_dev, int C, int steps, in
                                        double loglstar, void *stream, const nnest_ens_moves_t *moves);
 int nnest_ensemble_fill_moves(const int *work_dev, int *move_dev, int *b_dev, float *gamma_dev, int C, int D, int steps, uint64_t step0,
                               uint64_t seed, const nnest_ens_moves_t *moves, void *stream);
+
+/* RANDOM-WALK METROPOLIS in the latent space of the flow with the likelihood, the prior and the Jacobian in the ratio: MCMCSampler's
+ * run, Sampler._mcmc_sample with loglstar = None (nnest/mcmc.py:79-126, nnest/sampler.py:372-416), every step of a launch inside the
+ * kernel.  BUILD-DEFINED STREAM, THE REFERENCE'S MOVE: the draws are this library's Philox4x32-10 words, so parity with torch's
+ * stream is statistical.  C walkers z_k in R^D; step t (global index, 0-based; `step0` is the index of a launch's first step); the
+ * global walker index is w = walker_offset + k:
+ *   normals:  eps[4g .. 4g+3] = the four Box-Muller normals of Philox(key seed; counter (g, w, t, 5 << 28 | w >> 32)), with the
+ *             arithmetic of the slice proposal's directions (float32: u = r 2^-32 + 2^-33, sqrt(-2 ln u), sin / cos in revolutions);
+ *   uniform:  u = the top 24 bits of word 0 of Philox(key seed; counter (0, w, t, 6 << 28 | w >> 32)) / 2^24;
+ *   proposal: q = z_k + step_size * eps (float32, each operation rounded);
+ *   accept:   the walker moves to q iff lp(q) - lp(z_k) > log u (float64), lp the target of nnest_ensemble_steps at constrained = 0:
+ *             x = f^-1(z), T(x) = x * t_std + t_mean, logL = safe_loglike(T(x)), lp = (logL + log|det dx/dz|) + prior, the prior 0 in
+ *             the box [lo, hi] on T(x) (NaN inside) and -inf outside;
+ *   logged:   the walker carries logL(T(x)) (float64) beside lp: the reference returns logL in `loglikes`.
+ * A run is a function of (seed, global walker index, global step) only: neither the cut into launches, nor the kernel layout, nor
+ * a shard of the population (walker_offset) changes it.  Walkers are independent: there is no hand-off, no residency limit and no
+ * work buffer, and the calls are asynchronous on `stream`.  Only this unconstrained target is built (the hard constraint is
+ * nnest_mh_constrained_steps's); the step is fixed.  (All added within ABI 15.)
+ * nnest_mcmc_steps: the default NVP shape (hidden 16, 3 blocks, 1 layer, scale ''), x_dim <= 128, a known likelihood id
+ *   (like->scale is ignored: the likelihood sees T(x)); other shapes: NNEST_E_UNSUPPORTED.  Any C >= 1: one walker per wave,
+ *   ceil(C / 4) workgroups.  z_in_dev [C,D]; lp_in_dev, logl_in_dev [C]: both (the start's lp and logL, as a previous launch returned
+ *   them) or both NULL (evaluated); z_out_dev, x_out_dev [C,D], lp_out_dev, logl_out_dev [C]: the last state (z_out_dev may be
+ *   z_in_dev); hist_z_dev, hist_x_dev [C, steps, D], hist_logl_dev [C, steps]: the state after every step, all three or all NULL
+ *   (the ends only); n_accept_dev [C] or NULL.  t_std_dev, t_mean_dev [D], both or both NULL (T = identity); lo_dev, hi_dev [D], both
+ *   or both NULL (no prior).  steps = 0 evaluates the start: x_out_dev, lp_out_dev and logl_out_dev are written, nothing else is
+ *   (z_out_dev may then be NULL).
+ * nnest_spline_mcmc_steps: the same run through the neural-spline flow, on the team tile of nnest_spline_ensemble_steps and its
+ *   shapes: 16 walkers per workgroup, four waves; a step is ONE evaluation of the tile in which every live row proposes (rows >= C
+ *   evaluate their own point, and the result is discarded); the four waves take bit-identical decisions.
+ * nnest_mcmc_fill_noise: the draws above as arrays, through the kernels' own functions: dz_dev [steps, C, D] float32 (eps) and u_dev
+ *   [steps, C] float32, either or NULL, for steps step0 .. step0 + steps - 1 and walkers walker_offset .. walker_offset + C - 1. */
+int nnest_mcmc_steps(nnest_nvp_t *nvp, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                     const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev,
+                     float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev, float *hist_x_dev,
+                     double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size, uint64_t step0, uint64_t seed,
+                     uint64_t walker_offset, void *stream);
+int nnest_spline_mcmc_steps(struct nnest_spline *spl, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                            const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev,
+                            const double *logl_in_dev, float *z_out_dev, float *x_out_dev, double *lp_out_dev, double *logl_out_dev,
+                            float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C, int steps,
+                            float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, void *stream);
+int nnest_mcmc_fill_noise(float *dz_dev, float *u_dev, int steps, int C, int D, uint64_t step0, uint64_t seed, uint64_t walker_offset,
+                          void *stream);
 /* size of sync_dev in 8-byte words for a launch of `steps` steps */
 int nnest_mh_sync_words(int steps);
 /* number of adaptation groups nnest_mh_constrained_steps uses for C walkers (size of scale_out_dev) */

@@ -217,6 +217,10 @@ SIGNATURES = {
     'nnest_ensemble_rounds_moves_accept': [_vp, _i, _i, _i, _i, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp],
     'nnest_ensemble_fill_moves': [_vp, _vp, _vp, _vp, _i, _i, _i, _u64, _u64, _vp, _vp],
+    'nnest_mcmc_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64, _u64, _u64, _vp],
+    'nnest_spline_mcmc_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64, _u64, _u64,
+                                _vp],
+    'nnest_mcmc_fill_noise': [_vp, _vp, _i, _i, _i, _u64, _u64, _u64, _vp],
     'nnest_host_prior_consume': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  ctypes.c_longlong, _d, ctypes.c_longlong, ctypes.c_longlong, _d, _d, _i],
     'nnest_chain_stats_work_words': [_i, _i, _i],

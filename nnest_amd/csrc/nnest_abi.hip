@@ -8,6 +8,7 @@
 #include "nnest_internal.h"
 #include "mh_common.h"
 #include "ensemble_common.h"
+#include "mcmc_walk.h"
 
 using namespace nnest;
 
@@ -405,6 +406,24 @@ int nnest_ensemble_work_words(int C, int steps) {
 }
 
 }  // extern "C"
+int nnest::mcmc_args(McmcArgs *a, const float *t_std, const float *t_mean, const float *lo, const float *hi, const float *z_in,
+                     const double *lp_in, const double *logl_in, float *z_out, float *x_out, double *lp_out, double *logl_out,
+                     float *hist_z, float *hist_x, double *hist_logl, int *n_accept, int C, int steps, float step_size, uint64_t step0,
+                     uint64_t seed, uint64_t walker_offset) {
+    if (C < 1 || steps < 0) return fail(NNEST_E_ARG, "mcmc: C=%d (>= 1 walkers) steps=%d (>= 0)", C, steps);
+    if (!isfinite(step_size) || step_size < 0.f) return fail(NNEST_E_ARG, "mcmc: step_size=%g (finite, >= 0)", (double)step_size);
+    if (!z_in || !x_out || !lp_out || !logl_out || (steps > 0 && !z_out)) return fail(NNEST_E_ARG, "NULL device buffer");
+    if (!t_std != !t_mean) return fail(NNEST_E_ARG, "t_std_dev and t_mean_dev: both or neither");
+    if (!lo != !hi) return fail(NNEST_E_ARG, "lo_dev and hi_dev: both or neither");
+    if (!lp_in != !logl_in) return fail(NNEST_E_ARG, "lp_in_dev and logl_in_dev: both or neither");
+    if ((!hist_z != !hist_x) || (!hist_z != !hist_logl)) return fail(NNEST_E_ARG, "hist_z_dev, hist_x_dev and hist_logl_dev: all or none");
+    a->t_std = t_std; a->t_mean = t_mean; a->lo = lo; a->hi = hi;
+    a->z_in = z_in; a->lp_in = lp_in; a->logl_in = logl_in;
+    a->z_out = z_out; a->x_out = x_out; a->lp_out = lp_out; a->logl_out = logl_out;
+    a->hist_z = hist_z; a->hist_x = hist_x; a->hist_logl = hist_logl; a->n_accept = n_accept;
+    a->C = C; a->S = steps; a->step = step_size; a->step0 = (uint32_t)step0; a->seed = seed; a->walker_offset = walker_offset;
+    return NNEST_OK;
+}
 int nnest::ensemble_sizes(int C, int steps) {
     if (C < 2 || C > (1 << 16) || steps < 0) return fail(NNEST_E_ARG, "ensemble: C=%d (2..65536 walkers) steps=%d", C, steps);
     if (nnest_ensemble_work_words(C, steps) < 0) return fail(NNEST_E_ARG, "ensemble: C=%d x steps=%d: the work buffer exceeds 2^31 words", C, steps);
@@ -455,6 +474,37 @@ int nnest_ensemble_fill_noise(int *work_dev, float *u_dev, int C, int steps, uin
     if (rc) return rc;
     if (!work_dev) return fail(NNEST_E_ARG, "NULL work_dev");
     HIP_TRY(launch_ensemble_split(work_dev, u_dev, C, steps, (uint32_t)step0, seed, (hipStream_t)stream));
+    return NNEST_OK;
+}
+
+// (the checks that need no handle come first: they answer on a machine without a GPU, where no handle can exist)
+int nnest_mcmc_steps(nnest_nvp_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                     const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev,
+                     float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev, float *hist_x_dev,
+                     double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size, uint64_t step0, uint64_t seed,
+                     uint64_t walker_offset, void *stream) {
+    if (!like) return fail(NNEST_E_ARG, "like is NULL");
+    if (like->id < 0 || like->id >= NNEST_LIKE_COUNT) return fail(NNEST_E_ARG, "unknown likelihood id %d", like->id);
+    McmcArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc = mcmc_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev, lp_out_dev,
+                       logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0, seed, walker_offset);
+    if (rc) return rc;
+    if (!h) return fail(NNEST_E_ARG, "NULL handle");
+    if ((rc = check_like(like, h->s.D, &a.like))) return rc;
+    a.like.scale = 1.0f;
+    if (!ensemble_form_eligible(h->s))
+        return fail(NNEST_E_UNSUPPORTED, "mcmc: hidden 16, 3 blocks, 1 layer, scale '' (the one-walker-per-wave layout), x_dim <= 128");
+    hipError_t e = launch_mcmc(h->s, h->w, a, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(NNEST_E_UNSUPPORTED, "mcmc: x_dim=%d not instantiated", h->s.D);
+    if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_mcmc: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+int nnest_mcmc_fill_noise(float *dz_dev, float *u_dev, int steps, int C, int D, uint64_t step0, uint64_t seed, uint64_t walker_offset,
+                          void *stream) {
+    if (steps < 0 || C < 0 || D < 1) return fail(NNEST_E_ARG, "mcmc_fill_noise: steps=%d C=%d D=%d", steps, C, D);
+    HIP_TRY(launch_mcmc_fill_noise(dz_dev, u_dev, steps, C, D, (uint32_t)step0, seed, walker_offset, (hipStream_t)stream));
     return NNEST_OK;
 }
 

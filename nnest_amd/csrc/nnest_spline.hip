@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ensemble_common.h"
+#include "mcmc_walk.h"
 #include "nnest_internal.h"
 #include "mh_common.h"
 
@@ -416,6 +417,29 @@ int nnest_spline_ensemble_steps(nnest_spline_t *h, const nnest_like_t *like, con
     msg[0] = 0;
     rc = launch_spline_ensemble(SplArgs{h->img, h->s}, a, h->num_cu, (hipStream_t)stream, msg, sizeof(msg));
     if (rc) return spline_fail(rc, "%s", msg);
+    return NNEST_OK;
+}
+
+// the random-walk Metropolis run through the spline flow (nnest_spline_mcmc.hip); the argument checks of nnest_mcmc_steps
+int nnest_spline_mcmc_steps(nnest_spline_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                            const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev,
+                            const double *logl_in_dev, float *z_out_dev, float *x_out_dev, double *lp_out_dev, double *logl_out_dev,
+                            float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C, int steps,
+                            float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, void *stream) {
+    if (!like) return spline_fail(NNEST_E_ARG, "like is NULL");
+    if (like->id < 0 || like->id >= NNEST_LIKE_COUNT) return spline_fail(NNEST_E_ARG, "unknown likelihood id %d", like->id);
+    McmcArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc = mcmc_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev, lp_out_dev,
+                       logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0, seed, walker_offset);
+    if (rc) return rc;
+    if (!h) return spline_fail(NNEST_E_ARG, "NULL handle");
+    if ((rc = scheck_like(like, h->s.D, &a.like))) return rc;
+    a.like.scale = 1.0f;
+    hipError_t e = launch_spline_mcmc(SplArgs{h->img, h->s}, a, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration)
+        return spline_fail(NNEST_E_UNSUPPORTED, "spline mcmc: x_dim=%d hidden_dim=%d not instantiated", h->s.D, h->s.H);
+    if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_mcmc: %s", hipGetErrorString(e));
     return NNEST_OK;
 }
 

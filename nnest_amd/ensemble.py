@@ -129,13 +129,6 @@ class EnsembleSampler(Sampler):
         self.logger.info('ncall: {:d}\n'.format(self.total_calls))
         return training_samples
 
-    def _install_transform(self, mean, std):
-        """T(x) = x * std + mean, also as per-dimension float arrays for the device routes"""
-        self.transform = lambda x: x * std + mean
-        self._ensemble_transform = (np.asarray(std, np.float64), np.asarray(mean, np.float64))
-        self._linear_scale = None   # (the Metropolis kernels only know x -> s * x)
-        self._fused_like_id = None
-
     def run(self, mcmc_steps, num_walkers, training_samples, stats_interval=10, output_interval=None, initial_jitter=0.01,
             final_jitter=0.01, init_samples=None, route=None, moves=None):
         """ensemble.py:186-231.  As in the reference, `init_samples` is accepted and not forwarded; `stats_interval` is used with

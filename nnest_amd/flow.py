@@ -386,6 +386,53 @@ class _HipFlow(object):
                 _lib.current_stream(dev), *(() if mv is None else (_lib.moves_ref(mv),))))
         return out
 
+    def mcmc_steps(self, like_id, z, steps, step_size, t_std=None, t_mean=None, lo=None, hi=None, lp=None, logl=None, seed=0, step0=0,
+                   walker_offset=0, like_params=None, history=True):
+        """`steps` steps of random-walk Metropolis in latent space with the likelihood, the prior and the Jacobian in the ratio, in ONE
+        launch (the family's `mcmc` entry point: nnest_mcmc_steps, nnest_spline_mcmc_steps; build-defined stream, the reference's move:
+        include/nnest_hip.h has the definition).  z [C, D] float32 on the device: the walkers' start; lp, logl [C] float64: the
+        start's target and likelihood as a previous launch returned them, or both None (evaluated); the likelihood `like_id` sees
+        T(x) = x * t_std + t_mean (per dimension; None: identity); lo / hi [D]: the prior box on T(x) (None: no prior).  step0: the
+        global index of the first step, walker_offset: the global index of walker 0 -- the draws depend on (seed, walker, step)
+        only, so a run cut into launches or into shards is the same run.  steps = 0 evaluates the start (x, lp, logl; z is the
+        caller's).  Returns z, x, lp, logl (the last state), hist_z, hist_x [C, steps, D], hist_logl [C, steps] (the state after
+        every step; None with history=False or steps = 0) and n_accept [C].  Asynchronous on the current stream.
+        NotImplementedError for a family without such a kernel (its handle must not reach another family's)."""
+        fn = self._sym.get('mcmc')
+        if fn is None:
+            raise NotImplementedError('no fused random-walk Metropolis kernel for %s' % type(self).__name__)
+        dev = self.device
+        z = _as_dev_f32(z, dev).contiguous()
+        C, D, steps = z.shape[0], self.D, int(steps)
+        if z.shape != (C, D):
+            raise ValueError('mcmc_steps: z must be shaped [C, %d], got %s' % (D, tuple(z.shape)))
+        if (lp is None) != (logl is None):
+            raise ValueError('mcmc_steps: lp and logl: both or neither')
+        if (t_std is None) != (t_mean is None):
+            raise ValueError('mcmc_steps: t_std and t_mean: both or neither')
+        f32 = dict(dtype=torch.float32, device=dev)
+        f64 = dict(dtype=torch.float64, device=dev)
+        vec = lambda v: None if v is None else _as_dev_f32(np.asarray(v, np.float32).reshape(1, D), dev).reshape(D)
+        t_std, t_mean, lo_t, hi_t = vec(t_std), vec(t_mean), vec(lo), vec(hi)
+        if lp is not None:
+            lp = torch.as_tensor(lp, dtype=torch.float64).to(dev).contiguous()
+            logl = torch.as_tensor(logl, dtype=torch.float64).to(dev).contiguous()
+        hist = bool(history) and steps > 0
+        out = dict(z=torch.empty(C, D, **f32) if steps > 0 else z, x=torch.empty(C, D, **f32), lp=torch.empty(C, **f64),
+                   logl=torch.empty(C, **f64),
+                   hist_z=torch.empty(C, steps, D, **f32) if hist else None, hist_x=torch.empty(C, steps, D, **f32) if hist else None,
+                   hist_logl=torch.empty(C, steps, **f64) if hist else None,
+                   n_accept=torch.empty(C, dtype=torch.int32, device=dev) if steps > 0 else torch.zeros(C, dtype=torch.int32, device=dev))
+        with torch.cuda.device(dev):
+            lk = _lib.like_spec(like_id, 1.0, like_params)
+            _lib.check(fn(
+                self._h, ctypes.byref(lk), _lib.ptr(t_std), _lib.ptr(t_mean), _lib.ptr(lo_t), _lib.ptr(hi_t), _lib.ptr(z), _lib.ptr(lp),
+                _lib.ptr(logl), _lib.ptr(out['z']) if steps > 0 else None, _lib.ptr(out['x']), _lib.ptr(out['lp']), _lib.ptr(out['logl']),
+                _lib.ptr(out['hist_z']), _lib.ptr(out['hist_x']), _lib.ptr(out['hist_logl']), _lib.ptr(out['n_accept']), C, steps,
+                ctypes.c_float(float(step_size)), int(step0) & 0xFFFFFFFFFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                int(walker_offset) & 0xFFFFFFFFFFFFFFFF, _lib.current_stream(dev)))
+        return out
+
     def mh_form_for(self, C, dynamic=False, lag=None, free=False, form=None, warm=0):
         """the K4 form (name) `mh_steps` runs for C walkers under this step rule -- asked of the library
         (nnest_mh_form_for), which knows the shapes each form is built for; None if the launch would be refused.  A caller
@@ -623,7 +670,7 @@ class HipNVP(_PaddedVectors, _HipFlow):
         self._lib = _lib.load()
         self._bind('nnest_nvp', mh='nnest_mh_constrained_steps', slice='nnest_slice_steps', ensemble='nnest_ensemble_steps',
                    ensemble_max_walkers='nnest_ensemble_max_walkers', ensemble_moves='nnest_ensemble_moves_steps',
-                   ensemble_moves_max_walkers='nnest_ensemble_moves_max_walkers')
+                   ensemble_moves_max_walkers='nnest_ensemble_moves_max_walkers', mcmc='nnest_mcmc_steps')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (_PaddedVectors)
         with torch.cuda.device(self.device):
@@ -839,6 +886,19 @@ def loglike(like_id, x_unit, like_scale, device=None, like_params=None):
         _lib.check(_lib.load().nnest_loglike(ctypes.byref(lk), _lib.ptr(x), _lib.ptr(out), x.shape[0],
                                              x.shape[1], _lib.current_stream(device)))
     return out
+
+
+def mcmc_fill_noise(steps, C, D, seed=0, step0=0, walker_offset=0, device=None):
+    """the draws of the fused random-walk Metropolis kernels (nnest_mcmc_fill_noise), exported for the checker through the kernels' own
+    functions: (eps [steps, C, D], u [steps, C]) float32, for steps step0 .. and walkers walker_offset .. (flow-independent)"""
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    dz = torch.empty(int(steps), int(C), int(D), dtype=torch.float32, device=dev)
+    u = torch.empty(int(steps), int(C), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().nnest_mcmc_fill_noise(_lib.ptr(dz), _lib.ptr(u), int(steps), int(C), int(D), int(step0) & 0xFFFFFFFFFFFFFFFF,
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset) & 0xFFFFFFFFFFFFFFFF,
+                                                     _lib.current_stream(dev)))
+    return dz, u
 
 
 def ensemble_x_max_walkers(D, like_id, device=None, moves=None):

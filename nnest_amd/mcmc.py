@@ -3,7 +3,9 @@ train the flow on a set of (normalised) training samples, then run `_mcmc_sample
 proposal ratio (loglstar = None, sampler.py:371-410).  As in the reference, `mcmc_dynamic_step_size` is accepted and not
 forwarded (mcmc.py:118-120): the chains run at the fixed step 2 / sqrt(x_dim).  With chain_stats=True the run logs the reference's
 chain statistics (acceptance, ESS, jump distance: sampler.py:451-452 every `stats_interval` steps, mcmc.py:119-120 at the end),
-computed on the GPU by nnest_amd.evaluation (plain numpy in the reference, nnest/utils/evaluation.py; no getdist involved)."""
+computed on the GPU by nnest_amd.evaluation (plain numpy in the reference, nnest/utils/evaluation.py; no getdist involved).
+`run(..., route='fused')` runs the chains inside one kernel per launch (Sampler._mcmc_sample_device) where the likelihood, the prior
+and the flow allow it; the default is the host step loop, draw for draw as before."""
 import logging
 
 import numpy as np
@@ -25,20 +27,39 @@ class MCMCSampler(Sampler):
         self.sampler = 'mcmc'
 
     def run(self, mcmc_steps, mcmc_num_chains, training_samples, mcmc_dynamic_step_size=True, stats_interval=100,
-            output_interval=None, initial_jitter=0.01, final_jitter=0.01, init_samples=None):
-        """mcmc.py:79-130"""
+            output_interval=None, initial_jitter=0.01, final_jitter=0.01, init_samples=None, route=None, seed=None):
+        """mcmc.py:79-130.  `route` and `seed` are not in the reference.  route: None or 'host' -- the reference's step loop with the
+        flow passes on the GPU and the likelihood and the prior on the host (`_mcmc_sample_host`), draw for draw on torch's and
+        numpy's streams; 'fused' -- every step inside the kernel (`_mcmc_sample_device`: nnest_mcmc_steps for the NVP,
+        nnest_spline_mcmc_steps for the spline flow; build-defined stream, the reference's move), taken where the likelihood is one
+        the kernels know and agrees with the host callable on T(x), there are no derived parameters, the prior is none or a
+        UniformPrior on T(x), num_slow = 0 and the flow has such a kernel; ValueError, naming what is not taken, otherwise.  The
+        route that ran is left in `mcmc_route`.  seed: the fused run's Philox seed (None: `_next_seed()`); the host route does not
+        use it.  Both routes keep the fixed step 2 / sqrt(x_dim)."""
+        if route not in (None, 'host', 'fused'):
+            raise ValueError("route=%r: None or 'host' (the reference's step loop) or 'fused' (build-defined stream)" % (route,))
         mean = np.mean(training_samples, axis=0)
         std = np.std(training_samples, axis=0)
         training_samples = (training_samples - mean) / std          # normalise
-        self.transform = lambda x: x * std + mean
-        self._linear_scale = None                                    # the fused kernels only know x -> s * x
-        self._fused_like_id = None
+        self._install_transform(mean, std)                           # T(x) = x * std + mean (the K4 kernels only know x -> s * x)
+        if route == 'fused':
+            why = self._mcmc_device_refusal()
+            if why is not None:
+                raise ValueError('MCMCSampler.run: the fused route does not take %s' % why)
         self.trainer.train(training_samples, jitter=initial_jitter)
-        samples, latent_samples, derived_samples, loglikes, scale, ncall = self._mcmc_sample(
-            mcmc_steps, num_chains=mcmc_num_chains, stats_interval=stats_interval, output_interval=output_interval,
-            init_samples=init_samples)   # mcmc.py:118-120 does not forward mcmc_dynamic_step_size: the chains keep a fixed step
-        if self.chain_stats:
-            self._log_chain_stats(samples, (std, mean), mcmc_steps, stats_interval, prefix_offset=1, min_step=0)
+        if route == 'fused':
+            samples, latent_samples, derived_samples, loglikes, scale, ncall = self._mcmc_sample_device(
+                mcmc_steps, num_chains=mcmc_num_chains, init_samples=init_samples, output_interval=output_interval,
+                stats_interval=stats_interval, seed=seed)
+            if self.chain_stats:   # (the interval lines were logged by the run)
+                self._log_chain_stats(samples, (std, mean), mcmc_steps, None, prefix_offset=1, min_step=0)
+        else:
+            samples, latent_samples, derived_samples, loglikes, scale, ncall = self._mcmc_sample(
+                mcmc_steps, num_chains=mcmc_num_chains, stats_interval=stats_interval, output_interval=output_interval,
+                init_samples=init_samples)   # mcmc.py:118-120 does not forward mcmc_dynamic_step_size: the chains keep a fixed step
+            if self.chain_stats:
+                self._log_chain_stats(samples, (std, mean), mcmc_steps, stats_interval, prefix_offset=1, min_step=0)
+        self.mcmc_route = 'fused' if route == 'fused' else 'host'
         samples = self.transform(samples)
         self.samples = np.concatenate((samples, derived_samples), axis=2)
         self.latent_samples = latent_samples

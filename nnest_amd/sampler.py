@@ -759,6 +759,97 @@ class Sampler(object):
             return None
         return like_id, params, lo, hi
 
+    def _install_transform(self, mean, std):
+        """T(x) = x * std + mean, also as per-dimension float arrays for the device routes"""
+        self.transform = lambda x: x * std + mean
+        self._ensemble_transform = (np.asarray(std, np.float64), np.asarray(mean, np.float64))
+        self._linear_scale = None   # (the Metropolis kernels only know x -> s * x)
+        self._fused_like_id = None
+
+    def _mcmc_device_refusal(self):
+        """why `_mcmc_sample_device` does not take this sampler (a string), or None where it does: the likelihood and the prior must
+        run on the device for the installed transform (`_ensemble_device_like`), every parameter is fast, and the flow's family
+        binds an `mcmc` entry (HipNVP, HipSpline)"""
+        if self.num_derived != 0:
+            return 'derived parameters (num_derived=%d)' % self.num_derived
+        if self.num_slow != 0:
+            return 'the fast/slow proposal (num_slow=%d)' % self.num_slow
+        netG = self.trainer.netG
+        if 'mcmc' not in getattr(netG, '_sym', ()):
+            return 'the flow %s (no fused random-walk Metropolis kernel)' % type(netG).__name__
+        if getattr(self._user_loglike, 'hip_like_id', None) is None:
+            return 'a likelihood the kernels do not know (a Python callable)'
+        if self._ensemble_device_like(self._ensemble_affine()) is None:
+            return 'this transform, likelihood or prior (an affine transform, a likelihood that agrees with the kernel\'s, and no prior or a UniformPrior on T(x))'
+        return None
+
+    def _mcmc_sample_device(self, mcmc_steps, step_size=0.0, num_chains=1, init_samples=None, max_start_tries=100, output_interval=None,
+                            stats_interval=None, seed=None, chunk_steps=None):
+        """`_mcmc_sample` with loglstar = None (sampler.py:372-416: the likelihood, the prior and the Jacobian in the ratio) with every
+        step of a launch inside the kernel (include/nnest_hip.h nnest_mcmc_steps, nnest_spline_mcmc_steps).  BUILD-DEFINED STREAM,
+        THE REFERENCE'S MOVE: parity with the host route's torch stream is statistical.  The step is fixed (`step_size`, <= 0: the
+        reference's 2 / sqrt(x_dim)).  Starts: forward(init_samples), or draws of the flow's base, the whole batch redrawn while any
+        chain's target is <= -1e30, up to `max_start_tries` times (sampler.py:275-284).  The run is cut into launches of `chunk_steps`
+        steps (default: by device memory, ENSEMBLE_HISTORY_BYTES) and at `output_interval`; the cut does not change it.  Returns the
+        reference's tuple (samples [N, S + 1, D] (x, before the transform: the start, then every step), latent_samples [N, S + 1, D],
+        derived_samples [N, S + 1, 0], loglikes [N, S + 1] (logL), scale, ncall).  Raises ValueError naming what is not taken."""
+        why = self._mcmc_device_refusal()
+        if why is not None:
+            raise ValueError('mcmc: the fused route does not take %s' % why)
+        S = int(mcmc_steps)
+        if step_size <= 0.0:
+            step_size = 2 / self.x_dim ** 0.5
+        D = self.x_dim
+        netG = self.trainer.netG
+        affine = self._ensemble_affine()
+        like_id, params, lo, hi = self._ensemble_device_like(affine)
+        seed = self._next_seed() if seed is None else int(seed)
+        kw = dict(t_std=affine[0], t_mean=affine[1], lo=lo, hi=hi, seed=seed, like_params=params)
+        if init_samples is not None:
+            z, _ = netG.forward(init_samples)
+            z = z.contiguous()
+            start, tries = netG.mcmc_steps(like_id, z, 0, step_size, **kw), 1
+        else:
+            for tries in range(1, int(max_start_tries) + 1):
+                z = netG.prior_sample(int(num_chains)).contiguous()
+                start = netG.mcmc_steps(like_id, z, 0, step_size, **kw)
+                if bool((start['lp'] > -1e30).all().item()):
+                    break
+            else:
+                raise Exception('Could not find starting value')
+        N = z.shape[0]
+        if chunk_steps is None:
+            chunk_steps = max(1, self.ENSEMBLE_HISTORY_BYTES // (N * (8 * D + 8)))
+        chunk_steps = max(1, min(int(chunk_steps), S if S > 0 else 1))
+        if output_interval:
+            chunk_steps = min(chunk_steps, int(output_interval))
+        samples = np.empty((N, S + 1, D), np.float32)
+        latent = np.empty((N, S + 1, D), np.float32)
+        loglikes = np.empty((N, S + 1))
+        derived = np.zeros((N, S + 1, 0))
+        samples[:, 0], latent[:, 0], loglikes[:, 0] = start['x'].cpu().numpy(), z.cpu().numpy(), start['logl'].cpu().numpy()
+        lp, logl = start['lp'], start['logl']
+        n_acc, done = 0, 0
+        while done < S:
+            k = min(chunk_steps, S - done)
+            res = netG.mcmc_steps(like_id, z, k, step_size, lp=lp, logl=logl, step0=done, **kw)
+            z, lp, logl = res['z'], res['lp'], res['logl']
+            n_acc += int(res['n_accept'].sum().item())
+            samples[:, 1 + done:1 + done + k] = res['hist_x'].cpu().numpy()
+            latent[:, 1 + done:1 + done + k] = res['hist_z'].cpu().numpy()
+            loglikes[:, 1 + done:1 + done + k] = res['hist_logl'].cpu().numpy()
+            done += k
+            if output_interval is not None and done % int(output_interval) == 0:
+                self._save_samples(self.transform(samples[:, :1 + done].reshape(-1, D)), loglikes[:, :1 + done].reshape(-1),
+                                   derived_samples=np.zeros((N * (1 + done), 0)))
+        if self.chain_stats and stats_interval is not None:   # sampler.py:451-452: the transformed chains up to step `it`
+            self._log_chain_stats(samples, affine, S, stats_interval, prefix_offset=1, min_step=0, final=False)
+        ncall = N * (tries + S)
+        self.total_calls += ncall
+        self.total_accepted += n_acc
+        self.total_rejected += N * S - n_acc
+        return samples, latent, derived, loglikes, step_size, ncall
+
     def _ensemble_sample(self, mcmc_steps, num_walkers, init_samples=None, init_loglikes=None, init_derived=None, loglstar=None,
                          show_progress=False, max_start_tries=100, output_interval=None, stats_interval=None, plot_trace=True,
                          moves=None, seed=None, chunk_steps=None, route=None):
@@ -944,17 +1035,17 @@ class Sampler(object):
             self.logger.info('Step [%d] acceptance [%5.4f] min ESS [%5.4f] max ESS [%5.4f] average jump [%5.4f]' %
                              (step, acceptance, np.min(ess), np.max(ess), jump_distance))
 
-    def _log_chain_stats(self, samples, affine, mcmc_steps, stats_interval, prefix_offset, min_step):
+    def _log_chain_stats(self, samples, affine, mcmc_steps, stats_interval, prefix_offset, min_step, final=True):
         """MCMCSampler / EnsembleSampler with chain_stats=True: the lines the reference logs while it samples (step `it` of
         stats_interval, on the transformed chains up to that step: prefix_offset + it states, sampler.py:451-452 and :712-713,
         steps > min_step), then once on the whole run (mcmc.py:119-120, ensemble.py:224-225).  One upload of the history; every
-        prefix is read in place through its strides, the transform applied on load."""
+        prefix is read in place through its strides, the transform applied on load.  final=False: the interval lines alone."""
         h = torch.from_numpy(np.ascontiguousarray(samples, dtype=np.float32)).to(self.trainer.netG.device)
         if stats_interval is not None:
             for it in range(int(stats_interval), int(mcmc_steps) + 1, int(stats_interval)):
                 if it > min_step and prefix_offset + it >= 2:
                     self._chain_stats(h[:, :prefix_offset + it], step=it, affine=affine)
-        if mcmc_steps > 1:
+        if final and mcmc_steps > 1:
             self._chain_stats(h, affine=affine)
 
     # ---- chain files (sampler.py:494-527): getdist text format "weight -logL params..." ------------------------

@@ -33,7 +33,8 @@ class HipSpline(_PaddedVectors, _HipFlow):
         self._lib = _lib.load()
         L = self._lib
         self._bind('nnest_spline', mh='nnest_spline_mh_constrained_steps', slice='nnest_spline_slice_steps',
-                   ensemble='nnest_spline_ensemble_steps', ensemble_max_walkers='nnest_spline_ensemble_max_walkers')
+                   ensemble='nnest_spline_ensemble_steps', ensemble_max_walkers='nnest_spline_ensemble_max_walkers',
+                   mcmc='nnest_spline_mcmc_steps')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (flow._PaddedVectors: zero-padded, exact)
         with torch.cuda.device(self.device):
