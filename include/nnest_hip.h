@@ -471,6 +471,50 @@ int nnest_spline_mcmc_steps(struct nnest_spline *spl, const nnest_like_t *like, 
                             float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, void *stream);
 int nnest_mcmc_fill_noise(float *dz_dev, float *u_dev, int steps, int C, int D, uint64_t step0, uint64_t seed, uint64_t walker_offset,
                           void *stream);
+/* IMPORTANCE-SAMPLED EVIDENCE with the trained flow as the proposal: Z = E_q[L(T(x)) pi(T(x)) / q(x)], drawn, evaluated and reduced
+ * inside one kernel.  BUILD-DEFINED: the reference has no such estimator.  Sample m is a global 64-bit index; row k of a launch of M
+ * samples is m = sample_offset + k:
+ *   draws:   z_m[4g .. 4g+3] = the four Box-Muller normals of Philox(key seed; counter (g, m, 0, 7 << 28 | m >> 32)), with the
+ *            arithmetic of nnest_mcmc_steps's normals (stream 7; streams 0-6 are taken);
+ *   target:  lp(z_m), exactly the target of nnest_mcmc_steps: x = f^-1(z), ld = log|det dx/dz|, T(x) = x * t_std + t_mean in float32,
+ *            logL = safe_loglike(T(x)), lp = (logL + ld) + prior, the prior 0 in the box [lo, hi] on T(x) (NaN inside), -inf outside;
+ *   base:    N(0, I) only: logb(z) = -1/2 sum z_d^2 - (D / 2) log 2 pi, in float64 from the float32 z;
+ *   weight:  logw_m = lp(z_m) - logb(z_m), float64.  A sample is LIVE when logw is neither NaN nor -inf; a dead one has weight 0;
+ *   sums:    a = max logw over the live samples (-inf: none), S1 = sum exp(logw - a), S2 = sum exp(2 (logw - a)), n_live; float64,
+ *            written as double sums_dev[4] = {a, S1, S2, n_live}.  (log Z over x is a + log S1 - log M; the ESS is S1^2 / S2.)
+ * The reduction is deterministic and uses no floating-point atomics: each wave keeps a running (a, S1, S2), each workgroup writes one
+ * partial into partials_dev, and a second, one-workgroup kernel combines the partials in index order; the live count is added up as
+ * an integer.  The same call made twice returns bit-identical sums.  A sample's z, x, logL and logw are functions of (seed, m) only:
+ * not of M, sample_offset, the grid, or whether the per-sample outputs were asked for; the sums of a run cut into launches and merged
+ * on the host (a = max a_i, S1 = sum S1_i e^(a_i - a), S2 = sum S2_i e^(2 (a_i - a))) agree with the single launch's up to reordered
+ * float64 addition.  The calls are asynchronous on `stream`.  (All added within ABI 15.)
+ * nnest_importance_groups: the workgroups a launch of M samples uses (a persistent grid: ceil(M / tile), capped by a multiple of the
+ *   CU count of the current device); tile = 4 (nnest_importance_evidence) or 16 (nnest_spline_importance_evidence); partials_dev
+ *   holds 3 * groups doubles.  -1: a bad argument or no device.
+ * nnest_importance_evidence: the shapes of nnest_mcmc_steps (hidden 16, 3 blocks, 1 layer, scale '', x_dim <= 128; like->scale is
+ *   ignored); one sample per wave, four waves per workgroup, the weights loaded once per workgroup.  z_out_dev, x_out_dev [M,D],
+ *   logl_out_dev, logw_out_dev [M]: the per-sample z, x = f^-1(z) (NOT T(x)), logL and logw, all four or all NULL (the sums only).
+ *   t_std_dev, t_mean_dev [D], both or both NULL (T = identity); lo_dev, hi_dev [D], both or both NULL (no prior).  M = 0 .. 2^30;
+ *   M = 0 is valid: the sums are {-inf, 0, 0, 0} and nothing else is written.  NNEST_E_UNSUPPORTED, before any launch: a
+ *   GeneralisedNormal base (nnest_nvp_set_base with beta != 0), an unknown likelihood id, another shape.
+ * nnest_spline_importance_evidence: the same through the neural-spline flow, on the team tile of nnest_spline_mcmc_steps and its
+ *   shapes: 16 samples per workgroup and pass, four waves; rows >= M of the last tile evaluate their point and are neither counted nor
+ *   written; the four waves hold identical sums and one of them publishes.
+ * nnest_importance_fill_noise: the draws above as an array, through the kernels' own function: z_dev [M, D] float32.
+ * nnest_importance_check, nnest_spline_importance_check: NNEST_OK where the entry takes this handle (its shape and base) and this
+ *   likelihood id, else NNEST_E_UNSUPPORTED with the reason in nnest_hip_last_error(), as the entry itself would answer; nothing is
+ *   launched: a front end asks before it chooses its route. */
+int nnest_importance_groups(int M, int tile);
+int nnest_importance_check(nnest_nvp_t *nvp, int like_id);
+int nnest_spline_importance_check(struct nnest_spline *spl, int like_id);
+int nnest_importance_evidence(nnest_nvp_t *nvp, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                              const float *hi_dev, float *z_out_dev, float *x_out_dev, double *logl_out_dev, double *logw_out_dev,
+                              double *partials_dev, double *sums_dev, int M, uint64_t seed, uint64_t sample_offset, void *stream);
+int nnest_spline_importance_evidence(struct nnest_spline *spl, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                                     const float *lo_dev, const float *hi_dev, float *z_out_dev, float *x_out_dev, double *logl_out_dev,
+                                     double *logw_out_dev, double *partials_dev, double *sums_dev, int M, uint64_t seed,
+                                     uint64_t sample_offset, void *stream);
+int nnest_importance_fill_noise(float *z_dev, int M, int D, uint64_t seed, uint64_t sample_offset, void *stream);
 /* size of sync_dev in 8-byte words for a launch of `steps` steps */
 int nnest_mh_sync_words(int steps);
 /* number of adaptation groups nnest_mh_constrained_steps uses for C walkers (size of scale_out_dev) */

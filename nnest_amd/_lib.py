@@ -8,6 +8,7 @@ shared with torch tensors).
 """
 import os
 import ctypes
+import math
 
 import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 
@@ -221,6 +222,12 @@ SIGNATURES = {
     'nnest_spline_mcmc_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64, _u64, _u64,
                                 _vp],
     'nnest_mcmc_fill_noise': [_vp, _vp, _i, _i, _i, _u64, _u64, _u64, _vp],
+    'nnest_importance_groups': [_i, _i],
+    'nnest_importance_check': [_vp, _i],
+    'nnest_spline_importance_check': [_vp, _i],
+    'nnest_importance_evidence': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u64, _u64, _vp],
+    'nnest_spline_importance_evidence': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u64, _u64, _vp],
+    'nnest_importance_fill_noise': [_vp, _i, _i, _u64, _u64, _vp],
     'nnest_host_prior_consume': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  ctypes.c_longlong, _d, ctypes.c_longlong, ctypes.c_longlong, _d, _d, _i],
     'nnest_chain_stats_work_words': [_i, _i, _i],
@@ -237,6 +244,35 @@ CHAIN_STATS_ALL_LAGS, CHAIN_STATS_NO_ESS, CHAIN_STATS_RHAT_AT_MEAN = 1, 2, 4   #
 HOST_FINISHED, HOST_RETRAIN, HOST_NEED_SAMPLES, HOST_LOG, HOST_CHECKPOINT, HOST_DEAD_FULL = range(6)   # include/nnest_hip.h NNEST_HOST_*
 HOST_EXPIRED = 6
 HOST_TOP, HOST_AFTER_TRAIN, HOST_AFTER_SAMPLES, HOST_AFTER_LOG = range(4)
+
+
+def merge_importance(parts):
+    """the sums (a, S1, S2, n_live) of the union of sample sets from the sums of each (include/nnest_hip.h
+    nnest_importance_evidence): a = max a_i, S1 = sum S1_i e^(a_i - a), S2 = sum S2_i e^(2 (a_i - a)); float64"""
+    parts = [tuple(float(v) for v in p) for p in parts]
+    a = max([p[0] for p in parts], default=-math.inf)
+    s1 = s2 = n = 0.0
+    for ai, s1i, s2i, ni in parts:
+        if ai == -math.inf:   # (nothing live in this part: its sums are 0)
+            continue
+        e = math.exp(ai - a)
+        s1 += s1i * e
+        s2 += s2i * e * e
+        n += ni
+    return a, s1, s2, n
+
+
+def importance_result(a, S1, S2, n_live, M):
+    """the estimate from the sums of M samples: logz_x = a + log S1 - log M (log Z over x), ess = S1^2 / S2,
+    logzerr = sqrt((M / ess - 1) / (M - 1)) (the delta-method standard error of log Z: the relative standard error of the mean
+    weight), max_weight_share = 1 / S1 (the largest weight's share of the total).  Everything dead: logz_x = -inf, ess = 0,
+    logzerr = inf"""
+    M = int(M)
+    if not (M > 0 and n_live > 0 and S1 > 0.0 and a > -math.inf):
+        return dict(logz_x=-math.inf, ess=0.0, logzerr=math.inf, max_weight_share=math.nan, n_live=int(n_live), n_samples=M)
+    ess = S1 * S1 / S2
+    err = math.sqrt(max(M / ess - 1.0, 0.0) / (M - 1)) if M > 1 else math.inf
+    return dict(logz_x=a + math.log(S1) - math.log(M), ess=ess, logzerr=err, max_weight_share=1.0 / S1, n_live=int(n_live), n_samples=M)
 
 
 class HostState(ctypes.Structure):   # nnest_host_state_t

@@ -9,6 +9,7 @@
 #include "mh_common.h"
 #include "ensemble_common.h"
 #include "mcmc_walk.h"
+#include "importance_walk.h"
 
 using namespace nnest;
 
@@ -424,6 +425,19 @@ int nnest::mcmc_args(McmcArgs *a, const float *t_std, const float *t_mean, const
     a->C = C; a->S = steps; a->step = step_size; a->step0 = (uint32_t)step0; a->seed = seed; a->walker_offset = walker_offset;
     return NNEST_OK;
 }
+int nnest::importance_args(ImpArgs *a, const float *t_std, const float *t_mean, const float *lo, const float *hi, float *z_out, float *x_out,
+                           double *logl_out, double *logw_out, double *partials, double *sums, int M, uint64_t seed, uint64_t sample_offset) {
+    if (M < 0 || M > (1 << 30)) return fail(NNEST_E_ARG, "importance: M=%d (0 .. 2^30 samples a launch)", M);
+    if (!sums || (M > 0 && !partials)) return fail(NNEST_E_ARG, "importance: NULL sums_dev or partials_dev");
+    if (!t_std != !t_mean) return fail(NNEST_E_ARG, "t_std_dev and t_mean_dev: both or neither");
+    if (!lo != !hi) return fail(NNEST_E_ARG, "lo_dev and hi_dev: both or neither");
+    if ((!z_out != !x_out) || (!z_out != !logl_out) || (!z_out != !logw_out))
+        return fail(NNEST_E_ARG, "z_out_dev, x_out_dev, logl_out_dev and logw_out_dev: all or none");
+    a->t_std = t_std; a->t_mean = t_mean; a->lo = lo; a->hi = hi;
+    a->z_out = z_out; a->x_out = x_out; a->logl_out = logl_out; a->logw_out = logw_out;
+    a->partials = partials; a->sums = sums; a->M = M; a->seed = seed; a->sample_offset = sample_offset;
+    return NNEST_OK;
+}
 int nnest::ensemble_sizes(int C, int steps) {
     if (C < 2 || C > (1 << 16) || steps < 0) return fail(NNEST_E_ARG, "ensemble: C=%d (2..65536 walkers) steps=%d", C, steps);
     if (nnest_ensemble_work_words(C, steps) < 0) return fail(NNEST_E_ARG, "ensemble: C=%d x steps=%d: the work buffer exceeds 2^31 words", C, steps);
@@ -505,6 +519,54 @@ int nnest_mcmc_fill_noise(float *dz_dev, float *u_dev, int steps, int C, int D, 
                           void *stream) {
     if (steps < 0 || C < 0 || D < 1) return fail(NNEST_E_ARG, "mcmc_fill_noise: steps=%d C=%d D=%d", steps, C, D);
     HIP_TRY(launch_mcmc_fill_noise(dz_dev, u_dev, steps, C, D, (uint32_t)step0, seed, walker_offset, (hipStream_t)stream));
+    return NNEST_OK;
+}
+
+// what nnest_importance_evidence takes, asked before a launch (and by the entry itself): the refusals name their reason
+int nnest_importance_check(nnest_nvp_t *h, int like_id) {
+    if (!h) return fail(NNEST_E_ARG, "NULL handle");
+    if (like_id < 0 || like_id >= NNEST_LIKE_COUNT) return fail(NNEST_E_UNSUPPORTED, "importance: unknown likelihood id %d", like_id);
+    if (h->s.base_beta != 0.f)
+        return fail(NNEST_E_UNSUPPORTED, "importance: GeneralisedNormal base (beta=%g): the kernel draws from N(0, I) only", (double)h->s.base_beta);
+    if (!ensemble_form_eligible(h->s))
+        return fail(NNEST_E_UNSUPPORTED, "importance: x_dim=%d hidden=%d blocks=%d layers=%d scale mode %d: the kernel takes hidden 16, 3 blocks, "
+                    "1 layer, scale '' (the one-sample-per-wave layout), x_dim <= 128", h->s.D, h->s.H, h->s.B, h->s.L, h->s.scale_mode);
+    if (h->s.NT < 1 || h->s.NT > 4) return fail(NNEST_E_UNSUPPORTED, "importance: x_dim=%d not instantiated", h->s.D);
+    return NNEST_OK;
+}
+
+// (as nnest_mcmc_steps: the checks that need no handle come first)
+int nnest_importance_evidence(nnest_nvp_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                              const float *hi_dev, float *z_out_dev, float *x_out_dev, double *logl_out_dev, double *logw_out_dev,
+                              double *partials_dev, double *sums_dev, int M, uint64_t seed, uint64_t sample_offset, void *stream) {
+    if (!like) return fail(NNEST_E_ARG, "like is NULL");
+    ImpArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc = importance_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_out_dev, x_out_dev, logl_out_dev, logw_out_dev, partials_dev,
+                             sums_dev, M, seed, sample_offset);
+    if (rc) return rc;
+    if ((rc = nnest_importance_check(h, like->id))) return rc;
+    if ((rc = check_like(like, h->s.D, &a.like))) return rc;
+    a.like.scale = 1.0f;
+    a.groups = importance_groups(M, IMP_NVP_TILE, h->num_cu);
+    const hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(launch_importance_begin(sums_dev, st));
+    HIP_TRY(launch_importance(h->s, h->w, a, st));
+    HIP_TRY(launch_importance_combine(partials_dev, sums_dev, a.groups, st));
+    return NNEST_OK;
+}
+
+int nnest_importance_groups(int M, int tile) {
+    if (M < 0 || (tile != IMP_NVP_TILE && tile != IMP_SPLINE_TILE)) return -1;
+    int dev = 0;
+    hipDeviceProp_t p;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return -1;
+    return importance_groups(M, tile, p.multiProcessorCount);
+}
+
+int nnest_importance_fill_noise(float *z_dev, int M, int D, uint64_t seed, uint64_t sample_offset, void *stream) {
+    if (M < 0 || D < 1 || (M > 0 && !z_dev)) return fail(NNEST_E_ARG, "importance_fill_noise: M=%d D=%d z_dev=%p", M, D, (void *)z_dev);
+    HIP_TRY(launch_importance_fill_noise(z_dev, M, D, seed, sample_offset, (hipStream_t)stream));
     return NNEST_OK;
 }
 

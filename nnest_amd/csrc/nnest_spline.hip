@@ -16,6 +16,7 @@
 
 #include "ensemble_common.h"
 #include "mcmc_walk.h"
+#include "importance_walk.h"
 #include "nnest_internal.h"
 #include "mh_common.h"
 
@@ -440,6 +441,45 @@ int nnest_spline_mcmc_steps(nnest_spline_t *h, const nnest_like_t *like, const f
     if (e == hipErrorInvalidConfiguration)
         return spline_fail(NNEST_E_UNSUPPORTED, "spline mcmc: x_dim=%d hidden_dim=%d not instantiated", h->s.D, h->s.H);
     if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_mcmc: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+// what nnest_spline_importance_evidence takes, asked before a launch (and by the entry itself): the refusals name their reason
+int nnest_spline_importance_check(nnest_spline_t *h, int like_id) {
+    if (!h) return spline_fail(NNEST_E_ARG, "NULL handle");
+    if (like_id < 0 || like_id >= NNEST_LIKE_COUNT) return spline_fail(NNEST_E_UNSUPPORTED, "importance: unknown likelihood id %d", like_id);
+    if (h->s.base_beta != 0.f)
+        return spline_fail(NNEST_E_UNSUPPORTED, "importance: GeneralisedNormal base (beta=%g): the kernel draws from N(0, I) only",
+                           (double)h->s.base_beta);
+    ImpArgs probe;
+    memset(&probe, 0, sizeof(probe));   // (M = 0: the shape's verdict, nothing is launched)
+    if (launch_spline_importance(SplArgs{h->img, h->s}, probe, nullptr) == hipErrorInvalidConfiguration)
+        return spline_fail(NNEST_E_UNSUPPORTED, "spline importance: x_dim=%d hidden_dim=%d not instantiated (the team tile's shapes)", h->s.D,
+                           h->s.H);
+    return NNEST_OK;
+}
+
+// the importance-sampled evidence through the spline flow (nnest_spline_importance.hip); the argument checks of
+// nnest_importance_evidence
+int nnest_spline_importance_evidence(nnest_spline_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                                     const float *lo_dev, const float *hi_dev, float *z_out_dev, float *x_out_dev, double *logl_out_dev,
+                                     double *logw_out_dev, double *partials_dev, double *sums_dev, int M, uint64_t seed,
+                                     uint64_t sample_offset, void *stream) {
+    if (!like) return spline_fail(NNEST_E_ARG, "like is NULL");
+    ImpArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc = importance_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_out_dev, x_out_dev, logl_out_dev, logw_out_dev, partials_dev,
+                             sums_dev, M, seed, sample_offset);
+    if (rc) return rc;
+    if ((rc = nnest_spline_importance_check(h, like->id))) return rc;
+    if ((rc = scheck_like(like, h->s.D, &a.like))) return rc;
+    a.like.scale = 1.0f;
+    a.groups = importance_groups(M, IMP_SPLINE_TILE, h->num_cu);
+    const hipStream_t st = (hipStream_t)stream;
+    SHIP_TRY(launch_importance_begin(sums_dev, st));
+    hipError_t e = launch_spline_importance(SplArgs{h->img, h->s}, a, st);
+    if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_importance: %s", hipGetErrorString(e));
+    SHIP_TRY(launch_importance_combine(partials_dev, sums_dev, a.groups, st));
     return NNEST_OK;
 }
 

@@ -68,6 +68,7 @@ class _HipFlow(object):
     base_beta = 0.0   # 0: N(0, I); > 0: GeneralisedNormal(0, 1, beta)
     base_dist = None  # the distribution object handed to Trainer(base_dist=...), if any
 
+    _IMPORTANCE_TILE = 4   # samples per workgroup and pass of the family's `importance` kernel (nnest_importance_groups)
     _FAMILY_ENTRIES = ('forward', 'inverse', 'log_probs', 'inverse_loglike', 'set_base', 'loss_grad', 'vjp', 'adam_step', 'destroy')
 
     def _bind(self, family, **named):
@@ -433,6 +434,59 @@ class _HipFlow(object):
                 int(walker_offset) & 0xFFFFFFFFFFFFFFFF, _lib.current_stream(dev)))
         return out
 
+    def importance_refusal(self, like_id):
+        """why `importance_evidence` would refuse this flow (its shape, its base) or this likelihood id -- the library's own words
+        (the family's `importance_check` entry; nothing is launched) --, or None where it is taken.  NotImplementedError for a
+        family without such a kernel"""
+        fn = self._sym.get('importance_check')
+        if fn is None or 'importance' not in self._sym:
+            raise NotImplementedError('no fused importance-sampling kernel for %s' % type(self).__name__)
+        with torch.cuda.device(self.device):
+            rc = fn(self._h, int(like_id))
+        if rc == _lib.NNEST_OK:
+            return None
+        msg = self._lib.nnest_hip_last_error()
+        return msg.decode() if msg else 'error %d' % rc
+
+    def importance_evidence(self, like_id, M, t_std=None, t_mean=None, lo=None, hi=None, seed=0, sample_offset=0, like_params=None,
+                            want_samples=False):
+        """the sums of the importance-sampled evidence with this flow as the proposal, M samples drawn, evaluated and reduced in ONE
+        launch (the family's `importance` entry point: nnest_importance_evidence, nnest_spline_importance_evidence; build-defined:
+        include/nnest_hip.h has the definition).  The likelihood `like_id` sees T(x) = x * t_std + t_mean (per dimension; None:
+        identity); lo / hi [D]: the prior box on T(x) (None: no prior); sample_offset: the global index of sample 0 -- a sample
+        depends on (seed, global index) only, so a run cut into launches is the same run.  Returns a dict: sums [4] float64 on the
+        device ({a, S1, S2, n_live}: _lib.merge_importance / importance_result read them) and, with want_samples, z, x [M, D]
+        float32 (x before T), logl, logw [M] float64.  Asynchronous on the current stream.  NotImplementedError for a family
+        without such a kernel (its handle must not reach another family's)."""
+        fn = self._sym.get('importance')
+        if fn is None:
+            raise NotImplementedError('no fused importance-sampling kernel for %s' % type(self).__name__)
+        dev = self.device
+        M, D = int(M), self.D
+        if M < 0:
+            raise ValueError('importance_evidence: M=%d' % M)
+        if (t_std is None) != (t_mean is None):
+            raise ValueError('importance_evidence: t_std and t_mean: both or neither')
+        f32 = dict(dtype=torch.float32, device=dev)
+        f64 = dict(dtype=torch.float64, device=dev)
+        vec = lambda v: None if v is None else _as_dev_f32(np.asarray(v, np.float32).reshape(1, D), dev).reshape(D)
+        t_std, t_mean, lo_t, hi_t = vec(t_std), vec(t_mean), vec(lo), vec(hi)
+        out = dict(sums=torch.empty(4, **f64))
+        if want_samples:
+            out.update(z=torch.empty(M, D, **f32), x=torch.empty(M, D, **f32), logl=torch.empty(M, **f64), logw=torch.empty(M, **f64))
+        with torch.cuda.device(dev):
+            groups = int(self._lib.nnest_importance_groups(M, self._IMPORTANCE_TILE))
+            if groups < 0:
+                raise _lib.NnestHipError('nnest_importance_groups(%d, %d) failed' % (M, self._IMPORTANCE_TILE))
+            partials = torch.empty(3 * max(groups, 1), **f64)
+            lk = _lib.like_spec(like_id, 1.0, like_params)
+            _lib.check(fn(
+                self._h, ctypes.byref(lk), _lib.ptr(t_std), _lib.ptr(t_mean), _lib.ptr(lo_t), _lib.ptr(hi_t), _lib.ptr(out.get('z')),
+                _lib.ptr(out.get('x')), _lib.ptr(out.get('logl')), _lib.ptr(out.get('logw')), _lib.ptr(partials), _lib.ptr(out['sums']), M,
+                int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset) & 0xFFFFFFFFFFFFFFFF, _lib.current_stream(dev)))
+        out['groups'] = groups
+        return out
+
     def mh_form_for(self, C, dynamic=False, lag=None, free=False, form=None, warm=0):
         """the K4 form (name) `mh_steps` runs for C walkers under this step rule -- asked of the library
         (nnest_mh_form_for), which knows the shapes each form is built for; None if the launch would be refused.  A caller
@@ -670,7 +724,8 @@ class HipNVP(_PaddedVectors, _HipFlow):
         self._lib = _lib.load()
         self._bind('nnest_nvp', mh='nnest_mh_constrained_steps', slice='nnest_slice_steps', ensemble='nnest_ensemble_steps',
                    ensemble_max_walkers='nnest_ensemble_max_walkers', ensemble_moves='nnest_ensemble_moves_steps',
-                   ensemble_moves_max_walkers='nnest_ensemble_moves_max_walkers', mcmc='nnest_mcmc_steps')
+                   ensemble_moves_max_walkers='nnest_ensemble_moves_max_walkers', mcmc='nnest_mcmc_steps',
+                   importance='nnest_importance_evidence', importance_check='nnest_importance_check')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (_PaddedVectors)
         with torch.cuda.device(self.device):
@@ -899,6 +954,17 @@ def mcmc_fill_noise(steps, C, D, seed=0, step0=0, walker_offset=0, device=None):
                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset) & 0xFFFFFFFFFFFFFFFF,
                                                      _lib.current_stream(dev)))
     return dz, u
+
+
+def importance_fill_noise(M, D, seed=0, sample_offset=0, device=None):
+    """the draws of the fused importance-sampling kernels (nnest_importance_fill_noise), exported for the checker through the kernels'
+    own function: z [M, D] float32, for samples sample_offset .. (flow-independent)"""
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    z = torch.empty(int(M), int(D), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().nnest_importance_fill_noise(_lib.ptr(z), int(M), int(D), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                           int(sample_offset) & 0xFFFFFFFFFFFFFFFF, _lib.current_stream(dev)))
+    return z
 
 
 def ensemble_x_max_walkers(D, like_id, device=None, moves=None):

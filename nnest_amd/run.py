@@ -56,8 +56,18 @@ def main(args):
                'retrains': sampler.num_retrains, 'batches': sampler.num_batches,
                'train_epochs_total': int(sampler.trainer.total_iters)}
     print(json.dumps(summary))
-    with open(os.path.join(sampler.logs['results'], 'summary.json'), 'w') as f:
+    path = os.path.join(sampler.logs['results'], 'summary.json')
+    with open(path, 'w') as f:
         json.dump(summary, f, indent=1)
+    if args.importance_samples > 0:   # a second estimate of log Z, independent of the chain length (Sampler.importance_evidence);
+        # after the run's summary is out and on disk: nothing that happens here can lose it
+        imp = sampler.importance_evidence(args.importance_samples)
+        print('log Z [%5.4f +- %5.4f] importance-sampled [%5.4f +- %5.4f] (%d samples, ESS %.1f, route %s)' % (
+            sampler.logz, sampler.logzerr, imp['logz'], imp['logzerr'], imp['n_samples'], imp['ess'], imp['route']))
+        summary.update(importance_logz=imp['logz'], importance_logzerr=imp['logzerr'], importance_ess=imp['ess'],
+                       importance_samples=imp['n_samples'], importance_route=imp['route'])
+        with open(path, 'w') as f:
+            json.dump(summary, f, indent=1)
 
 
 if __name__ == '__main__':
@@ -85,4 +95,5 @@ if __name__ == '__main__':
     p.add_argument('--scale', type=str, default='')
     p.add_argument('--mcmc_proposal', type=str, default='mh', choices=('mh', 'slice'))   # 'slice': build-defined, not in the reference
     p.add_argument('--chain_stats', action='store_true')   # acceptance / ESS / jump distance of each logged batch in results.csv (GPU)
+    p.add_argument('--importance_samples', type=int, default=0)   # > 0: the importance-sampled log Z from the last flow, printed beside log Z
     main(p.parse_args())

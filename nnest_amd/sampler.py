@@ -734,19 +734,13 @@ class Sampler(object):
             return np.full(self.x_dim, self._linear_scale), np.zeros(self.x_dim)
         return None
 
-    def _ensemble_device_like(self, affine):
-        """(like_id, like_params, lo, hi) when the likelihood and the prior run on the device for the transform `affine`, else None:
-        a likelihood the kernels know (checked against the host callable), no derived parameters, and no prior or a box on T(x)"""
+    def _device_likelihood(self, affine):
+        """(like_id, like_params) when the likelihood runs on the device for the transform `affine` (std, mean), else None: a
+        likelihood the kernels know, checked against the host callable on T(x), and no derived parameters"""
         like = self._user_loglike
         like_id = getattr(like, 'hip_like_id', None)
         if like_id is None or affine is None or self.num_derived != 0:
             return None
-        prior = self._user_prior
-        lo = hi = None
-        if prior is not None:
-            if not (self._transform_prior and isinstance(prior, UniformPrior) and type(prior).__call__ is UniformPrior.__call__):
-                return None
-            lo, hi = np.asarray(prior.minimum, np.float32), np.asarray(prior.maximum, np.float32)
         from . import flow
         params = tuple(getattr(like, 'hip_like_params', ()) or ())
         std, mean = (np.asarray(v, np.float32) for v in affine)
@@ -757,7 +751,21 @@ class Sampler(object):
         if not np.allclose(dev, host, rtol=1e-5, atol=1e-4):
             self.logger.warning('ensemble: likelihood id %d disagrees with the host callable; using the host protocol' % like_id)
             return None
-        return like_id, params, lo, hi
+        return like_id, params
+
+    def _ensemble_device_like(self, affine):
+        """(like_id, like_params, lo, hi) when the likelihood and the prior run on the device for the transform `affine`, else None:
+        a likelihood the kernels know (checked against the host callable), no derived parameters, and no prior or a box on T(x)"""
+        if getattr(self._user_loglike, 'hip_like_id', None) is None or affine is None or self.num_derived != 0:
+            return None
+        prior = self._user_prior
+        lo = hi = None
+        if prior is not None:
+            if not (self._transform_prior and isinstance(prior, UniformPrior) and type(prior).__call__ is UniformPrior.__call__):
+                return None
+            lo, hi = np.asarray(prior.minimum, np.float32), np.asarray(prior.maximum, np.float32)
+        got = self._device_likelihood(affine)
+        return None if got is None else got + (lo, hi)
 
     def _install_transform(self, mean, std):
         """T(x) = x * std + mean, also as per-dimension float arrays for the device routes"""
@@ -782,6 +790,146 @@ class Sampler(object):
         if self._ensemble_device_like(self._ensemble_affine()) is None:
             return 'this transform, likelihood or prior (an affine transform, a likelihood that agrees with the kernel\'s, and no prior or a UniformPrior on T(x))'
         return None
+
+    # ---- importance-sampled evidence from the trained flow (build-defined: the reference has none) ---------------------------------
+    IMPORTANCE_CHUNK = 1 << 22   # samples per launch when nothing per sample comes back
+
+    def _prior_is_unit_box_on_x(self):
+        """the NestedSampler's prior: the unit box on x, not on T(x) (`transform_prior=False`)"""
+        prior = self._user_prior
+        return prior is not None and not self._transform_prior and bool(getattr(prior, 'is_unit_box', lambda: False)())
+
+    def _importance_device_like(self, affine):
+        """`_ensemble_device_like` for the evidence: (like_id, like_params, lo, hi).  Beside no prior and a UniformPrior on T(x) it
+        takes the NestedSampler's prior, the unit box on x, under x -> s * x (`_linear_scale`): the box on T(x) is +-|s|"""
+        if not (self._prior_is_unit_box_on_x() and self._linear_scale is not None):
+            return self._ensemble_device_like(affine)
+        got = self._device_likelihood(affine)
+        if got is None:
+            return None
+        s = abs(float(self._linear_scale))
+        return got + (np.full(self.x_dim, -s, np.float32), np.full(self.x_dim, s, np.float32))
+
+    def _importance_constant(self, affine):
+        """what turns the weights' log Z over x into `importance_evidence`'s logz (its docstring has the convention)"""
+        if self._user_prior is not None and not self._transform_prior:   # a prior on x: Z over x is the evidence already
+            return -self.x_dim * np.log(2.0) if self._prior_is_unit_box_on_x() else 0.0   # (the unit box, normalised: 2^-D)
+        if affine is None:
+            return 0.0
+        return float(np.sum(np.log(np.abs(np.asarray(affine[0], np.float64)))))
+
+    def _importance_device_refusal(self):
+        """why the fused route of `importance_evidence` does not take this sampler (a string), or None where it does: the
+        conditions of `_mcmc_device_refusal` (with the unit box on x of the NestedSampler taken too), and what the library says of
+        the flow's shape and base (`importance_refusal`: nothing is launched)"""
+        if self.num_derived != 0:
+            return 'derived parameters (num_derived=%d)' % self.num_derived
+        if self.num_slow != 0:
+            return 'the fast/slow proposal (num_slow=%d)' % self.num_slow
+        netG = self.trainer.netG
+        if 'importance' not in getattr(netG, '_sym', ()):
+            return 'the flow %s (no fused importance-sampling kernel)' % type(netG).__name__
+        like_id = getattr(self._user_loglike, 'hip_like_id', None)
+        if like_id is None:
+            return 'a likelihood the kernels do not know (a Python callable)'
+        why = netG.importance_refusal(like_id)
+        if why is not None:
+            return 'the flow %s: %s' % (type(netG).__name__, why)
+        if self._importance_device_like(self._ensemble_affine()) is None:
+            return 'this transform, likelihood or prior (an affine transform, a likelihood that agrees with the kernel\'s, and no prior, a UniformPrior on T(x) or the unit box on x)'
+        return None
+
+    def _importance_host_sums(self, n):
+        """the sums (a, S1, S2, n_live) of n samples of the flow with the user's callables on the host, and (T(x), logw)"""
+        netG = self.trainer.netG
+        x_t = netG.sample(int(n))
+        logq = netG.log_probs(x_t).double().cpu().numpy()
+        x = x_t.cpu().numpy()
+        logl, _ = self.loglike(x)                  # (safe: non-finite -> -1e100; counts the calls)
+        logw = logl + np.asarray(self.prior(x), np.float64) - logq
+        live = ~(np.isnan(logw) | (logw == -np.inf))
+        if not live.any():
+            return (-np.inf, 0.0, 0.0, 0.0), x, logw
+        a = float(np.max(logw[live]))
+        e = np.exp(logw[live] - a)
+        return (a, float(e.sum()), float((e * e).sum()), float(live.sum())), x, logw
+
+    def importance_evidence(self, num_samples, seed=None, route=None, chunk=None, return_samples=False):
+        """The evidence by importance sampling with the trained flow as the proposal (build-defined; the reference has none):
+        Z = E_q[L(T(x)) pi(T(x)) / q(x)] over `num_samples` exact draws of the flow -- an estimate that does not depend on how well
+        any chain has mixed, with an error bar and an effective sample size.  For every front end, once a flow has been trained.
+        route: 'fused' -- drawn, evaluated and reduced inside the kernel (include/nnest_hip.h nnest_importance_evidence,
+        nnest_spline_importance_evidence), in launches of `chunk` samples addressed by their global index (the cut does not change
+        a sample; chunk defaults to 2^22, or by ENSEMBLE_HISTORY_BYTES when samples come back); taken where `_mcmc_sample_device`
+        would take the sampler (a likelihood the kernels know, no derived or slow parameters, an affine transform, no prior or a
+        UniformPrior on T(x), HipNVP in the default shape or HipSpline) or the prior is the NestedSampler's unit box on x, and the
+        base is N(0, I); ValueError, naming what is not taken, otherwise.  'host' -- netG.sample / netG.log_probs with the
+        likelihood and the prior as the host Metropolis route evaluates them: every flow, base, prior and Python likelihood.
+        None -- 'fused' where it is taken, 'host' otherwise.  seed: the fused route's Philox seed (None: `_next_seed()`).
+        CONVENTION of logz: the weights estimate Z over x.  With no prior, or a prior evaluated on T(x) (`transform_prior`, the
+        default), and an affine transform, sum log|t_std| is added: the result is log of the integral of L(theta) pi(theta) d theta
+        with pi as the prior callable returns it (the UniformPrior is the UNNORMALISED indicator of its box); under a transform that
+        is not affine (host route only) nothing is added and Z stays over x.  With a prior evaluated on x (`transform_prior=False`)
+        Z over x is the evidence already and nothing is added, whatever the transform; where that prior is the unit box on x
+        (NestedSampler) it is taken as the normalised 2^-D and the result is logz_x - D log 2: directly comparable with
+        NestedSampler's `logz`.
+        Returns a dict: logz, logzerr (the delta-method standard error of log Z), ess, n_samples, n_live, max_weight_share, route;
+        with return_samples also samples (T(x), as `self.transform` gives it) [n, D] and logw [n] (the log weights over x:
+        logsumexp(logw) - log n is logz less the convention's constant).  Leaves the route in `importance_route`, logs one line."""
+        if route not in (None, 'host', 'fused'):
+            raise ValueError("route=%r: None, 'host' or 'fused'" % (route,))
+        M = int(num_samples)
+        if M < 1:
+            raise ValueError('importance_evidence: num_samples=%d' % M)
+        why = None if route == 'host' else self._importance_device_refusal()
+        if route == 'fused' and why is not None:
+            raise ValueError('importance_evidence: the fused route does not take %s' % why)
+        route = 'fused' if (route != 'host' and why is None) else 'host'
+        D = self.x_dim
+        parts, xs, lws = [], [], []
+        if route == 'fused':
+            netG = self.trainer.netG
+            affine = self._ensemble_affine()
+            like_id, params, lo, hi = self._importance_device_like(affine)
+            seed = self._next_seed() if seed is None else int(seed)
+            if chunk is None:
+                chunk = max(1, self.ENSEMBLE_HISTORY_BYTES // (8 * D + 16)) if return_samples else self.IMPORTANCE_CHUNK
+            chunk = max(1, min(int(chunk), 1 << 30))
+            sums = []
+            for first in range(0, M, chunk):
+                k = min(chunk, M - first)
+                res = netG.importance_evidence(like_id, k, t_std=affine[0], t_mean=affine[1], lo=lo, hi=hi, seed=seed,
+                                               sample_offset=first, like_params=params, want_samples=return_samples)
+                sums.append(res['sums'])
+                if return_samples:
+                    xs.append(res['x'].cpu().numpy())
+                    lws.append(res['logw'].cpu().numpy())
+            parts = [tuple(t.cpu().numpy()) for t in sums]
+            self.total_calls += M
+        else:
+            if chunk is None:
+                chunk = 1 << 16
+            chunk = max(1, int(chunk))
+            for first in range(0, M, chunk):
+                p, x, lw = self._importance_host_sums(min(chunk, M - first))
+                parts.append(p)
+                if return_samples:
+                    xs.append(x)
+                    lws.append(lw)
+            affine = self._ensemble_affine()
+        const = self._importance_constant(affine)
+        a, s1, s2, n_live = _lib.merge_importance(parts)
+        r = _lib.importance_result(a, s1, s2, n_live, M)
+        out = dict(logz=r['logz_x'] + const if r['logz_x'] > -np.inf else -np.inf, logzerr=r['logzerr'], ess=r['ess'], n_samples=M,
+                   n_live=r['n_live'], max_weight_share=r['max_weight_share'], route=route)
+        if return_samples:
+            out['samples'] = np.asarray(self.transform(np.concatenate(xs, axis=0)))
+            out['logw'] = np.concatenate(lws, axis=0)
+        self.importance_route = route
+        if self.single_or_primary_process:
+            self.logger.info('importance: log Z [%5.4f +- %5.4f] ESS [%.1f of %d] live [%d] max weight share [%.3g] route [%s]' % (
+                out['logz'], out['logzerr'], out['ess'], M, out['n_live'], out['max_weight_share'], route))
+        return out
 
     def _mcmc_sample_device(self, mcmc_steps, step_size=0.0, num_chains=1, init_samples=None, max_start_tries=100, output_interval=None,
                             stats_interval=None, seed=None, chunk_steps=None):

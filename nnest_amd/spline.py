@@ -19,6 +19,7 @@ from .flow import _HipFlow, _PaddedVectors, _as_dev_f32, pad_index, native_hidde
 
 
 class HipSpline(_PaddedVectors, _HipFlow):
+    _IMPORTANCE_TILE = 16   # (the team tile of nnest_spline_importance_evidence)
 
     def __init__(self, num_inputs, hidden_dim=16, num_blocks=3, num_bins=8, tail_bound=3.0, device=None, seed=None):
         if not torch.cuda.is_available():
@@ -34,7 +35,8 @@ class HipSpline(_PaddedVectors, _HipFlow):
         L = self._lib
         self._bind('nnest_spline', mh='nnest_spline_mh_constrained_steps', slice='nnest_spline_slice_steps',
                    ensemble='nnest_spline_ensemble_steps', ensemble_max_walkers='nnest_spline_ensemble_max_walkers',
-                   mcmc='nnest_spline_mcmc_steps')
+                   mcmc='nnest_spline_mcmc_steps', importance='nnest_spline_importance_evidence',
+                   importance_check='nnest_spline_importance_check')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (flow._PaddedVectors: zero-padded, exact)
         with torch.cuda.device(self.device):
