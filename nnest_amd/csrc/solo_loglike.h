@@ -110,7 +110,7 @@ static __device__ __forceinline__ double solo_loglike(const LikeSpec &lk_in, int
             for (int k = 0; k < 2; ++k) {
                 const double sig = (double)lk.p[3 * k], rs = (double)lk.p[3 * k + 1], cen = (double)lk.p[3 * k + 2];
                 double r2 = s2 - 2.0 * cen * s1 + Dd * cen * cen;
-                double rad = sqrt(r2 > 0.0 ? r2 : 0.0);
+                double rad = sqrt(r2 < 0.0 ? 0.0 : r2);   // (a NaN moment stays NaN: the safe rule maps the row)
                 sh[k] = -((rad - rs) * (rad - rs)) / (2.0 * sig * sig);
             }
             if (lk.id == 5) acc = sh[0];

@@ -177,9 +177,11 @@ class DoubleGaussianShell(Likelihood):
         self.shell1 = GaussianShell(x_dim, sigma=sigmas[0], rshell=rshells[0], center=centers[0])
         self.shell2 = GaussianShell(x_dim, sigma=sigmas[1], rshell=rshells[1], center=centers[1])
         self.weights = tuple(weights)
-        if self.weights != (1.0, 1.0):
+        # (a sub-shell with a vector centre of unequal entries is not the kernel's: it cleared its own id, and so does the pair;
+        # the centres go to the kernel as the scalars the sub-shells made of them)
+        if self.weights != (1.0, 1.0) or self.shell1.hip_like_id is None or self.shell2.hip_like_id is None:
             self.hip_like_id = None
-        self.hip_like_params = (sigmas[0], rshells[0], centers[0], sigmas[1], rshells[1], centers[1])
+        self.hip_like_params = self.shell1.hip_like_params + self.shell2.hip_like_params
 
     def loglike_rows(self, x):
         return np.logaddexp(np.log(self.weights[0]) + self.shell1.loglike_rows(x),
