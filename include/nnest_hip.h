@@ -471,6 +471,50 @@ int nnest_spline_mcmc_steps(struct nnest_spline *spl, const nnest_like_t *like, 
                             float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, void *stream);
 int nnest_mcmc_fill_noise(float *dz_dev, float *u_dev, int steps, int C, int D, uint64_t step0, uint64_t seed, uint64_t walker_offset,
                           void *stream);
+/* THE TEMPERED TARGET of the same run, and the two service kernels of a SEQUENTIAL MONTE CARLO sampler built on it (SMCSampler,
+ * nnest_amd/smc.py).  BUILD-DEFINED: the reference has no such sampler.  The sampler anneals L^beta pi from beta = 0
+ * (the prior, sampled exactly) to beta = 1; between two temperatures it reweights, resamples, retrains the flow and moves the
+ * particles with Metropolis steps in the flow's latent space.  (All added within ABI 15.)
+ * nnest_mcmc_tempered_steps, nnest_spline_mcmc_tempered_steps: nnest_mcmc_steps / nnest_spline_mcmc_steps with the likelihood to the
+ *   power `beta` -- the arguments of their siblings plus `double beta` before `stream`.  Everything said of nnest_mcmc_steps holds, with
+ *     lp_beta(z) = ((beta * logL) + log|det dx/dz|) + prior,
+ *   float64, each operation rounded; logL is the safe value (-1e100 for non-finite).  lp_in_dev, lp_out_dev and the accept rule use
+ *   lp_beta; the walker still carries and logs the UNTEMPERED logL (logl_in_dev, logl_out_dev, hist_logl_dev).  The draws are the
+ *   same (streams 5 and 6), and so are the invariances: the cut into launches, a shard by walker_offset; steps = 0 evaluates the
+ *   start.  beta must be finite and >= 0, else NNEST_E_ARG before any launch, the outputs untouched; beta = 0 is valid: the prior and
+ *   the Jacobian alone.  beta = 1.0 is bit-identical to the untempered entry (1.0 * logL is exact) on every output.  The tempering is
+ *   a compile-time variant of the two kernels: the untempered entries run the code they ran before.
+ * nnest_smc_reweight: the next temperature and the weights that lead there.  logl_dev [N] float64 (safe values), 1 <= N <= 2^20;
+ *   beta in [0, 1): the population's temperature; ess_fraction in (0, 1).  With w_i(b) = exp((b - beta) (logL_i - max logL)) and
+ *   ESS(b) = (sum w)^2 / sum w^2:  if ESS(1) >= ess_fraction * N then beta' = 1;  otherwise 64 bisection steps on [lo, hi] = [beta, 1]:
+ *   mid = 0.5 * (lo + hi); ESS(mid) < ess_fraction * N ? hi = mid : lo = mid; beta' = hi, and where that does not exceed beta in
+ *   float64, beta' = 1: the ladder always advances.  out_dev [4] float64 = {beta', log((1/N) sum_i exp((beta' - beta) logL_i))
+ *   computed as (beta' - beta) max logL + log(sum w / N), ESS(beta'), max logL}.  m_dev [N] int64: m_i = floor(w_i(beta') * 2^31),
+ *   INTEGER weights (0 .. 2^31): their sums do not depend on the order of a scan.  One workgroup; every reduction float64 in a fixed
+ *   order, no floating-point atomics: the same call twice returns the same bits.  Asynchronous on `stream`.  NNEST_E_ARG before any
+ *   launch: N outside 1 .. 2^20, ess_fraction outside (0, 1) (NaN included), beta outside [0, 1), a NULL buffer.
+ * nnest_smc_resample: systematic resampling on the integer weights m_dev [N] int64 (>= 0).  T = sum m;
+ *     u = the top 24 bits of word 0 of Philox(key seed; counter (0, stage, 0, 8 << 28)) / 2^24 (stream 8; streams 0-7 are taken);
+ *     p_j = floor(((j + u) * (double)T) / N), float64, each operation rounded (every operand is exact);
+ *     anc_j = the smallest i whose inclusive prefix sum of m exceeds p_j;
+ *   row j of theta_out_dev [N, D] float32 and of logl_out_dev [N] float64 is row anc_j of theta_in_dev and logl_in_dev, and
+ *   anc_out_dev [N] int32 holds anc_j (non-decreasing in j).  The outputs must not be the inputs.  stage >= 0, D >= 1.  One workgroup.
+ *   The call returns after the kernel has finished (it reads the kernel's verdict back): T = 0, or a negative weight, is NNEST_E_ARG
+ *   with theta_out_dev and logl_out_dev unwritten (anc_out_dev[0] = -1). */
+int nnest_mcmc_tempered_steps(nnest_nvp_t *nvp, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                              const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev,
+                              float *z_out_dev, float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev,
+                              float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size,
+                              uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta, void *stream);
+int nnest_spline_mcmc_tempered_steps(struct nnest_spline *spl, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                                     const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev,
+                                     const double *logl_in_dev, float *z_out_dev, float *x_out_dev, double *lp_out_dev,
+                                     double *logl_out_dev, float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev,
+                                     int C, int steps, float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta,
+                                     void *stream);
+int nnest_smc_reweight(const double *logl_dev, int N, double beta, double ess_fraction, double *out_dev, long long *m_dev, void *stream);
+int nnest_smc_resample(const long long *m_dev, int N, int D, uint64_t seed, int stage, const float *theta_in_dev, const double *logl_in_dev,
+                       int *anc_out_dev, float *theta_out_dev, double *logl_out_dev, void *stream);
 /* IMPORTANCE-SAMPLED EVIDENCE with the trained flow as the proposal: Z = E_q[L(T(x)) pi(T(x)) / q(x)], drawn, evaluated and reduced
  * inside one kernel.  BUILD-DEFINED: the reference has no such estimator.  Sample m is a global 64-bit index; row k of a launch of M
  * samples is m = sample_offset + k:

@@ -13,4 +13,7 @@ def __getattr__(name):   # the reference's package-level names (nnest/__init__.p
     if name == 'EnsembleSampler':
         from .ensemble import EnsembleSampler
         return EnsembleSampler
+    if name == 'SMCSampler':   # (build-defined: the reference has none)
+        from .smc import SMCSampler
+        return SMCSampler
     raise AttributeError(name)

@@ -222,6 +222,15 @@ SIGNATURES = {
     'nnest_spline_mcmc_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64, _u64, _u64,
                                 _vp],
     'nnest_mcmc_fill_noise': [_vp, _vp, _i, _i, _i, _u64, _u64, _u64, _vp],
+    # the tempered target of the two entries above: their arguments plus `double beta` before `stream`
+    'nnest_mcmc_tempered_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64, _u64,
+                                  _u64, _d, _vp],
+    'nnest_spline_mcmc_tempered_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64,
+                                         _u64, _u64, _d, _vp],
+    # (logl_dev, N, beta, ess_fraction, out_dev [4], m_dev [N] int64, stream)
+    'nnest_smc_reweight': [_vp, _i, _d, _d, _vp, _vp, _vp],
+    # (m_dev, N, D, seed, stage, theta_in_dev, logl_in_dev, anc_out_dev, theta_out_dev, logl_out_dev, stream)
+    'nnest_smc_resample': [_vp, _i, _i, _u64, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     'nnest_importance_groups': [_i, _i],
     'nnest_importance_check': [_vp, _i],
     'nnest_spline_importance_check': [_vp, _i],

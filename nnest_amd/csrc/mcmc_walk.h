@@ -32,6 +32,12 @@ __device__ __forceinline__ float mcmc_uniform(uint64_t seed, uint64_t walker, ui
 #pragma clang fp contract(off)
 // q = z + step * eps, each operation rounded (as ens_propose is written)
 __device__ __forceinline__ float mcmc_propose(float z, float step, float eps) { return z + step * eps; }
+// the TEMPERED target (nnest_mcmc_tempered_steps): ens_target at constrained = 0 with the likelihood to the power beta,
+// lp_beta = ((beta * logL) + log|det|) + prior, each operation rounded; beta = 1 is ens_target bit for bit (1.0 * logL is exact)
+__device__ __forceinline__ double mcmc_target_tempered(double logl, float ld, bool in_prior, double beta) {
+    const double prior = in_prior ? 0.0 : -INFINITY;
+    return ((beta * logl) + (double)ld) + prior;
+}
 #pragma clang fp contract(fast)
 
 // the arguments of a launch (nnest_mcmc_steps, nnest_spline_mcmc_steps).  The flow goes with them: FlowShape + packed weights for
@@ -52,6 +58,14 @@ struct McmcArgs {
     uint32_t step0;
     uint64_t seed, walker_offset;
 };
+// ... of a tempered launch (nnest_mcmc_tempered_steps, nnest_spline_mcmc_tempered_steps): the likelihood's power beside them.  A type
+// of its own, so that the untempered kernels keep the arguments -- and with them the code -- they had
+struct McmcTemperedArgs : McmcArgs {
+    double beta;                    // finite, >= 0 (0: the prior and the Jacobian alone)
+};
+// the arguments of an instantiation: TP selects the tempered target at compile time
+template <bool TP> struct McmcArgsOf { typedef McmcArgs type; };
+template <> struct McmcArgsOf<true> { typedef McmcTemperedArgs type; };
 
 // nnest_abi.hip: the argument checks both entries share (sets the error string); fills `a` (a.like is the caller's, after its own
 // likelihood check)
@@ -63,5 +77,10 @@ hipError_t launch_mcmc_fill_noise(float *dz, float *u, int S, int C, int D, uint
 hipError_t launch_mcmc(const FlowShape &s, const float *packed, const McmcArgs &a, hipStream_t st);
 // hipErrorInvalidConfiguration: a shape the team tile is not instantiated for
 hipError_t launch_spline_mcmc(const SplArgs &q, const McmcArgs &a, hipStream_t st);
+// the tempered instantiations of the same two kernels (a.beta as the entry checked it: nnest_abi.hip mcmc_beta_ok)
+hipError_t launch_mcmc_tempered(const FlowShape &s, const float *packed, const McmcTemperedArgs &a, hipStream_t st);
+hipError_t launch_spline_mcmc_tempered(const SplArgs &q, const McmcTemperedArgs &a, hipStream_t st);
+// nnest_abi.hip: the check of a tempered entry's beta (sets the error string)
+int mcmc_beta_ok(double beta);
 
 }  // namespace nnest

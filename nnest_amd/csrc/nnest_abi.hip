@@ -425,6 +425,10 @@ int nnest::mcmc_args(McmcArgs *a, const float *t_std, const float *t_mean, const
     a->C = C; a->S = steps; a->step = step_size; a->step0 = (uint32_t)step0; a->seed = seed; a->walker_offset = walker_offset;
     return NNEST_OK;
 }
+int nnest::mcmc_beta_ok(double beta) {
+    if (!isfinite(beta) || beta < 0.0) return fail(NNEST_E_ARG, "mcmc: beta=%g (the likelihood's power: finite, >= 0)", beta);
+    return NNEST_OK;
+}
 int nnest::importance_args(ImpArgs *a, const float *t_std, const float *t_mean, const float *lo, const float *hi, float *z_out, float *x_out,
                            double *logl_out, double *logw_out, double *partials, double *sums, int M, uint64_t seed, uint64_t sample_offset) {
     if (M < 0 || M > (1 << 30)) return fail(NNEST_E_ARG, "importance: M=%d (0 .. 2^30 samples a launch)", M);
@@ -492,27 +496,51 @@ int nnest_ensemble_fill_noise(int *work_dev, float *u_dev, int C, int steps, uin
 }
 
 // (the checks that need no handle come first: they answer on a machine without a GPU, where no handle can exist)
-int nnest_mcmc_steps(nnest_nvp_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
-                     const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev,
-                     float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev, float *hist_x_dev,
-                     double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size, uint64_t step0, uint64_t seed,
-                     uint64_t walker_offset, void *stream) {
+// beta NULL: nnest_mcmc_steps; else nnest_mcmc_tempered_steps at *beta
+static int mcmc_steps_entry(nnest_nvp_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                            const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev,
+                            float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev, float *hist_x_dev,
+                            double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size, uint64_t step0, uint64_t seed,
+                            uint64_t walker_offset, const double *beta, void *stream) {
     if (!like) return fail(NNEST_E_ARG, "like is NULL");
     if (like->id < 0 || like->id >= NNEST_LIKE_COUNT) return fail(NNEST_E_ARG, "unknown likelihood id %d", like->id);
-    McmcArgs a;
+    int rc;
+    if (beta && (rc = mcmc_beta_ok(*beta))) return rc;
+    McmcTemperedArgs a;
     memset(&a, 0, sizeof(a));
-    int rc = mcmc_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev, lp_out_dev,
-                       logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0, seed, walker_offset);
+    a.beta = beta ? *beta : 1.0;
+    rc = mcmc_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev, lp_out_dev,
+                   logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0, seed, walker_offset);
     if (rc) return rc;
     if (!h) return fail(NNEST_E_ARG, "NULL handle");
     if ((rc = check_like(like, h->s.D, &a.like))) return rc;
     a.like.scale = 1.0f;
     if (!ensemble_form_eligible(h->s))
         return fail(NNEST_E_UNSUPPORTED, "mcmc: hidden 16, 3 blocks, 1 layer, scale '' (the one-walker-per-wave layout), x_dim <= 128");
-    hipError_t e = launch_mcmc(h->s, h->w, a, (hipStream_t)stream);
+    hipError_t e = beta ? launch_mcmc_tempered(h->s, h->w, a, (hipStream_t)stream) : launch_mcmc(h->s, h->w, a, (hipStream_t)stream);
     if (e == hipErrorInvalidConfiguration) return fail(NNEST_E_UNSUPPORTED, "mcmc: x_dim=%d not instantiated", h->s.D);
     if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_mcmc: %s", hipGetErrorString(e));
     return NNEST_OK;
+}
+
+int nnest_mcmc_steps(nnest_nvp_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                     const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev,
+                     float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev, float *hist_x_dev,
+                     double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size, uint64_t step0, uint64_t seed,
+                     uint64_t walker_offset, void *stream) {
+    return mcmc_steps_entry(h, like, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev, lp_out_dev,
+                            logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0, seed,
+                            walker_offset, nullptr, stream);
+}
+
+int nnest_mcmc_tempered_steps(nnest_nvp_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                              const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev,
+                              float *z_out_dev, float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev,
+                              float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size,
+                              uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta, void *stream) {
+    return mcmc_steps_entry(h, like, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev, lp_out_dev,
+                            logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0, seed,
+                            walker_offset, &beta, stream);
 }
 
 int nnest_mcmc_fill_noise(float *dz_dev, float *u_dev, int steps, int C, int D, uint64_t step0, uint64_t seed, uint64_t walker_offset,

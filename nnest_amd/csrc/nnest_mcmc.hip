@@ -20,6 +20,9 @@
 // target is wrapped (see the comments there), and this one returns logL beside lp.  ONE loop runs the launch's evaluations -- i = -1
 // is the start, where nobody moves -- so the inverse is inlined once and the start of a launch is evaluated by the code that
 // evaluated it as a proposal in the launch before: a run cut into launches is the same run, bit for bit.
+//
+// The TEMPERED run (nnest_mcmc_tempered_steps) is the same kernel with the likelihood to the power beta in lp
+// (mcmc_target_tempered), a compile-time variant: the walker still carries and logs the untempered logL.
 #include <stdio.h>
 #include <string.h>
 
@@ -52,8 +55,10 @@ __global__ void mcmc_fill_noise_kernel(float *__restrict__ dz, float *__restrict
     }
 }
 
-template <int U, int LK>
-__global__ void __launch_bounds__(256) mcmc_kernel(FlowShape s, const float *__restrict__ packed, McmcArgs a) {
+// TP: the tempered target (mcmc_target_tempered at a.beta), a compile-time variant: the TP = false instantiations are the kernels
+// of nnest_mcmc_steps as they were, instruction for instruction
+template <int U, int LK, bool TP>
+__global__ void __launch_bounds__(256) mcmc_kernel(FlowShape s, const float *__restrict__ packed, typename McmcArgsOf<TP>::type a) {
     extern __shared__ __attribute__((aligned(16))) float wlds[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int D = s.D, C = a.C, S = a.S;
@@ -126,7 +131,8 @@ __global__ void __launch_bounds__(256) mcmc_kernel(FlowShape s, const float *__r
             }
         const bool in_prior = __ballot(ok != 0) == ~0ull;
         logl = solo_loglike<U, LK>(like, D, lane, tx);
-        return ens_target(logl, ld, in_prior, 0, 0.0);
+        if constexpr (TP) return mcmc_target_tempered(logl, ld, in_prior, a.beta);
+        else return ens_target(logl, ld, in_prior, 0, 0.0);
     };
 
     const bool writer_lane = lane < 16;
@@ -234,24 +240,32 @@ hipError_t launch_mcmc_fill_noise(float *dz, float *u, int S, int C, int D, uint
     return hipGetLastError();
 }
 
-template <int U, int LK>
-static hipError_t mcmc_launch_k(const FlowShape &s, const float *packed, const McmcArgs &a, hipStream_t st) {
+template <int U, int LK, bool TP>
+static hipError_t mcmc_launch_k(const FlowShape &s, const float *packed, const typename McmcArgsOf<TP>::type &a, hipStream_t st) {
     // (ensemble_kernel's LDS: the packed nets, or the three blocks' gathered fields at x_dim > 64)
     const size_t lds = U >= 3 ? (size_t)3 * SOLO4_NF * 64 * sizeof(float) : (size_t)s.nets_params() * sizeof(float);
-    hipLaunchKernelGGL((mcmc_kernel<U, LK>), dim3((a.C + 3) / 4), dim3(256), lds, st, s, packed, a);
+    hipLaunchKernelGGL((mcmc_kernel<U, LK, TP>), dim3((a.C + 3) / 4), dim3(256), lds, st, s, packed, a);
     return hipGetLastError();
 }
 
-hipError_t launch_mcmc(const FlowShape &s, const float *packed, const McmcArgs &a, hipStream_t st) {
+template <bool TP>
+static hipError_t mcmc_dispatch(const FlowShape &s, const float *packed, const typename McmcArgsOf<TP>::type &a, hipStream_t st) {
     if (a.C <= 0) return hipSuccess;
     const bool rosen = a.like.id == NNEST_LIKE_ROSENBROCK;
     switch (s.NT) {
-        case 1: return rosen ? mcmc_launch_k<1, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : mcmc_launch_k<1, -1>(s, packed, a, st);
-        case 2: return rosen ? mcmc_launch_k<2, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : mcmc_launch_k<2, -1>(s, packed, a, st);
-        case 3: return rosen ? mcmc_launch_k<3, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : mcmc_launch_k<3, -1>(s, packed, a, st);
-        case 4: return rosen ? mcmc_launch_k<4, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : mcmc_launch_k<4, -1>(s, packed, a, st);
+        case 1: return rosen ? mcmc_launch_k<1, NNEST_LIKE_ROSENBROCK, TP>(s, packed, a, st) : mcmc_launch_k<1, -1, TP>(s, packed, a, st);
+        case 2: return rosen ? mcmc_launch_k<2, NNEST_LIKE_ROSENBROCK, TP>(s, packed, a, st) : mcmc_launch_k<2, -1, TP>(s, packed, a, st);
+        case 3: return rosen ? mcmc_launch_k<3, NNEST_LIKE_ROSENBROCK, TP>(s, packed, a, st) : mcmc_launch_k<3, -1, TP>(s, packed, a, st);
+        case 4: return rosen ? mcmc_launch_k<4, NNEST_LIKE_ROSENBROCK, TP>(s, packed, a, st) : mcmc_launch_k<4, -1, TP>(s, packed, a, st);
     }
     return hipErrorInvalidConfiguration;
+}
+
+hipError_t launch_mcmc(const FlowShape &s, const float *packed, const McmcArgs &a, hipStream_t st) {
+    return mcmc_dispatch<false>(s, packed, a, st);
+}
+hipError_t launch_mcmc_tempered(const FlowShape &s, const float *packed, const McmcTemperedArgs &a, hipStream_t st) {
+    return mcmc_dispatch<true>(s, packed, a, st);
 }
 
 }  // namespace nnest

@@ -421,27 +421,54 @@ int nnest_spline_ensemble_steps(nnest_spline_t *h, const nnest_like_t *like, con
     return NNEST_OK;
 }
 
-// the random-walk Metropolis run through the spline flow (nnest_spline_mcmc.hip); the argument checks of nnest_mcmc_steps
+// the random-walk Metropolis run through the spline flow (nnest_spline_mcmc.hip); the argument checks of nnest_mcmc_steps.
+// beta NULL: nnest_spline_mcmc_steps; else nnest_spline_mcmc_tempered_steps at *beta
+static int spline_mcmc_steps_entry(nnest_spline_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                                   const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev,
+                                   const double *logl_in_dev, float *z_out_dev, float *x_out_dev, double *lp_out_dev, double *logl_out_dev,
+                                   float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C, int steps,
+                                   float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, const double *beta,
+                                   void *stream) {
+    if (!like) return spline_fail(NNEST_E_ARG, "like is NULL");
+    if (like->id < 0 || like->id >= NNEST_LIKE_COUNT) return spline_fail(NNEST_E_ARG, "unknown likelihood id %d", like->id);
+    int rc;
+    if (beta && (rc = mcmc_beta_ok(*beta))) return rc;
+    McmcTemperedArgs a;
+    memset(&a, 0, sizeof(a));
+    a.beta = beta ? *beta : 1.0;
+    rc = mcmc_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev, lp_out_dev,
+                   logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0, seed, walker_offset);
+    if (rc) return rc;
+    if (!h) return spline_fail(NNEST_E_ARG, "NULL handle");
+    if ((rc = scheck_like(like, h->s.D, &a.like))) return rc;
+    a.like.scale = 1.0f;
+    const hipError_t e = beta ? launch_spline_mcmc_tempered(SplArgs{h->img, h->s}, a, (hipStream_t)stream)
+                              : launch_spline_mcmc(SplArgs{h->img, h->s}, a, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration)
+        return spline_fail(NNEST_E_UNSUPPORTED, "spline mcmc: x_dim=%d hidden_dim=%d not instantiated", h->s.D, h->s.H);
+    if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_mcmc: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
 int nnest_spline_mcmc_steps(nnest_spline_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
                             const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev,
                             const double *logl_in_dev, float *z_out_dev, float *x_out_dev, double *lp_out_dev, double *logl_out_dev,
                             float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C, int steps,
                             float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, void *stream) {
-    if (!like) return spline_fail(NNEST_E_ARG, "like is NULL");
-    if (like->id < 0 || like->id >= NNEST_LIKE_COUNT) return spline_fail(NNEST_E_ARG, "unknown likelihood id %d", like->id);
-    McmcArgs a;
-    memset(&a, 0, sizeof(a));
-    int rc = mcmc_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev, lp_out_dev,
-                       logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0, seed, walker_offset);
-    if (rc) return rc;
-    if (!h) return spline_fail(NNEST_E_ARG, "NULL handle");
-    if ((rc = scheck_like(like, h->s.D, &a.like))) return rc;
-    a.like.scale = 1.0f;
-    hipError_t e = launch_spline_mcmc(SplArgs{h->img, h->s}, a, (hipStream_t)stream);
-    if (e == hipErrorInvalidConfiguration)
-        return spline_fail(NNEST_E_UNSUPPORTED, "spline mcmc: x_dim=%d hidden_dim=%d not instantiated", h->s.D, h->s.H);
-    if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_mcmc: %s", hipGetErrorString(e));
-    return NNEST_OK;
+    return spline_mcmc_steps_entry(h, like, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev,
+                                   lp_out_dev, logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0,
+                                   seed, walker_offset, nullptr, stream);
+}
+
+int nnest_spline_mcmc_tempered_steps(nnest_spline_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                                     const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev,
+                                     const double *logl_in_dev, float *z_out_dev, float *x_out_dev, double *lp_out_dev,
+                                     double *logl_out_dev, float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev,
+                                     int C, int steps, float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta,
+                                     void *stream) {
+    return spline_mcmc_steps_entry(h, like, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev,
+                                   lp_out_dev, logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0,
+                                   seed, walker_offset, &beta, stream);
 }
 
 // what nnest_spline_importance_evidence takes, asked before a launch (and by the entry itself): the refusals name their reason

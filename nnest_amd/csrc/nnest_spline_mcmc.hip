@@ -16,6 +16,9 @@
 // exchange it (as in ens_tile_walk).  Walkers are independent: no hand-off, no residency limit, no work buffer.  Every wave runs
 // every evaluation of the launch, so the team's barriers inside the inverse always meet.
 //
+// The TEMPERED run (nnest_spline_mcmc_tempered_steps) is the same kernel with the likelihood to the power beta in lp
+// (mcmc_target_tempered), a compile-time variant.
+//
 // Compiled with -mllvm -disable-machine-licm, as nnest_spline_ensemble.hip is: a step loop around the same inverse.
 #include <stdio.h>
 #include <string.h>
@@ -39,8 +42,9 @@ __device__ __forceinline__ f32x4 mcmc_class(const f32x4 &v0, const f32x4 &v1, in
 
 // The walk of one tile (16 walkers, this wave's copy) through the S steps of a launch.  tpar: [4][32 NT] in LDS -- std, mean, lo, hi
 // (padded dims: 0, 0, -inf, +inf).  `writer`: the wave that stores.
-template <int NT, class Inv>
-__device__ __forceinline__ void mcmc_tile_walk(const McmcArgs &a, int D, int tile, int lane, const Inv &inv, const float *tpar, bool writer) {
+// TP: the tempered target at `beta` (mcmc_target_tempered), a compile-time variant; beta is not read otherwise.
+template <int NT, bool TP, class Inv>
+__device__ __forceinline__ void mcmc_tile_walk(const McmcArgs &a, double beta, int D, int tile, int lane, const Inv &inv, const float *tpar, bool writer) {
     const int S = a.S, C = a.C;
     const int g = lane >> 4;
     const int row = tile * SPL_MCMC_TILE + (lane & 15);
@@ -74,7 +78,8 @@ __device__ __forceinline__ void mcmc_tile_walk(const McmcArgs &a, int D, int til
         }
         const bool in_prior = group_all(inside != 0, lane) != 0;
         logl = loglike_tile<NT>(like, D, lane, tx);
-        return ens_target(logl, ld, in_prior, 0, 0.0);
+        if constexpr (TP) return mcmc_target_tempered(logl, ld, in_prior, beta);
+        else return ens_target(logl, ld, in_prior, 0, 0.0);
     };
 
     // ONE loop over the launch's evaluations, so that the inverse is inlined once: i = -1 is the start (nobody moves, every walker
@@ -150,8 +155,9 @@ __device__ __forceinline__ void mcmc_tile_walk(const McmcArgs &a, int D, int til
 __host__ __device__ inline int spl_mcmc_lds_tpar(int D, int NT) { return ((4 * 16 * (D + 1) + 3) & ~3) + 4 * NT * 64 * 4 + 4 * 16; }
 __host__ __device__ inline int spl_mcmc_lds_floats(int D, int NT) { return spl_mcmc_lds_tpar(D, NT) + 4 * 32 * NT; }
 
-template <int NT, int NH>
-__global__ void __launch_bounds__(256) spline_mcmc_kernel_team(McmcArgs a, SplArgs q) {
+// (TP = false: the kernels of nnest_spline_mcmc_steps as they were, instruction for instruction)
+template <int NT, int NH, bool TP>
+__global__ void __launch_bounds__(256) spline_mcmc_kernel_team(typename McmcArgsOf<TP>::type a, SplArgs q) {
     extern __shared__ __attribute__((aligned(16))) float lds_buf[];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int D = q.sp.D;
@@ -168,34 +174,41 @@ __global__ void __launch_bounds__(256) spline_mcmc_kernel_team(McmcArgs a, SplAr
     }
     __syncthreads();
     SplineInverseTeam<NT, NH, 4> inv = {q.img, q.sp, bufs + (size_t)wv * 16 * (D + 1), xch, ldred, lane, wv};
-    mcmc_tile_walk<NT>(a, D, blockIdx.x, lane, inv, tpar, wv == 0);
+    if constexpr (TP) mcmc_tile_walk<NT, true>(a, a.beta, D, blockIdx.x, lane, inv, tpar, wv == 0);
+    else mcmc_tile_walk<NT, false>(a, 0.0, D, blockIdx.x, lane, inv, tpar, wv == 0);
 }
 
 // ------------------------------------------------------------------------------------------------
 // host side
-template <int NT, int NH>
-static hipError_t spl_mcmc_launch_t(const McmcArgs &a, const SplArgs &q, hipStream_t st) {
+template <int NT, int NH, bool TP>
+static hipError_t spl_mcmc_launch_t(const typename McmcArgsOf<TP>::type &a, const SplArgs &q, hipStream_t st) {
     const size_t lds = (size_t)spl_mcmc_lds_floats(q.sp.D, NT) * sizeof(float);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(spline_mcmc_kernel_team<NT, NH>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(spline_mcmc_kernel_team<NT, NH, TP>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((spline_mcmc_kernel_team<NT, NH>), dim3((a.C + SPL_MCMC_TILE - 1) / SPL_MCMC_TILE), dim3(256), lds, st, a, q);
+    hipLaunchKernelGGL((spline_mcmc_kernel_team<NT, NH, TP>), dim3((a.C + SPL_MCMC_TILE - 1) / SPL_MCMC_TILE), dim3(256), lds, st, a, q);
     return hipGetLastError();
 }
 
 // The shapes of the team form of the ensemble kernel (spl_ens_dispatch)
-hipError_t launch_spline_mcmc(const SplArgs &q, const McmcArgs &a, hipStream_t st) {
+template <bool TP>
+static hipError_t spl_mcmc_dispatch(const SplArgs &q, const typename McmcArgsOf<TP>::type &a, hipStream_t st) {
     if (!spline_shape_supported(q.sp)) return hipErrorInvalidConfiguration;
     if (a.C <= 0) return hipSuccess;
     switch (q.sp.NTh * 10 + q.sp.NH) {
-        case 11: return spl_mcmc_launch_t<1, 1>(a, q, st);
-        case 21: return spl_mcmc_launch_t<2, 1>(a, q, st);
-        case 31: return spl_mcmc_launch_t<3, 1>(a, q, st);
-        case 41: return spl_mcmc_launch_t<4, 1>(a, q, st);
-        case 12: return spl_mcmc_launch_t<1, 2>(a, q, st);
-        case 22: return spl_mcmc_launch_t<2, 2>(a, q, st);
+        case 11: return spl_mcmc_launch_t<1, 1, TP>(a, q, st);
+        case 21: return spl_mcmc_launch_t<2, 1, TP>(a, q, st);
+        case 31: return spl_mcmc_launch_t<3, 1, TP>(a, q, st);
+        case 41: return spl_mcmc_launch_t<4, 1, TP>(a, q, st);
+        case 12: return spl_mcmc_launch_t<1, 2, TP>(a, q, st);
+        case 22: return spl_mcmc_launch_t<2, 2, TP>(a, q, st);
     }
     return hipErrorInvalidConfiguration;
+}
+
+hipError_t launch_spline_mcmc(const SplArgs &q, const McmcArgs &a, hipStream_t st) { return spl_mcmc_dispatch<false>(q, a, st); }
+hipError_t launch_spline_mcmc_tempered(const SplArgs &q, const McmcTemperedArgs &a, hipStream_t st) {
+    return spl_mcmc_dispatch<true>(q, a, st);
 }
 
 }  // namespace nnest

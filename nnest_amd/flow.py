@@ -388,7 +388,7 @@ class _HipFlow(object):
         return out
 
     def mcmc_steps(self, like_id, z, steps, step_size, t_std=None, t_mean=None, lo=None, hi=None, lp=None, logl=None, seed=0, step0=0,
-                   walker_offset=0, like_params=None, history=True):
+                   walker_offset=0, like_params=None, history=True, beta=None):
         """`steps` steps of random-walk Metropolis in latent space with the likelihood, the prior and the Jacobian in the ratio, in ONE
         launch (the family's `mcmc` entry point: nnest_mcmc_steps, nnest_spline_mcmc_steps; build-defined stream, the reference's move:
         include/nnest_hip.h has the definition).  z [C, D] float32 on the device: the walkers' start; lp, logl [C] float64: the
@@ -398,10 +398,14 @@ class _HipFlow(object):
         only, so a run cut into launches or into shards is the same run.  steps = 0 evaluates the start (x, lp, logl; z is the
         caller's).  Returns z, x, lp, logl (the last state), hist_z, hist_x [C, steps, D], hist_logl [C, steps] (the state after
         every step; None with history=False or steps = 0) and n_accept [C].  Asynchronous on the current stream.
+        beta: None -- the entry above, as it was; a float -- the TEMPERED target lp_beta = ((beta * logL) + log|det|) + prior through
+        the family's `mcmc_tempered` entry (nnest_mcmc_tempered_steps, nnest_spline_mcmc_tempered_steps: the same draws, the same
+        invariances; lp is lp_beta, logl stays the untempered logL; beta finite and >= 0, 1.0 is the untempered run bit for bit).
         NotImplementedError for a family without such a kernel (its handle must not reach another family's)."""
-        fn = self._sym.get('mcmc')
+        fn = self._sym.get('mcmc' if beta is None else 'mcmc_tempered')
         if fn is None:
-            raise NotImplementedError('no fused random-walk Metropolis kernel for %s' % type(self).__name__)
+            raise NotImplementedError('no fused %srandom-walk Metropolis kernel for %s' % ('' if beta is None else 'tempered ', type(self).__name__))
+        tempered = () if beta is None else (ctypes.c_double(float(beta)),)
         dev = self.device
         z = _as_dev_f32(z, dev).contiguous()
         C, D, steps = z.shape[0], self.D, int(steps)
@@ -431,7 +435,7 @@ class _HipFlow(object):
                 _lib.ptr(logl), _lib.ptr(out['z']) if steps > 0 else None, _lib.ptr(out['x']), _lib.ptr(out['lp']), _lib.ptr(out['logl']),
                 _lib.ptr(out['hist_z']), _lib.ptr(out['hist_x']), _lib.ptr(out['hist_logl']), _lib.ptr(out['n_accept']), C, steps,
                 ctypes.c_float(float(step_size)), int(step0) & 0xFFFFFFFFFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                int(walker_offset) & 0xFFFFFFFFFFFFFFFF, _lib.current_stream(dev)))
+                int(walker_offset) & 0xFFFFFFFFFFFFFFFF, *tempered, _lib.current_stream(dev)))
         return out
 
     def importance_refusal(self, like_id):
@@ -725,7 +729,8 @@ class HipNVP(_PaddedVectors, _HipFlow):
         self._bind('nnest_nvp', mh='nnest_mh_constrained_steps', slice='nnest_slice_steps', ensemble='nnest_ensemble_steps',
                    ensemble_max_walkers='nnest_ensemble_max_walkers', ensemble_moves='nnest_ensemble_moves_steps',
                    ensemble_moves_max_walkers='nnest_ensemble_moves_max_walkers', mcmc='nnest_mcmc_steps',
-                   importance='nnest_importance_evidence', importance_check='nnest_importance_check')
+                   importance='nnest_importance_evidence', importance_check='nnest_importance_check',
+                   mcmc_tempered='nnest_mcmc_tempered_steps')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (_PaddedVectors)
         with torch.cuda.device(self.device):
@@ -954,6 +959,54 @@ def mcmc_fill_noise(steps, C, D, seed=0, step0=0, walker_offset=0, device=None):
                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset) & 0xFFFFFFFFFFFFFFFF,
                                                      _lib.current_stream(dev)))
     return dz, u
+
+
+SMC_MAX_PARTICLES = 1 << 20   # the population nnest_smc_reweight and nnest_smc_resample take (one workgroup each)
+
+
+def smc_reweight(logl, beta, ess_fraction):
+    """the next temperature of a sequential Monte Carlo ladder and the weights that lead there (nnest_smc_reweight; include/nnest_hip.h
+    has the definition): logl [N] float64 on the device (safe values), beta in [0, 1) the population's temperature, ess_fraction in
+    (0, 1).  Returns (out, m): out [4] float64 on the device = {beta', log mean exp((beta' - beta) logL), ESS(beta'), max logL}, beta'
+    where the effective sample size of w_i = exp((beta' - beta) (logL_i - max logL)) falls to ess_fraction * N (bisection; 1 where it
+    never does), and m [N] int64 = floor(w_i 2^31), the integer weights smc_resample takes.  Deterministic: the same call twice
+    returns the same bits.  Asynchronous on the current stream."""
+    logl = torch.as_tensor(logl)
+    if not logl.is_cuda:
+        raise ValueError('smc_reweight: logl must be on the device')
+    logl = logl.to(torch.float64).contiguous().reshape(-1)
+    dev, N = logl.device, logl.shape[0]
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    m = torch.empty(N, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().nnest_smc_reweight(_lib.ptr(logl), N, float(beta), float(ess_fraction), _lib.ptr(out), _lib.ptr(m),
+                                                  _lib.current_stream(dev)))
+    return out, m
+
+
+def smc_resample(m, theta, logl, seed, stage):
+    """systematic resampling of a population on integer weights (nnest_smc_resample; include/nnest_hip.h has the definition): m [N]
+    int64 (>= 0, as smc_reweight returns them), theta [N, D] float32 and logl [N] float64 on the device; the one uniform of the draw
+    is a function of (seed, stage) (Philox stream 8).  Returns (anc [N] int32, theta[anc], logl[anc]) as new tensors: anc_j is the
+    smallest i whose inclusive prefix sum of m exceeds floor((j + u) sum(m) / N).  Returns after the kernel has finished; NnestHipError
+    where the weights sum to 0."""
+    m = torch.as_tensor(m)
+    if not m.is_cuda:
+        raise ValueError('smc_resample: m must be on the device')
+    dev = m.device
+    m = m.to(torch.int64).contiguous().reshape(-1)
+    theta = _as_dev_f32(theta, dev).contiguous()
+    logl = torch.as_tensor(logl, dtype=torch.float64).to(dev).contiguous().reshape(-1)
+    N = m.shape[0]
+    if theta.shape[0] != N or logl.shape[0] != N:
+        raise ValueError('smc_resample: m [%d], theta %s and logl [%d]: one row per particle' % (N, tuple(theta.shape), logl.shape[0]))
+    anc = torch.empty(N, dtype=torch.int32, device=dev)
+    theta_out, logl_out = torch.empty_like(theta), torch.empty_like(logl)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().nnest_smc_resample(_lib.ptr(m), N, theta.shape[1], int(seed) & 0xFFFFFFFFFFFFFFFF, int(stage), _lib.ptr(theta),
+                                                  _lib.ptr(logl), _lib.ptr(anc), _lib.ptr(theta_out), _lib.ptr(logl_out),
+                                                  _lib.current_stream(dev)))
+    return anc, theta_out, logl_out
 
 
 def importance_fill_noise(M, D, seed=0, sample_offset=0, device=None):
