@@ -50,8 +50,7 @@
 #include "ensemble_common.h"
 #include "flow_tile.h"
 #include "nnest_internal.h"
-#include "solo_loglike.h"
-#include "solo_tile.h"
+#include "solo_latent.h"
 
 namespace nnest {
 
@@ -145,8 +144,8 @@ __global__ void ensemble_fill_moves_kernel(const int *__restrict__ work, int *__
 }
 
 // ------------------------------------------------------------------------------------------------
-// FUSED route: one walker per wave (the solo layout of nnest_solo.hip: lane = 32 n + 16 h + p holds dims 2U p + 2u + c; the four
-// (n, h) rows hold copies), four walkers per workgroup.
+// FUSED route: one walker per wave, four walkers per workgroup, in the solo layout; the latent target -- the flow's inverse, T, the
+// box, the likelihood -- is solo_latent.h's for ensemble_x_kernel (its box half); ensemble_kernel states it itself, see there.
 // (struct EnsArgs: ensemble_common.h)
 
 // The walk of one walker (one wave) through the S steps of a launch, shared by the two fused kernels: `target` maps a position in
@@ -160,24 +159,8 @@ __device__ __forceinline__ void ens_walk(const EnsArgs &a, const int row, const 
     const int D = a.s.D, S = a.S, C = a.C;
     const int pos = lane & 15;
     const bool writer_lane = lane < 16;
-    auto load_row = [&](const float *base, float (&v)[2][U]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int d = 2 * U * pos + 2 * u + c;
-                v[c][u] = d < D ? base[d] : 0.f;
-            }
-    };
-    auto store_row = [&](float *base, const float (&v)[2][U]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int d = 2 * U * pos + 2 * u + c;
-                if (d < D) base[d] = v[c][u];
-            }
-    };
+    auto load_row = [&](const float *base, float (&v)[2][U]) { solo_load_row<U>(base, D, pos, v); };
+    auto store_row = [&](float *base, const float (&v)[2][U]) { solo_store_row<U>(base, D, pos, v); };
     int *err = a.work;
     unsigned *tags = reinterpret_cast<unsigned *>(a.work + ENS_CTRL_WORDS);
     const int *inds = a.work + ens_split_off(C);
@@ -260,6 +243,12 @@ __device__ __forceinline__ void ens_walk(const EnsArgs &a, const int row, const 
     }
 }
 
+// This kernel keeps its target WRITTEN OUT (the text solo_latent.h states for the other three kernels of the layout): its register
+// allocation reacts to how the target is wrapped.  Sharing the header moved its SGPR spills (<3, -1, false> 39 -> 62, <2, -1, false>
+// 37 -> 59, <1, -1, false> 39 -> 54) and tools/time_ensemble.py then measured it above the parent by more than the parent's spread at
+// the wide shapes: x_dim 70 GaussianMix 7.978 -> 8.039 ms (spread 0.058), x_dim 100 GaussianMix 9.410 -> 9.487 ms (0.056), x_dim 100
+// Rosenbrock 9.419 -> 9.471 ms (0.035) (profiles/latent_target/timing.txt, section 3).  As written here every instantiation is the
+// parent's, instruction for instruction.
 template <int U, int LK, bool MIX>
 __global__ void __launch_bounds__(256) ensemble_kernel(EnsArgs a) {
     extern __shared__ __attribute__((aligned(16))) float wlds[];
@@ -337,43 +326,20 @@ __global__ void __launch_bounds__(256) ensemble_kernel(EnsArgs a) {
     ens_walk<U, true, MIX>(a, row, lane, target);
 }
 
-// The x-space run: the same walk with f = identity and ld = 0, so lp(x) = safe logL(T(x)) + prior.  No flow, hence no
-// weights and no LDS; t_std / t_mean NULL: T = identity (x * 1 + 0 in float32, the value the round route computes with an identity
-// flow).  The mapped row is T(x): x_out (optional) receives it.
+// The x-space run: the same walk with f = identity and ld = 0, so lp(x) = safe logL(T(x)) + prior: the box half of
+// solo_latent.h alone.  No flow, hence no weights and no LDS.  The mapped row is T(x): x_out (optional) receives it.
 template <int U, int LK, bool MIX>
 __global__ void __launch_bounds__(256) ensemble_x_kernel(EnsArgs a) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int D = a.s.D;
-    const int pos = lane & 15;
     const int row = blockIdx.x * 4 + wave;
     if (row >= a.C) return;
-    float sd[2][U], mu[2][U], blo[2][U], bhi[2][U];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int d = 2 * U * pos + 2 * u + c;
-            const bool v = d < D;
-            sd[c][u] = v ? (a.t_std ? a.t_std[d] : 1.f) : 0.f;
-            mu[c][u] = v && a.t_mean ? a.t_mean[d] : 0.f;
-            blo[c][u] = v && a.lo ? a.lo[d] : -INFINITY;
-            bhi[c][u] = v && a.hi ? a.hi[d] : INFINITY;
-        }
-    LikeSpec like = a.like;
-    like.scale = 1.0f;
+    SoloBox<U, LK> box;
+    box.init(a, a.s.D, lane, lane & 15);
     // x <- T(x) in place; returns lp
     auto target = [&](float (&xs)[2][U]) -> double {
-        int ok = 1;
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                xs[c][u] = ens_T(xs[c][u], sd[c][u], mu[c][u]);
-                ok &= !(xs[c][u] < blo[c][u] || xs[c][u] > bhi[c][u]);   // (NaN counts as inside: UniformPrior, priors.py)
-            }
-        const bool in_prior = __ballot(ok != 0) == ~0ull;
-        const double logl = solo_loglike<U, LK>(like, D, lane, xs);
-        return ens_target(logl, 0.f, in_prior, a.constrained, a.loglstar);
+        return box.eval(xs, xs, 0.f, [&](double logl, float ld, bool in_prior) {
+            return ens_target(logl, ld, in_prior, a.constrained, a.loglstar);
+        });
     };
     ens_walk<U, false, MIX>(a, row, lane, target);
 }
@@ -513,16 +479,11 @@ hipError_t launch_ensemble_fill_moves(const int *work, int *move, int *jb, float
 
 bool ensemble_form_eligible(const FlowShape &s) { return slice_form_eligible(s); }
 
-template <int U, int LK>
-static size_t ens_lds(const FlowShape &s) {
-    return U >= 3 ? (size_t)3 * SOLO4_NF * 64 * sizeof(float) : (size_t)s.nets_params() * sizeof(float);
-}
-
 // X: the x-space kernel (no flow: a.s carries D and NT only, no LDS); MIX: the instantiation that knows the DE move
 template <int U, int LK, bool X, bool MIX>
 static hipError_t ens_launch_k(const EnsArgs &a, int num_cu, bool launch, int *max_walkers, hipStream_t st) {
     const void *fn = X ? reinterpret_cast<const void *>(ensemble_x_kernel<U, LK, MIX>) : reinterpret_cast<const void *>(ensemble_kernel<U, LK, MIX>);
-    const size_t lds = X ? 0 : ens_lds<U, LK>(a.s);
+    const size_t lds = X ? 0 : solo_flow_lds_bytes<U>(a.s);
     int per_cu = 0;
     hipError_t e = ens_blocks_per_cu(fn, lds, &per_cu);
     if (e != hipSuccess) return e;
@@ -536,14 +497,9 @@ static hipError_t ens_launch_k(const EnsArgs &a, int num_cu, bool launch, int *m
 // launch (when `launch` and C fits) or only size: *max_walkers = the resident population of the instantiation the call would run
 template <bool X, bool MIX>
 static hipError_t ens_dispatch_m(const EnsArgs &a, int num_cu, bool launch, int *max_walkers, hipStream_t st) {
-    const bool rosen = a.like.id == NNEST_LIKE_ROSENBROCK;
-    switch (a.s.NT) {
-        case 1: return rosen ? ens_launch_k<1, NNEST_LIKE_ROSENBROCK, X, MIX>(a, num_cu, launch, max_walkers, st) : ens_launch_k<1, -1, X, MIX>(a, num_cu, launch, max_walkers, st);
-        case 2: return rosen ? ens_launch_k<2, NNEST_LIKE_ROSENBROCK, X, MIX>(a, num_cu, launch, max_walkers, st) : ens_launch_k<2, -1, X, MIX>(a, num_cu, launch, max_walkers, st);
-        case 3: return rosen ? ens_launch_k<3, NNEST_LIKE_ROSENBROCK, X, MIX>(a, num_cu, launch, max_walkers, st) : ens_launch_k<3, -1, X, MIX>(a, num_cu, launch, max_walkers, st);
-        case 4: return rosen ? ens_launch_k<4, NNEST_LIKE_ROSENBROCK, X, MIX>(a, num_cu, launch, max_walkers, st) : ens_launch_k<4, -1, X, MIX>(a, num_cu, launch, max_walkers, st);
-    }
-    return hipErrorInvalidConfiguration;
+    return solo_for_shape(a.s.NT, a.like.id, [&](auto sh) {
+        return ens_launch_k<decltype(sh)::U, decltype(sh)::LK, X, MIX>(a, num_cu, launch, max_walkers, st);
+    });
 }
 
 // a run with a DE step in it (a.mv.thr < 2^24) takes the MIX instantiation; every other run the stretch move's own, as before

@@ -2,13 +2,14 @@
 // proposal q, drawn, evaluated and reduced inside one kernel (include/nnest_hip.h nnest_importance_evidence has the definition in
 // full).  BUILD-DEFINED: the reference has no such estimator.  Sample k of the launch is sample
 // m = sample_offset + k of the run:
-//   z_m[4g .. 4g+3] = noise_normal4(seed, m, 0, g, stream 7);  lp(z_m) = nnest_mcmc_steps's target (the same inverse, ens_T, box test,
-//   NaN-inside rule, solo_loglike at scale 1 and ens_target);  logw_m = lp(z_m) - logb(z_m) in float64, logb the N(0, I) density.
+//   z_m[4g .. 4g+3] = noise_normal4(seed, m, 0, g, stream 7);  lp(z_m) = nnest_mcmc_steps's target (solo_latent.h's latent target
+//   combined by ens_target);  logw_m = lp(z_m) - logb(z_m) in float64, logb the N(0, I) density.
 //
-// Layout: mcmc_kernel's (the solo layout of nnest_solo.hip): one sample per wave, lane = 32 n + 16 h + p holds dims 2U p + 2u + c,
-// the four (n, h) rows hold copies; the weights in registers (x_dim <= 64) or in LDS.  The grid is PERSISTENT: a workgroup loads the
-// weights once, then wave `wg` of the grid's `nw` takes samples wg, wg + nw, ...  A lane's dims map to Philox blocks as mcmc_kernel's
-// eps do.  sum z^2 is reduced over a row's 16 positions in float64 (a butterfly: every lane of the wave ends with the same bits).
+// Layout: the solo layout (solo_latent.h, which states the target and the lane's normals; this kernel keeps a written-out copy of
+// both, for a measured reason: see the comment above it): one sample per wave; the weights in registers (x_dim <= 64) or in LDS.
+// The grid is PERSISTENT: a workgroup loads the weights once, then wave `wg` of the grid's `nw` takes samples wg, wg + nw, ...  A
+// lane's dims map to Philox blocks as mcmc_kernel's eps do.  sum z^2 is reduced over a row's 16 positions in float64 (a butterfly:
+// every lane of the wave ends with the same bits).
 //
 // Reduction, deterministic, no floating-point atomics: each wave keeps a running (a, S1, S2, n) (importance_walk.h), the four waves
 // of a workgroup are merged in wave order by one thread, which writes the workgroup's partial; importance_combine_kernel, one
@@ -19,8 +20,7 @@
 #include "flow_tile.h"
 #include "importance_walk.h"
 #include "nnest_internal.h"
-#include "solo_loglike.h"
-#include "solo_tile.h"
+#include "solo_latent.h"
 
 namespace nnest {
 
@@ -53,6 +53,11 @@ __global__ void importance_combine_kernel(const double *__restrict__ partials, d
     sums[3] = (double)n;
 }
 
+// This kernel keeps its target WRITTEN OUT (the text solo_latent.h states for mcmc_kernel and ensemble_x_kernel).  On the shared
+// header importance_kernel<1, -1> measured above the parent by more than the parent's spread in every run: x_dim 20 GaussianMix,
+// 2^22 samples, 4.324 -> 4.365 ms, spread 0.017 (profiles/latent_target/timing.txt, section 3); T and the box were then loaded through
+// nested branches instead of predicated loads, 3073 instructions for 3051.  As written here every instantiation is the parent's,
+// instruction for instruction.
 template <int U, int LK>
 __global__ void __launch_bounds__(256) importance_kernel(FlowShape s, const float *__restrict__ packed, ImpArgs a) {
     extern __shared__ __attribute__((aligned(16))) float wlds[];
@@ -112,7 +117,7 @@ __global__ void __launch_bounds__(256) importance_kernel(FlowShape s, const floa
         }
     LikeSpec like = a.like;
     like.scale = 1.0f;
-    // x <- f^-1(x) in place; returns lp, and logL(T(x)) through `logl` (mcmc_kernel's target)
+    // x <- f^-1(x) in place; returns lp, and logL(T(x)) through `logl` (solo_latent.h's target, combined by ens_target)
     auto target = [&](float (&xs)[2][U], double &logl) -> double {
         const float ld = solo_logdet_total(inverse(xs));
         float tx[2][U];
@@ -139,7 +144,7 @@ __global__ void __launch_bounds__(256) importance_kernel(FlowShape s, const floa
                 if (d < D) base[d] = v[c][u];
             }
     };
-    // the lane's 2U dims start at dim 2U pos: component `off` (0 or 2) of Philox block g0 (as mcmc_kernel draws its eps)
+    // the lane's 2U dims start at dim 2U pos: component `off` (0 or 2) of Philox block g0 (solo_lane_normals, written out)
     constexpr int NB = U <= 2 ? 1 : 2;
     const uint32_t g0 = (uint32_t)(2 * U * pos) >> 2;
     const uint32_t offm = ((2 * U * pos) & 3) != 0 ? 0xffffffffu : 0u;
@@ -164,7 +169,7 @@ __global__ void __launch_bounds__(256) importance_kernel(FlowShape s, const floa
             for (int c = 0; c < 2; ++c) {
                 const int j = 2 * u + c;
                 float e = n[j];
-                // (a lane whose dims start at component 2; a mask, as mcmc_kernel selects)
+                // (a lane whose dims start at component 2; a mask: solo_lane_normals)
                 if constexpr ((U & 1) != 0)
                     e = __uint_as_float((__float_as_uint(n[j]) & ~offm) | (__float_as_uint(n[j + 2]) & offm));
                 z[c][u] = live[c][u] ? e : 0.f;   // (padded dims stay 0)
@@ -227,22 +232,13 @@ hipError_t launch_importance_combine(const double *partials, double *sums, int g
 
 template <int U, int LK>
 static hipError_t importance_launch_k(const FlowShape &s, const float *packed, const ImpArgs &a, hipStream_t st) {
-    // (mcmc_kernel's LDS: the packed nets, or the three blocks' gathered fields at x_dim > 64)
-    const size_t lds = U >= 3 ? (size_t)3 * SOLO4_NF * 64 * sizeof(float) : (size_t)s.nets_params() * sizeof(float);
-    hipLaunchKernelGGL((importance_kernel<U, LK>), dim3(a.groups), dim3(256), lds, st, s, packed, a);
+    hipLaunchKernelGGL((importance_kernel<U, LK>), dim3(a.groups), dim3(256), solo_flow_lds_bytes<U>(s), st, s, packed, a);
     return hipGetLastError();
 }
 
 hipError_t launch_importance(const FlowShape &s, const float *packed, const ImpArgs &a, hipStream_t st) {
     if (a.M <= 0 || a.groups <= 0) return hipSuccess;
-    const bool rosen = a.like.id == NNEST_LIKE_ROSENBROCK;
-    switch (s.NT) {
-        case 1: return rosen ? importance_launch_k<1, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : importance_launch_k<1, -1>(s, packed, a, st);
-        case 2: return rosen ? importance_launch_k<2, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : importance_launch_k<2, -1>(s, packed, a, st);
-        case 3: return rosen ? importance_launch_k<3, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : importance_launch_k<3, -1>(s, packed, a, st);
-        case 4: return rosen ? importance_launch_k<4, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : importance_launch_k<4, -1>(s, packed, a, st);
-    }
-    return hipErrorInvalidConfiguration;
+    return solo_for_shape(s.NT, a.like.id, [&](auto sh) { return importance_launch_k<decltype(sh)::U, decltype(sh)::LK>(s, packed, a, st); });
 }
 
 }  // namespace nnest

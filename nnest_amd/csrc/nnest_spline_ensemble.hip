@@ -3,10 +3,11 @@
 // (nnest_ensemble.hip has it in full), with the same split table, the same draws and the same arithmetic (ensemble_common.h): only
 // the flow differs -- the spline's inverse (spline_inverse.h) replaces the coupling stack -- and with it the layout.
 //
-// Layout: the TEAM tile of the spline proposal kernels: 16 walkers per workgroup, four waves per tile.  Every wave carries the same
-// 16 walkers in the parity-class tiles of flow_tile.h (z, x and lp stay in registers for the launch) and takes the same decisions;
-// only the spline evaluations of the inverse are divided between the waves (SplineInverseTeam).  Wave 0 stores.  T's scale and
-// offset and the box sit in LDS ([4][32 NT] floats), read per evaluation as the lane's eight dimensions.
+// Layout: the TEAM tile of the spline proposal kernels (spline_latent.h, which also states the target): 16 walkers per workgroup,
+// four waves per tile.  Every wave carries the same 16 walkers in the parity-class tiles of flow_tile.h (z, x and lp stay in
+// registers for the launch) and takes the same decisions; only the spline evaluations of the inverse are divided between the waves
+// (SplineInverseTeam).  Wave 0 stores.  T's scale and offset and the box sit in LDS ([4][32 NT] floats: spl_tile_setup), read per
+// evaluation as the lane's eight dimensions.
 //
 // A step is two half-steps, each ONE tile evaluation.  In half h the lanes whose walker is in set h propose against their partner's
 // row; the other lanes, and rows >= C, evaluate their own point and the result is discarded (as slice_body treats idle walkers).
@@ -39,29 +40,16 @@
 #include <string.h>
 
 #include "ensemble_common.h"
-#include "flow_tile.h"
-#include "mh_common.h"
-#include "nnest_internal.h"
-#include "spline_train_tile.h"
+#include "spline_latent.h"
 
 namespace nnest {
-
-#include "spline_inverse.h"
-
-constexpr int SPL_ENS_TILE = 16;   // walkers per workgroup
-
-// class c of the lane's eight consecutive values v0 (dims 0..3 of its block) and v1 (4..7): load_tile's layout
-__device__ __forceinline__ f32x4 ens_class(const f32x4 &v0, const f32x4 &v1, int c) {
-    return c ? (f32x4){v0.y, v0.w, v1.y, v1.w} : (f32x4){v0.x, v0.z, v1.x, v1.z};
-}
 
 // The walk of one tile (16 walkers, this wave's copy) through the S steps of a launch.  tpar: [4][32 NT] in LDS -- std, mean, lo, hi
 // (padded dims: 0, 0, -inf, +inf).  `writer`: the wave that stores and publishes.
 template <int NT, class Inv>
 __device__ __forceinline__ void ens_tile_walk(const EnsArgs &a, int D, int tile, int lane, const Inv &inv, const float *tpar, bool writer) {
     const int S = a.S, C = a.C;
-    const int g = lane >> 4;
-    const int row = tile * SPL_ENS_TILE + (lane & 15);
+    const int row = tile * SPL_TILE_WALKERS + (lane & 15);
     const bool ok = row < C;
     const bool store = writer && ok;
     int *err = a.work;
@@ -76,28 +64,9 @@ __device__ __forceinline__ void ens_tile_walk(const EnsArgs &a, int D, int tile,
 
     // x <- f^-1(x) in place; returns lp
     auto target = [&](f32x4 (&xs)[2][NT]) -> double {
-        const float ld = group_sum(inv(xs));
-        f32x4 tx[2][NT];
-        int inside = 1;
-#pragma unroll
-        for (int tau = 0; tau < NT; ++tau) {
-            const f32x4 *p = reinterpret_cast<const f32x4 *>(tpar + 32 * tau + 8 * g);
-            constexpr int PW = 8 * NT;   // f32x4 per parameter
-            const f32x4 s0 = p[0], s1 = p[1], m0 = p[PW], m1 = p[PW + 1], l0 = p[2 * PW], l1 = p[2 * PW + 1], h0 = p[3 * PW], h1 = p[3 * PW + 1];
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const f32x4 sd = ens_class(s0, s1, c), mu = ens_class(m0, m1, c), lo = ens_class(l0, l1, c), hi = ens_class(h0, h1, c);
-                f32x4 t;
-                t.x = ens_T(xs[c][tau].x, sd.x, mu.x); t.y = ens_T(xs[c][tau].y, sd.y, mu.y);
-                t.z = ens_T(xs[c][tau].z, sd.z, mu.z); t.w = ens_T(xs[c][tau].w, sd.w, mu.w);
-                // (NaN counts as inside: UniformPrior, priors.py)
-                inside &= !(t.x < lo.x || t.x > hi.x) & !(t.y < lo.y || t.y > hi.y) & !(t.z < lo.z || t.z > hi.z) & !(t.w < lo.w || t.w > hi.w);
-                tx[c][tau] = t;
-            }
-        }
-        const bool in_prior = group_all(inside != 0, lane) != 0;
-        const double logl = loglike_tile<NT>(like, D, lane, tx);
-        return ens_target(logl, ld, in_prior, constrained, loglstar);
+        return spl_tile_eval<NT>(inv, tpar, like, D, lane, xs, [&](double logl, float ld, bool in_prior) {
+            return ens_target(logl, ld, in_prior, constrained, loglstar);
+        });
     };
 
     // ONE loop over the launch's evaluations, so that the inverse is inlined once: hs = -1 is the initial evaluation (nobody moves,
@@ -172,29 +141,12 @@ __device__ __forceinline__ void ens_tile_walk(const EnsArgs &a, int D, int tile,
     }
 }
 
-// LDS of the team form: the waves' layout-exchange buffers, the spline exchange, the log-det reduction (spline_mh_kernel_team), T
-__host__ __device__ inline int spl_ens_lds_tpar(int D, int NT) { return ((4 * 16 * (D + 1) + 3) & ~3) + 4 * NT * 64 * 4 + 4 * 16; }
-__host__ __device__ inline int spl_ens_lds_floats(int D, int NT) { return spl_ens_lds_tpar(D, NT) + 4 * 32 * NT; }
-
 template <int NT, int NH>
 __global__ void __launch_bounds__(256) spline_ensemble_kernel_team(EnsArgs a, SplArgs q) {
     extern __shared__ __attribute__((aligned(16))) float lds_buf[];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int D = q.sp.D;
-    float *bufs = lds_buf;                                                                 // 4 x 16 x (D+1)
-    f32x4 *xch = reinterpret_cast<f32x4 *>(lds_buf + ((4 * 16 * (D + 1) + 3) & ~3));      // 4 x NT x 64 f32x4
-    float *ldred = reinterpret_cast<float *>(xch + 4 * NT * 64);                           // 4 x 16
-    float *tpar = lds_buf + spl_ens_lds_tpar(D, NT);                                       // 4 x 32 NT
-    for (int d = threadIdx.x; d < 32 * NT; d += 256) {
-        const bool v = d < D;
-        tpar[d] = v ? a.t_std[d] : 0.f;
-        tpar[32 * NT + d] = v ? a.t_mean[d] : 0.f;
-        tpar[2 * 32 * NT + d] = v && a.lo ? a.lo[d] : -INFINITY;
-        tpar[3 * 32 * NT + d] = v && a.hi ? a.hi[d] : INFINITY;
-    }
-    __syncthreads();
-    SplineInverseTeam<NT, NH, 4> inv = {q.img, q.sp, bufs + (size_t)wv * 16 * (D + 1), xch, ldred, lane, wv};
-    ens_tile_walk<NT>(a, D, blockIdx.x, lane, inv, tpar, wv == 0);
+    const SplTile<NT, NH> t = spl_tile_setup<NT, NH>(lds_buf, q, a.t_std, a.t_mean, a.lo, a.hi, lane, wv);
+    ens_tile_walk<NT>(a, q.sp.D, blockIdx.x, lane, t.inv, t.tpar, wv == 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -202,30 +154,22 @@ __global__ void __launch_bounds__(256) spline_ensemble_kernel_team(EnsArgs a, Sp
 template <int NT, int NH>
 static hipError_t spl_ens_launch_t(const EnsArgs &a, const SplArgs &q, int num_cu, bool launch, int *max_walkers, hipStream_t st) {
     const void *fn = reinterpret_cast<const void *>(spline_ensemble_kernel_team<NT, NH>);
-    const size_t lds = (size_t)spl_ens_lds_floats(q.sp.D, NT) * sizeof(float);
+    const size_t lds = (size_t)spl_tile_lds_floats(q.sp.D, NT) * sizeof(float);
     int per_cu = 0;
     hipError_t e = ens_blocks_per_cu(fn, lds, &per_cu);
     if (e != hipSuccess) return e;
-    *max_walkers = SPL_ENS_TILE * per_cu * num_cu;
+    *max_walkers = SPL_TILE_WALKERS * per_cu * num_cu;
     if (!launch) return hipSuccess;
     if (a.C > *max_walkers) return hipErrorInvalidConfiguration;   // (never a grid that is not proven resident)
-    hipLaunchKernelGGL((spline_ensemble_kernel_team<NT, NH>), dim3((a.C + SPL_ENS_TILE - 1) / SPL_ENS_TILE), dim3(256), lds, st, a, q);
+    hipLaunchKernelGGL((spline_ensemble_kernel_team<NT, NH>), dim3((a.C + SPL_TILE_WALKERS - 1) / SPL_TILE_WALKERS), dim3(256), lds, st, a, q);
     return hipGetLastError();
 }
 
-// launch (when `launch` and C fits) or only size: *max_walkers = the resident population of the instantiation the call would run.
-// The shapes of the team form of the proposal kernel (launch_spline_mh_team)
+// launch (when `launch` and C fits) or only size: *max_walkers = the resident population of the instantiation the call would run
 static hipError_t spl_ens_dispatch(const EnsArgs &a, const SplArgs &q, int num_cu, bool launch, int *max_walkers, hipStream_t st) {
-    if (!spline_shape_supported(q.sp)) return hipErrorInvalidConfiguration;
-    switch (q.sp.NTh * 10 + q.sp.NH) {
-        case 11: return spl_ens_launch_t<1, 1>(a, q, num_cu, launch, max_walkers, st);
-        case 21: return spl_ens_launch_t<2, 1>(a, q, num_cu, launch, max_walkers, st);
-        case 31: return spl_ens_launch_t<3, 1>(a, q, num_cu, launch, max_walkers, st);
-        case 41: return spl_ens_launch_t<4, 1>(a, q, num_cu, launch, max_walkers, st);
-        case 12: return spl_ens_launch_t<1, 2>(a, q, num_cu, launch, max_walkers, st);
-        case 22: return spl_ens_launch_t<2, 2>(a, q, num_cu, launch, max_walkers, st);
-    }
-    return hipErrorInvalidConfiguration;
+    return spl_tile_for_shape(q.sp, [&](auto sh) {
+        return spl_ens_launch_t<decltype(sh)::NT, decltype(sh)::NH>(a, q, num_cu, launch, max_walkers, st);
+    });
 }
 
 hipError_t spline_ensemble_max_walkers(const SplArgs &q, int num_cu, int *out) {
@@ -246,7 +190,7 @@ int launch_spline_ensemble(const SplArgs &q, const EnsArgs &a, int num_cu, hipSt
     if (e != hipSuccess) { snprintf(msg, msg_len, "occupancy query: %s", hipGetErrorString(e)); return NNEST_E_HIP; }
     if (a.C > max_walkers) {
         snprintf(msg, msg_len, "spline ensemble: %d walkers > %d resident (%d walkers per workgroup, every workgroup resident); the round route takes it",
-                 a.C, max_walkers, SPL_ENS_TILE);
+                 a.C, max_walkers, SPL_TILE_WALKERS);
         return NNEST_E_UNSUPPORTED;
     }
     if ((e = launch_ensemble_split(a.work, nullptr, a.C, a.S, a.step0, a.seed, st)) != hipSuccess) {
