@@ -1,0 +1,54 @@
+"""DeviceTarget: what the fused routes hand a kernel as the target -- the likelihood (an id the kernels know and its parameters), the
+affine T(x) = x * t_std + t_mean the likelihood sees, and the prior box [lo, hi] on T(x).  `Sampler._device_target` decides it, once
+per run; every launch of the run takes the same staged tensors (`launch_kwargs`)."""
+import numpy as np
+
+_FIXED = ('like_id', 'like_params', 't_std', 't_mean', 'lo', 'hi')
+
+
+def affine_on_device(x, t_std, t_mean):
+    """T(x) = x * t_std + t_mean on float32 device tensors: two roundings, as the fused kernels compute it"""
+    return x * t_std + t_mean
+
+
+class DeviceTarget(object):
+    """like_id, like_params; t_std, t_mean: float32 [D] or both None (the identity); lo, hi: float32 [D] or both None (no prior).
+    The fields are fixed once set: another transform is another target (`with_transform`), so tensors staged for one (std, mean)
+    never serve another."""
+
+    def __init__(self, like_id, like_params=(), t_std=None, t_mean=None, lo=None, hi=None):
+        if (t_std is None) != (t_mean is None) or (lo is None) != (hi is None):
+            raise ValueError('DeviceTarget: t_std and t_mean, and lo and hi: both or neither')
+        vec = lambda v: None if v is None else np.array(v, np.float32).reshape(-1)   # (a copy, cast as the bindings cast)
+        self.like_id, self.like_params = int(like_id), tuple(like_params or ())
+        self.t_std, self.t_mean, self.lo, self.hi = vec(t_std), vec(t_mean), vec(lo), vec(hi)
+        for v in (self.t_std, self.t_mean, self.lo, self.hi):
+            if v is not None:
+                v.setflags(write=False)
+        self._staged = {}
+
+    def __setattr__(self, name, value):
+        if name in _FIXED and name in self.__dict__:
+            raise AttributeError('DeviceTarget.%s is fixed: with_transform() makes the target under another T' % name)
+        object.__setattr__(self, name, value)
+
+    def with_transform(self, t_std, t_mean):
+        """the same likelihood and box under T(x) = x * t_std + t_mean: neither depends on T, so nothing is checked again"""
+        return DeviceTarget(self.like_id, self.like_params, t_std, t_mean, self.lo, self.hi)
+
+    def launch_kwargs(self, device):
+        """the keywords the flow bindings take (t_std, t_mean, lo, hi as float32 tensors on `device`, and like_params): staged on the
+        first call for a device, the same tensors after it"""
+        from . import flow
+        key = str(device)
+        if key not in self._staged:
+            vecs = flow.target_vectors('DeviceTarget', device, self.t_std, self.t_mean, self.lo, self.hi)
+            self._staged[key] = dict(zip(('t_std', 't_mean', 'lo', 'hi'), vecs), like_params=self.like_params)
+        return dict(self._staged[key])
+
+    def transform(self, x):
+        """T(x) of a float32 tensor on its own device"""
+        if self.t_std is None:
+            return x
+        kw = self.launch_kwargs(x.device)
+        return affine_on_device(x, kw['t_std'], kw['t_mean'])

@@ -6,7 +6,8 @@ EMCEE'S MOVE, so parity with emcee is statistical.  With chain_stats=True the ru
 nnest_amd.evaluation; the trace plots are not drawn.
 
 `bootstrap` (ensemble.py:81-184) starts without training samples: the same stretch move in X space on logL(x) + prior(x)
-(`Sampler._ensemble_sample_x`: the fused kernel nnest_ensemble_x_steps, or the round driver on an identity flow), emcee's integrated
+(`Sampler._ensemble_sample_x`: the fused kernel nnest_ensemble_x_steps where `Sampler._device_target` gives a target, or the round
+driver on an identity flow), emcee's integrated
 autocorrelation time of that run (nnest_amd.evaluation.integrated_autocorr_time), emcee's discard / thin rule for the first
 training samples, then rounds of train + latent-space run, each thinned into the next round's training samples by getdist's
 makeSingleSamples rule.  Neither emcee nor getdist is used: both rules are restated (see `bootstrap`)."""

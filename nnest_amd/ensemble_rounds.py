@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from . import flow as _flow
+from .device_target import affine_on_device
 
 
 def work_buffer(lib, C, steps, dev):
@@ -61,10 +62,6 @@ def fill_moves(C, D, steps, moves=None, seed=0, step0=0, device=None):
         _lib.check(lib.nnest_ensemble_fill_moves(_lib.ptr(work), _lib.ptr(move), _lib.ptr(jb), _lib.ptr(gamma), int(C), int(D), int(steps),
                                                  step0, seed, _lib.moves_ref(mv), sp))
     return move, jb, gamma
-
-
-def _dev_vec(v, D, dev):
-    return None if v is None else torch.as_tensor(np.asarray(v, np.float32).reshape(D)).to(dev)
 
 
 class IdentityFlow(object):
@@ -122,12 +119,9 @@ def ensemble_rounds(flow, z, steps, state=None, lp=None, t_std=None, t_mean=None
         propose_fn = lib.nnest_ensemble_rounds_propose if mv is None else lib.nnest_ensemble_rounds_moves_propose
         accept_fn = lib.nnest_ensemble_rounds_accept if mv is None else lib.nnest_ensemble_rounds_moves_accept
         mv_arg = () if mv is None else (_lib.moves_ref(mv),)
+        t_std_t = t_mean_t = lo_t = hi_t = None
         if like_id is not None:
-            t_std_t = _dev_vec(np.ones(D) if t_std is None else t_std, D, dev)
-            t_mean_t = _dev_vec(np.zeros(D) if t_mean is None else t_mean, D, dev)
-            lo_t, hi_t = _dev_vec(lo, D, dev), _dev_vec(hi, D, dev)
-        else:
-            t_std_t = t_mean_t = lo_t = hi_t = None
+            t_std_t, t_mean_t, lo_t, hi_t = _flow.target_vectors('ensemble_rounds', dev, t_std, t_mean, lo, hi, D=D, identity=True)
         work = work_buffer(lib, C, steps, dev)
         _lib.check(lib.nnest_ensemble_fill_noise(_lib.ptr(work), None, C, steps, step0, seed, sp))
 
@@ -135,8 +129,7 @@ def ensemble_rounds(flow, z, steps, state=None, lp=None, t_std=None, t_mean=None
             """x, ld, logl, lprior (device) and derived (host) of the rows q[:n]"""
             x, ld = flow.inverse(q[:n])
             if like_id is not None:
-                tx = x * t_std_t + t_mean_t   # (two roundings, as the fused kernel's T)
-                return x, ld, _flow.loglike(like_id, tx, 1.0, device=dev, like_params=like_params), None, None
+                return x, ld, _flow.loglike(like_id, affine_on_device(x, t_std_t, t_mean_t), 1.0, device=dev, like_params=like_params), None, None
             xh = x.cpu().numpy()
             out = loglike(xh)
             lv, dv = out if isinstance(out, tuple) else (out, None)

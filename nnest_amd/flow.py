@@ -57,6 +57,28 @@ def _as_dev_f32(x, device):
     return x.contiguous()
 
 
+def target_vectors(who, device, t_std, t_mean, lo, hi, D=None, identity=False):
+    """a device target's per-dimension vectors as the C entries take them: (t_std, t_mean, lo, hi), each a float32 [D] tensor on
+    `device` or None.  Each comes as an array (cast on the host, staged), as None, or as a float32 tensor already on the device, which
+    passes through untouched (DeviceTarget.launch_kwargs stages a run's once).  t_std and t_mean: both or neither, and so lo and hi;
+    identity=True fills a missing T with (1, 0), for the entries that require one"""
+    if (t_std is None) != (t_mean is None):
+        raise ValueError('%s: t_std and t_mean: both or neither' % who)
+    if (lo is None) != (hi is None):
+        raise ValueError('%s: lo and hi: both or neither' % who)
+    device = torch.device(device)
+
+    def vec(v, fill):
+        if v is None:
+            return torch.full((D,), fill, dtype=torch.float32, device=device) if identity and fill is not None else None
+        if torch.is_tensor(v) and v.dtype == torch.float32 and v.device == device and v.is_contiguous():
+            return v
+        if not torch.is_tensor(v):
+            v = np.array(v, np.float32)   # (cast on the host; a copy, so a read-only array stages too)
+        return _as_dev_f32(v.reshape(1, -1 if D is None else D), device).reshape(-1)
+    return vec(t_std, 1.0), vec(t_mean, 0.0), vec(lo, None), vec(hi, None)
+
+
 SCALE_MODES = {'': 0, 'translate': 1, 'constant': 2}
 TRAIN_KERNEL_MAX_BATCH = 128   # row slots of the one-launch training kernels (nnest_train.hip TRAIN_MAX_ROWS; nnest_spline_train.hip)
 
@@ -364,10 +386,7 @@ class _HipFlow(object):
         C, D, steps = z.shape[0], self.D, int(steps)
         _lib.ens_moves_mix(mv, C, 'ensemble_steps')
         f32 = dict(dtype=torch.float32, device=dev)
-        vec = lambda v, fill: torch.full((D,), fill, **f32) if v is None else _as_dev_f32(np.asarray(v, np.float32).reshape(1, D), dev).reshape(D)
-        t_std, t_mean = vec(t_std, 1.0), vec(t_mean, 0.0)
-        lo_t = None if lo is None else vec(lo, 0.0)
-        hi_t = None if hi is None else vec(hi, 0.0)
+        t_std, t_mean, lo_t, hi_t = target_vectors('ensemble_steps', dev, t_std, t_mean, lo, hi, D=D, identity=True)
         if lp is not None:
             lp = torch.as_tensor(lp, dtype=torch.float64).to(dev).contiguous()
         out = dict(z=torch.empty(C, D, **f32), x=torch.empty(C, D, **f32), lp=torch.empty(C, dtype=torch.float64, device=dev),
@@ -413,12 +432,9 @@ class _HipFlow(object):
             raise ValueError('mcmc_steps: z must be shaped [C, %d], got %s' % (D, tuple(z.shape)))
         if (lp is None) != (logl is None):
             raise ValueError('mcmc_steps: lp and logl: both or neither')
-        if (t_std is None) != (t_mean is None):
-            raise ValueError('mcmc_steps: t_std and t_mean: both or neither')
         f32 = dict(dtype=torch.float32, device=dev)
         f64 = dict(dtype=torch.float64, device=dev)
-        vec = lambda v: None if v is None else _as_dev_f32(np.asarray(v, np.float32).reshape(1, D), dev).reshape(D)
-        t_std, t_mean, lo_t, hi_t = vec(t_std), vec(t_mean), vec(lo), vec(hi)
+        t_std, t_mean, lo_t, hi_t = target_vectors('mcmc_steps', dev, t_std, t_mean, lo, hi, D=D)
         if lp is not None:
             lp = torch.as_tensor(lp, dtype=torch.float64).to(dev).contiguous()
             logl = torch.as_tensor(logl, dtype=torch.float64).to(dev).contiguous()
@@ -469,12 +485,9 @@ class _HipFlow(object):
         M, D = int(M), self.D
         if M < 0:
             raise ValueError('importance_evidence: M=%d' % M)
-        if (t_std is None) != (t_mean is None):
-            raise ValueError('importance_evidence: t_std and t_mean: both or neither')
         f32 = dict(dtype=torch.float32, device=dev)
         f64 = dict(dtype=torch.float64, device=dev)
-        vec = lambda v: None if v is None else _as_dev_f32(np.asarray(v, np.float32).reshape(1, D), dev).reshape(D)
-        t_std, t_mean, lo_t, hi_t = vec(t_std), vec(t_mean), vec(lo), vec(hi)
+        t_std, t_mean, lo_t, hi_t = target_vectors('importance_evidence', dev, t_std, t_mean, lo, hi, D=D)
         out = dict(sums=torch.empty(4, **f64))
         if want_samples:
             out.update(z=torch.empty(M, D, **f32), x=torch.empty(M, D, **f32), logl=torch.empty(M, **f64), logw=torch.empty(M, **f64))
@@ -1044,11 +1057,8 @@ def ensemble_x_steps(like_id, x, steps, t_std=None, t_mean=None, lo=None, hi=Non
     (C, D), steps = x.shape, int(steps)
     mv = _lib.ens_moves(moves, 'ensemble_x_steps')
     _lib.ens_moves_mix(mv, C, 'ensemble_x_steps')
-    if (t_std is None) != (t_mean is None):
-        raise ValueError('ensemble_x_steps: t_std and t_mean: both or neither')
     f32 = dict(dtype=torch.float32, device=dev)
-    vec = lambda v: None if v is None else _as_dev_f32(np.asarray(v, np.float32).reshape(1, D), dev).reshape(D)
-    t_std, t_mean, lo_t, hi_t = vec(t_std), vec(t_mean), vec(lo), vec(hi)
+    t_std, t_mean, lo_t, hi_t = target_vectors('ensemble_x_steps', dev, t_std, t_mean, lo, hi, D=D)
     if lp is not None:
         lp = torch.as_tensor(lp, dtype=torch.float64).to(dev).contiguous()
     lib = _lib.load()

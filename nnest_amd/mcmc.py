@@ -5,7 +5,7 @@ forwarded (mcmc.py:118-120): the chains run at the fixed step 2 / sqrt(x_dim).  
 chain statistics (acceptance, ESS, jump distance: sampler.py:451-452 every `stats_interval` steps, mcmc.py:119-120 at the end),
 computed on the GPU by nnest_amd.evaluation (plain numpy in the reference, nnest/utils/evaluation.py; no getdist involved).
 `run(..., route='fused')` runs the chains inside one kernel per launch (Sampler._mcmc_sample_device) where the likelihood, the prior
-and the flow allow it; the default is the host step loop, draw for draw as before."""
+and the flow allow it (Sampler._device_target decides, once per run); the default is the host step loop, draw for draw as before."""
 import logging
 
 import numpy as np
@@ -43,14 +43,14 @@ class MCMCSampler(Sampler):
         training_samples = (training_samples - mean) / std          # normalise
         self._install_transform(mean, std)                           # T(x) = x * std + mean (the K4 kernels only know x -> s * x)
         if route == 'fused':
-            why = self._mcmc_device_refusal()
+            target, why = self._device_target(entry='mcmc')
             if why is not None:
                 raise ValueError('MCMCSampler.run: the fused route does not take %s' % why)
         self.trainer.train(training_samples, jitter=initial_jitter)
         if route == 'fused':
             samples, latent_samples, derived_samples, loglikes, scale, ncall = self._mcmc_sample_device(
                 mcmc_steps, num_chains=mcmc_num_chains, init_samples=init_samples, output_interval=output_interval,
-                stats_interval=stats_interval, seed=seed)
+                stats_interval=stats_interval, seed=seed, target=target)
             if self.chain_stats:   # (the interval lines were logged by the run)
                 self._log_chain_stats(samples, (std, mean), mcmc_steps, None, prefix_offset=1, min_step=0)
         else:

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .device_target import DeviceTarget
 from .priors import UniformPrior
 from .utils import create_logger, get_or_create_run_dir, write_rows_e5
 
@@ -211,19 +212,28 @@ class Sampler(object):
         netG = getattr(self.trainer, 'netG', None)
         if like_id is None or getattr(netG, 'mh_steps', None) is None or self._linear_scale is None or self.num_derived != 0:
             return None
-        prior = self._user_prior
-        if prior is None or self._transform_prior or not getattr(prior, 'is_unit_box', lambda: False)():
+        if not self._unit_box_on_x():
             return None
         # verify the kernel's likelihood against the host callable on a few points before trusting it
-        from . import flow
-        x = np.random.RandomState(4321).uniform(-1, 1, size=(32, self.x_dim)).astype(np.float32)
         self._fused_like_params = tuple(getattr(like, 'hip_like_params', ()) or ())
-        dev = flow.loglike(like_id, x, self._linear_scale, device=netG.device, like_params=self._fused_like_params).cpu().numpy()
-        host = np.asarray(like(self._linear_scale * x.astype(np.float64)), dtype=np.float64)
-        if not np.allclose(dev, host, rtol=1e-5, atol=1e-4):
-            self.logger.warning('fused likelihood id %d disagrees with the host callable; using the host protocol' % like_id)
+        if not self._probe_agrees(like_id, self._fused_like_params, self._linear_scale, warn='fused '):
             return None
         return like_id
+
+    def _probe_agrees(self, like_id, params, scale=1.0, affine=None, warn=''):
+        """does the kernels' likelihood `like_id` agree with the host callable?  On 32 fixed points of the unit box, handed to the
+        kernel as each caller hands it its x: raw, with like_scale = `scale` (the K4 routes), or as T(x) = x * std + mean computed
+        here in float32, with scale 1 (the device targets: `affine` = (std, mean)).  Warns (`warn` opens the line) where it does not"""
+        from . import flow
+        x = np.random.RandomState(4321).uniform(-1, 1, size=(32, self.x_dim)).astype(np.float32)
+        if affine is not None:
+            x = x * np.asarray(affine[0], np.float32) + np.asarray(affine[1], np.float32)
+        dev = flow.loglike(like_id, x, scale, device=self.trainer.netG.device, like_params=params).cpu().numpy()
+        host = np.asarray(self._user_loglike(scale * x.astype(np.float64)), dtype=np.float64)
+        ok = bool(np.allclose(dev, host, rtol=1e-5, atol=1e-4))
+        if not ok:
+            self.logger.warning('%slikelihood id %d disagrees with the host callable; using the host protocol' % (warn, like_id))
+        return ok
 
     def _next_seed(self):
         """64-bit seed for the in-kernel Philox streams.  Drawn from a PRIVATE generator seeded once from the seed of torch's
@@ -271,7 +281,8 @@ class Sampler(object):
         return self._mcmc_sample_host(mcmc_steps, step_size, dynamic_step_size, num_chains, init_samples,
                                       init_loglikes, init_derived, loglstar, max_start_tries, prior_volume_steps)
 
-    def _unit_box_prior(self):
+    def _unit_box_on_x(self):
+        """the NestedSampler's prior: the unit box on x, not on T(x) (`transform_prior=False`)"""
         p = self._user_prior
         return p is not None and not self._transform_prior and bool(getattr(p, 'is_unit_box', lambda: False)())
 
@@ -289,7 +300,7 @@ class Sampler(object):
         fused_slice = getattr(netG, 'supports_fused_slice', None)
         if self._fused_like_id is None:
             from .slice_rounds import slice_rounds
-            prior = None if self._unit_box_prior() else (lambda x: self.prior(x) > -1e30)
+            prior = None if self._unit_box_on_x() else (lambda x: self.prior(x) > -1e30)
             res = slice_rounds(netG, *args, loglike=self.loglike, prior=prior, num_derived=self.num_derived, init_derived=init_derived, **kw)
         elif rounds or (fused_slice is not None and not fused_slice(C)):
             from .slice_rounds import slice_rounds
@@ -734,38 +745,50 @@ class Sampler(object):
             return np.full(self.x_dim, self._linear_scale), np.zeros(self.x_dim)
         return None
 
-    def _device_likelihood(self, affine):
-        """(like_id, like_params) when the likelihood runs on the device for the transform `affine` (std, mean), else None: a
-        likelihood the kernels know, checked against the host callable on T(x), and no derived parameters"""
+    ENTRY_NEEDS = {'mcmc': ('mcmc',), 'mcmc_tempered': ('mcmc', 'mcmc_tempered'), 'importance': ('importance',)}
+    ENTRY_KERNEL = {'mcmc': 'random-walk Metropolis', 'mcmc_tempered': 'tempered random-walk Metropolis', 'importance': 'importance-sampling'}
+
+    def _device_target(self, affine=None, entry=None, unit_box_on_x=False):
+        """(target, None) where the likelihood and the prior run on the device under the transform `affine` = (std, mean) (None:
+        `_ensemble_affine()`), else (None, what is not taken: the words the front ends put after 'the fused route does not take').
+        A DeviceTarget: no derived parameters, a likelihood the kernels know that agrees with the host callable on T(x), and no prior
+        or a UniformPrior on T(x) -- with `unit_box_on_x` (the evidence) also the NestedSampler's prior, the unit box on x under
+        x -> s * x (`_linear_scale`): the box on T(x) is +-|s|.  `entry` names the flow entry a front end needs bound ('mcmc',
+        'mcmc_tempered' -- which needs 'mcmc' too --, 'importance'): every parameter must then be fast and, for 'importance', the
+        library must take the flow's shape and base (`importance_refusal`: nothing is launched).  The ensemble routes name none:
+        they fall back to rounds.  One probe of the host callable (`_probe_agrees`) per call: a run resolves once and hands the
+        target down"""
+        affine = self._ensemble_affine() if affine is None else affine
+        netG = self.trainer.netG
+        if self.num_derived != 0:
+            return None, 'derived parameters (num_derived=%d)' % self.num_derived
+        if entry is not None and self.num_slow != 0:
+            return None, 'the fast/slow proposal (num_slow=%d)' % self.num_slow
+        for need in self.ENTRY_NEEDS.get(entry, ()):
+            if need not in getattr(netG, '_sym', ()):
+                return None, 'the flow %s (no fused %s kernel)' % (type(netG).__name__, self.ENTRY_KERNEL[need])
         like = self._user_loglike
         like_id = getattr(like, 'hip_like_id', None)
-        if like_id is None or affine is None or self.num_derived != 0:
-            return None
-        from . import flow
-        params = tuple(getattr(like, 'hip_like_params', ()) or ())
-        std, mean = (np.asarray(v, np.float32) for v in affine)
-        x = np.random.RandomState(4321).uniform(-1, 1, size=(32, self.x_dim)).astype(np.float32)
-        tx = x * std + mean
-        dev = flow.loglike(like_id, tx, 1.0, device=self.trainer.netG.device, like_params=params).cpu().numpy()
-        host = np.asarray(like(tx.astype(np.float64)), dtype=np.float64)
-        if not np.allclose(dev, host, rtol=1e-5, atol=1e-4):
-            self.logger.warning('ensemble: likelihood id %d disagrees with the host callable; using the host protocol' % like_id)
-            return None
-        return like_id, params
-
-    def _ensemble_device_like(self, affine):
-        """(like_id, like_params, lo, hi) when the likelihood and the prior run on the device for the transform `affine`, else None:
-        a likelihood the kernels know (checked against the host callable), no derived parameters, and no prior or a box on T(x)"""
-        if getattr(self._user_loglike, 'hip_like_id', None) is None or affine is None or self.num_derived != 0:
-            return None
+        if like_id is None:
+            return None, 'a likelihood the kernels do not know (a Python callable)'
+        if entry == 'importance':
+            why = netG.importance_refusal(like_id)
+            if why is not None:
+                return None, 'the flow %s: %s' % (type(netG).__name__, why)
+        refused = 'this transform, likelihood or prior (an affine transform, a likelihood that agrees with the kernel\'s, and no prior%s)' % (
+            ', a UniformPrior on T(x) or the unit box on x' if unit_box_on_x else ' or a UniformPrior on T(x)')
         prior = self._user_prior
-        lo = hi = None
-        if prior is not None:
-            if not (self._transform_prior and isinstance(prior, UniformPrior) and type(prior).__call__ is UniformPrior.__call__):
-                return None
-            lo, hi = np.asarray(prior.minimum, np.float32), np.asarray(prior.maximum, np.float32)
-        got = self._device_likelihood(affine)
-        return None if got is None else got + (lo, hi)
+        box = (None, None)
+        if unit_box_on_x and self._unit_box_on_x() and self._linear_scale is not None:
+            s = np.full(self.x_dim, abs(float(self._linear_scale)), np.float32)
+            box = (-s, s)
+        elif prior is not None:   # (a UniformPrior on T(x) whose rule is its own, or refused)
+            ok = self._transform_prior and isinstance(prior, UniformPrior) and type(prior).__call__ is UniformPrior.__call__
+            box = (prior.minimum, prior.maximum) if ok else None
+        params = tuple(getattr(like, 'hip_like_params', ()) or ())
+        if affine is None or box is None or not self._probe_agrees(like_id, params, affine=affine, warn='ensemble: '):
+            return None, refused
+        return DeviceTarget(like_id, params, affine[0], affine[1], *box), None
 
     def _install_transform(self, mean, std):
         """T(x) = x * std + mean, also as per-dimension float arrays for the device routes"""
@@ -774,70 +797,16 @@ class Sampler(object):
         self._linear_scale = None   # (the Metropolis kernels only know x -> s * x)
         self._fused_like_id = None
 
-    def _mcmc_device_refusal(self):
-        """why `_mcmc_sample_device` does not take this sampler (a string), or None where it does: the likelihood and the prior must
-        run on the device for the installed transform (`_ensemble_device_like`), every parameter is fast, and the flow's family
-        binds an `mcmc` entry (HipNVP, HipSpline)"""
-        if self.num_derived != 0:
-            return 'derived parameters (num_derived=%d)' % self.num_derived
-        if self.num_slow != 0:
-            return 'the fast/slow proposal (num_slow=%d)' % self.num_slow
-        netG = self.trainer.netG
-        if 'mcmc' not in getattr(netG, '_sym', ()):
-            return 'the flow %s (no fused random-walk Metropolis kernel)' % type(netG).__name__
-        if getattr(self._user_loglike, 'hip_like_id', None) is None:
-            return 'a likelihood the kernels do not know (a Python callable)'
-        if self._ensemble_device_like(self._ensemble_affine()) is None:
-            return 'this transform, likelihood or prior (an affine transform, a likelihood that agrees with the kernel\'s, and no prior or a UniformPrior on T(x))'
-        return None
-
     # ---- importance-sampled evidence from the trained flow (build-defined: the reference has none) ---------------------------------
     IMPORTANCE_CHUNK = 1 << 22   # samples per launch when nothing per sample comes back
-
-    def _prior_is_unit_box_on_x(self):
-        """the NestedSampler's prior: the unit box on x, not on T(x) (`transform_prior=False`)"""
-        prior = self._user_prior
-        return prior is not None and not self._transform_prior and bool(getattr(prior, 'is_unit_box', lambda: False)())
-
-    def _importance_device_like(self, affine):
-        """`_ensemble_device_like` for the evidence: (like_id, like_params, lo, hi).  Beside no prior and a UniformPrior on T(x) it
-        takes the NestedSampler's prior, the unit box on x, under x -> s * x (`_linear_scale`): the box on T(x) is +-|s|"""
-        if not (self._prior_is_unit_box_on_x() and self._linear_scale is not None):
-            return self._ensemble_device_like(affine)
-        got = self._device_likelihood(affine)
-        if got is None:
-            return None
-        s = abs(float(self._linear_scale))
-        return got + (np.full(self.x_dim, -s, np.float32), np.full(self.x_dim, s, np.float32))
 
     def _importance_constant(self, affine):
         """what turns the weights' log Z over x into `importance_evidence`'s logz (its docstring has the convention)"""
         if self._user_prior is not None and not self._transform_prior:   # a prior on x: Z over x is the evidence already
-            return -self.x_dim * np.log(2.0) if self._prior_is_unit_box_on_x() else 0.0   # (the unit box, normalised: 2^-D)
+            return -self.x_dim * np.log(2.0) if self._unit_box_on_x() else 0.0   # (the unit box, normalised: 2^-D)
         if affine is None:
             return 0.0
         return float(np.sum(np.log(np.abs(np.asarray(affine[0], np.float64)))))
-
-    def _importance_device_refusal(self):
-        """why the fused route of `importance_evidence` does not take this sampler (a string), or None where it does: the
-        conditions of `_mcmc_device_refusal` (with the unit box on x of the NestedSampler taken too), and what the library says of
-        the flow's shape and base (`importance_refusal`: nothing is launched)"""
-        if self.num_derived != 0:
-            return 'derived parameters (num_derived=%d)' % self.num_derived
-        if self.num_slow != 0:
-            return 'the fast/slow proposal (num_slow=%d)' % self.num_slow
-        netG = self.trainer.netG
-        if 'importance' not in getattr(netG, '_sym', ()):
-            return 'the flow %s (no fused importance-sampling kernel)' % type(netG).__name__
-        like_id = getattr(self._user_loglike, 'hip_like_id', None)
-        if like_id is None:
-            return 'a likelihood the kernels do not know (a Python callable)'
-        why = netG.importance_refusal(like_id)
-        if why is not None:
-            return 'the flow %s: %s' % (type(netG).__name__, why)
-        if self._importance_device_like(self._ensemble_affine()) is None:
-            return 'this transform, likelihood or prior (an affine transform, a likelihood that agrees with the kernel\'s, and no prior, a UniformPrior on T(x) or the unit box on x)'
-        return None
 
     def _importance_host_sums(self, n):
         """the sums (a, S1, S2, n_live) of n samples of the flow with the user's callables on the host, and (T(x), logw)"""
@@ -860,8 +829,8 @@ class Sampler(object):
         any chain has mixed, with an error bar and an effective sample size.  For every front end, once a flow has been trained.
         route: 'fused' -- drawn, evaluated and reduced inside the kernel (include/nnest_hip.h nnest_importance_evidence,
         nnest_spline_importance_evidence), in launches of `chunk` samples addressed by their global index (the cut does not change
-        a sample; chunk defaults to 2^22, or by ENSEMBLE_HISTORY_BYTES when samples come back); taken where `_mcmc_sample_device`
-        would take the sampler (a likelihood the kernels know, no derived or slow parameters, an affine transform, no prior or a
+        a sample; chunk defaults to 2^22, or by ENSEMBLE_HISTORY_BYTES when samples come back); taken where `_device_target`
+        gives a target (a likelihood the kernels know, no derived or slow parameters, an affine transform, no prior or a
         UniformPrior on T(x), HipNVP in the default shape or HipSpline) or the prior is the NestedSampler's unit box on x, and the
         base is N(0, I); ValueError, naming what is not taken, otherwise.  'host' -- netG.sample / netG.log_probs with the
         likelihood and the prior as the host Metropolis route evaluates them: every flow, base, prior and Python likelihood.
@@ -881,16 +850,15 @@ class Sampler(object):
         M = int(num_samples)
         if M < 1:
             raise ValueError('importance_evidence: num_samples=%d' % M)
-        why = None if route == 'host' else self._importance_device_refusal()
+        target, why = (None, None) if route == 'host' else self._device_target(entry='importance', unit_box_on_x=True)
         if route == 'fused' and why is not None:
             raise ValueError('importance_evidence: the fused route does not take %s' % why)
-        route = 'fused' if (route != 'host' and why is None) else 'host'
+        route = 'host' if target is None else 'fused'
         D = self.x_dim
         parts, xs, lws = [], [], []
         if route == 'fused':
             netG = self.trainer.netG
-            affine = self._ensemble_affine()
-            like_id, params, lo, hi = self._importance_device_like(affine)
+            kw = target.launch_kwargs(netG.device)
             seed = self._next_seed() if seed is None else int(seed)
             if chunk is None:
                 chunk = max(1, self.ENSEMBLE_HISTORY_BYTES // (8 * D + 16)) if return_samples else self.IMPORTANCE_CHUNK
@@ -898,8 +866,7 @@ class Sampler(object):
             sums = []
             for first in range(0, M, chunk):
                 k = min(chunk, M - first)
-                res = netG.importance_evidence(like_id, k, t_std=affine[0], t_mean=affine[1], lo=lo, hi=hi, seed=seed,
-                                               sample_offset=first, like_params=params, want_samples=return_samples)
+                res = netG.importance_evidence(target.like_id, k, seed=seed, sample_offset=first, want_samples=return_samples, **kw)
                 sums.append(res['sums'])
                 if return_samples:
                     xs.append(res['x'].cpu().numpy())
@@ -916,8 +883,7 @@ class Sampler(object):
                 if return_samples:
                     xs.append(x)
                     lws.append(lw)
-            affine = self._ensemble_affine()
-        const = self._importance_constant(affine)
+        const = self._importance_constant(self._ensemble_affine())
         a, s1, s2, n_live = _lib.merge_importance(parts)
         r = _lib.importance_result(a, s1, s2, n_live, M)
         out = dict(logz=r['logz_x'] + const if r['logz_x'] > -np.inf else -np.inf, logzerr=r['logzerr'], ess=r['ess'], n_samples=M,
@@ -932,7 +898,7 @@ class Sampler(object):
         return out
 
     def _mcmc_sample_device(self, mcmc_steps, step_size=0.0, num_chains=1, init_samples=None, max_start_tries=100, output_interval=None,
-                            stats_interval=None, seed=None, chunk_steps=None):
+                            stats_interval=None, seed=None, chunk_steps=None, target=None):
         """`_mcmc_sample` with loglstar = None (sampler.py:372-416: the likelihood, the prior and the Jacobian in the ratio) with every
         step of a launch inside the kernel (include/nnest_hip.h nnest_mcmc_steps, nnest_spline_mcmc_steps).  BUILD-DEFINED STREAM,
         THE REFERENCE'S MOVE: parity with the host route's torch stream is statistical.  The step is fixed (`step_size`, <= 0: the
@@ -940,63 +906,79 @@ class Sampler(object):
         chain's target is <= -1e30, up to `max_start_tries` times (sampler.py:275-284).  The run is cut into launches of `chunk_steps`
         steps (default: by device memory, ENSEMBLE_HISTORY_BYTES) and at `output_interval`; the cut does not change it.  Returns the
         reference's tuple (samples [N, S + 1, D] (x, before the transform: the start, then every step), latent_samples [N, S + 1, D],
-        derived_samples [N, S + 1, 0], loglikes [N, S + 1] (logL), scale, ncall).  Raises ValueError naming what is not taken."""
-        why = self._mcmc_device_refusal()
-        if why is not None:
-            raise ValueError('mcmc: the fused route does not take %s' % why)
+        derived_samples [N, S + 1, 0], loglikes [N, S + 1] (logL), scale, ncall).  `target`: the run's DeviceTarget where the caller
+        has resolved it (`_device_target(entry='mcmc')`); None: resolved here, ValueError naming what is not taken."""
+        if target is None:
+            target, why = self._device_target(entry='mcmc')
+            if why is not None:
+                raise ValueError('mcmc: the fused route does not take %s' % why)
         S = int(mcmc_steps)
         if step_size <= 0.0:
             step_size = 2 / self.x_dim ** 0.5
         D = self.x_dim
         netG = self.trainer.netG
-        affine = self._ensemble_affine()
-        like_id, params, lo, hi = self._ensemble_device_like(affine)
         seed = self._next_seed() if seed is None else int(seed)
-        kw = dict(t_std=affine[0], t_mean=affine[1], lo=lo, hi=hi, seed=seed, like_params=params)
+        kw = dict(target.launch_kwargs(netG.device), seed=seed)
         if init_samples is not None:
             z, _ = netG.forward(init_samples)
             z = z.contiguous()
-            start, tries = netG.mcmc_steps(like_id, z, 0, step_size, **kw), 1
+            start, tries = netG.mcmc_steps(target.like_id, z, 0, step_size, **kw), 1
         else:
             for tries in range(1, int(max_start_tries) + 1):
                 z = netG.prior_sample(int(num_chains)).contiguous()
-                start = netG.mcmc_steps(like_id, z, 0, step_size, **kw)
+                start = netG.mcmc_steps(target.like_id, z, 0, step_size, **kw)
                 if bool((start['lp'] > -1e30).all().item()):
                     break
             else:
                 raise Exception('Could not find starting value')
         N = z.shape[0]
-        if chunk_steps is None:
-            chunk_steps = max(1, self.ENSEMBLE_HISTORY_BYTES // (N * (8 * D + 8)))
-        chunk_steps = max(1, min(int(chunk_steps), S if S > 0 else 1))
-        if output_interval:
-            chunk_steps = min(chunk_steps, int(output_interval))
         samples = np.empty((N, S + 1, D), np.float32)
         latent = np.empty((N, S + 1, D), np.float32)
         loglikes = np.empty((N, S + 1))
         derived = np.zeros((N, S + 1, 0))
         samples[:, 0], latent[:, 0], loglikes[:, 0] = start['x'].cpu().numpy(), z.cpu().numpy(), start['logl'].cpu().numpy()
-        lp, logl = start['lp'], start['logl']
+
+        def launch(k, done, state):
+            res = netG.mcmc_steps(target.like_id, state[0], k, step_size, lp=state[1], logl=state[2], step0=done, **kw)
+            return ((res['z'], res['lp'], res['logl']), dict(x=res['hist_x'], z=res['hist_z'], logl=res['hist_logl']),
+                    int(res['n_accept'].sum().item()))
+
+        ncall = N * (tries + S)
+        self._run_in_launches(launch, (z, start['lp'], start['logl']), dict(x=samples, z=latent, logl=loglikes, derived=derived), S,
+                              chunk_steps, output_interval, first=1, ncall=ncall)
+        if self.chain_stats and stats_interval is not None:   # sampler.py:451-452: the transformed chains up to step `it`
+            self._log_chain_stats(samples, self._ensemble_affine(), S, stats_interval, prefix_offset=1, min_step=0, final=False)
+        return samples, latent, derived, loglikes, step_size, ncall
+
+    def _run_in_launches(self, launch, state, hist, S, chunk_steps, output_interval, first=0, save=True, ncall=0):
+        """A run of S steps cut into launches: of `chunk_steps` steps (None: what ENSEMBLE_HISTORY_BYTES of device history hold) and at
+        `output_interval`; the cut does not change the run.  launch(k, done, state) runs steps done .. done + k - 1 from `state` and
+        returns (the state the next launch starts from, the chunk's history {key: [N, k, ...] tensor or array}, its accept count).
+        hist: {'x', 'logl', 'derived', ...: [N, first + S, ...] numpy}, filled under the chunk's keys from column `first` on; with
+        `save` the chain file is rewritten from it whenever `done` reaches a multiple of output_interval.  Books total_accepted and
+        total_rejected, and `ncall` as total_calls (0 where the host protocol has counted its own)"""
+        N, D = hist['x'].shape[0], self.x_dim
+        if chunk_steps is None:
+            chunk_steps = max(1, self.ENSEMBLE_HISTORY_BYTES // (N * (8 * D + 8)))
+        chunk_steps = max(1, min(int(chunk_steps), S if S > 0 else 1))
+        if output_interval:
+            chunk_steps = min(chunk_steps, int(output_interval))
         n_acc, done = 0, 0
         while done < S:
             k = min(chunk_steps, S - done)
-            res = netG.mcmc_steps(like_id, z, k, step_size, lp=lp, logl=logl, step0=done, **kw)
-            z, lp, logl = res['z'], res['lp'], res['logl']
-            n_acc += int(res['n_accept'].sum().item())
-            samples[:, 1 + done:1 + done + k] = res['hist_x'].cpu().numpy()
-            latent[:, 1 + done:1 + done + k] = res['hist_z'].cpu().numpy()
-            loglikes[:, 1 + done:1 + done + k] = res['hist_logl'].cpu().numpy()
+            state, chunk, accepted = launch(k, done, state)
+            n_acc += accepted
+            for key, rows in chunk.items():
+                hist[key][:, first + done:first + done + k] = rows.cpu().numpy() if torch.is_tensor(rows) else rows
             done += k
-            if output_interval is not None and done % int(output_interval) == 0:
-                self._save_samples(self.transform(samples[:, :1 + done].reshape(-1, D)), loglikes[:, :1 + done].reshape(-1),
-                                   derived_samples=np.zeros((N * (1 + done), 0)))
-        if self.chain_stats and stats_interval is not None:   # sampler.py:451-452: the transformed chains up to step `it`
-            self._log_chain_stats(samples, affine, S, stats_interval, prefix_offset=1, min_step=0, final=False)
-        ncall = N * (tries + S)
+            if save and output_interval is not None and done % int(output_interval) == 0:
+                n = first + done
+                self._save_samples(self.transform(hist['x'][:, :n].reshape(-1, D)), hist['logl'][:, :n].reshape(-1),
+                                   derived_samples=hist['derived'][:, :n].reshape(N * n, hist['derived'].shape[2]))
         self.total_calls += ncall
         self.total_accepted += n_acc
         self.total_rejected += N * S - n_acc
-        return samples, latent, derived, loglikes, step_size, ncall
+        return state
 
     def _ensemble_sample(self, mcmc_steps, num_walkers, init_samples=None, init_loglikes=None, init_derived=None, loglstar=None,
                          show_progress=False, max_start_tries=100, output_interval=None, stats_interval=None, plot_trace=True,
@@ -1012,7 +994,6 @@ class Sampler(object):
         not built, NotImplementedError): one move per step by weight (include/nnest_hip.h nnest_ensemble_moves_steps).  With a DE
         step in the run the NVP's fused route is taken where its population fits the kernel that knows the move; the spline flow's
         fused kernel does not know it: rounds at route=None, ValueError at route='fused'."""
-        from . import _lib
         mv = _lib.ens_moves(moves)
         S = int(mcmc_steps)
         if init_samples is not None:
@@ -1030,61 +1011,43 @@ class Sampler(object):
         z = z.contiguous()
         lp0 = None if init_loglikes is None else torch.as_tensor(np.asarray(init_loglikes, np.float64)).to(z.device)
         seed = self._next_seed() if seed is None else int(seed)
-        affine = self._ensemble_affine()
-        dlike = self._ensemble_device_like(affine)
+        target, _ = self._device_target()
         # the fused kernel takes the flow (its family binds an `ensemble` entry: HipNVP, HipSpline), the likelihood and the population
         # (with a DE step in the run: an `ensemble_moves` entry, and the population of the kernel that knows the move)
-        fused_ok = (dlike is not None and ('ensemble_moves' if mix else 'ensemble') in getattr(netG, '_sym', ())
-                    and N <= (netG.ensemble_max_walkers(dlike[0], moves=mv) if mix else netG.ensemble_max_walkers(dlike[0])))
+        fused_ok = (target is not None and ('ensemble_moves' if mix else 'ensemble') in getattr(netG, '_sym', ())
+                    and N <= (netG.ensemble_max_walkers(target.like_id, moves=mv) if mix else netG.ensemble_max_walkers(target.like_id)))
         if route is None:   # (the spline's fused kernel is opt-in, route='fused': DESIGN.md 3.7)
             route = 'fused' if fused_ok and getattr(netG, 'ensemble_fused_by_default', False) else 'rounds'
         elif route == 'fused' and not fused_ok:
             raise ValueError('ensemble: the fused route does not take this flow, likelihood, population or move')
-        if chunk_steps is None:
-            chunk_steps = max(1, self.ENSEMBLE_HISTORY_BYTES // (N * (8 * D + 8)))
-        chunk_steps = max(1, min(int(chunk_steps), S if S > 0 else 1))
-        if output_interval:
-            chunk_steps = min(chunk_steps, int(output_interval))
         samples = np.empty((N, S, D), np.float32)
         latent = np.empty((N, S, D), np.float32)
         loglikes = np.empty((N, S))
         derived = np.zeros((N, S, nd))
-        ncall = 0 if init_loglikes is not None else N
+        ncall = (0 if init_loglikes is not None else N) + N * S
         from .ensemble_rounds import ensemble_rounds
-        state, n_acc, done = None, 0, 0
-        while done < S:
-            k = min(chunk_steps, S - done)
+        kw = dict(loglstar=loglstar, seed=seed, **mkw)
+        if target is not None:
+            kw.update(target.launch_kwargs(netG.device))
+        else:
+            host = dict(loglike=self.loglike, prior=self.prior if self._user_prior is not None else None, num_derived=nd,
+                        init_derived=init_derived)
+
+        def launch(k, done, state):
+            z, lp, rounds = state
             if route == 'fused':
-                like_id, params, lo, hi = dlike
-                res = netG.ensemble_steps(like_id, z, k, t_std=affine[0], t_mean=affine[1], lo=lo, hi=hi, lp=lp0, loglstar=loglstar,
-                                          seed=seed, step0=done, like_params=params, **mkw)
-                z, lp0 = res['z'], res['lp']
-                hz, hx, hl = res['hist_z'], res['hist_x'], res['hist_lp']
-                n_acc += int(res['n_accept'].sum().item())
-            else:
-                kw = dict(loglstar=loglstar, seed=seed, step0=done, **mkw)
-                if dlike is not None:
-                    kw.update(like_id=dlike[0], like_params=dlike[1], t_std=affine[0], t_mean=affine[1], lo=dlike[2], hi=dlike[3])
-                else:
-                    kw.update(loglike=self.loglike, prior=self.prior if self._user_prior is not None else None, num_derived=nd,
-                              init_derived=init_derived)
-                acc0 = 0 if state is None else int(state.n_accept.sum().item())
-                state, h = ensemble_rounds(netG, z, k, state=state, lp=lp0, **kw)
-                hz, hx, hl = h['hist_z'], h['hist_x'], h['hist_lp']
-                n_acc += int(state.n_accept.sum().item()) - acc0
-                derived[:, done:done + k] = h['hist_derived']
-            samples[:, done:done + k] = hx.cpu().numpy()
-            latent[:, done:done + k] = hz.cpu().numpy()
-            loglikes[:, done:done + k] = hl.cpu().numpy()
-            done += k
-            if output_interval is not None and done % int(output_interval) == 0:
-                self._save_samples(self.transform(samples[:, :done].reshape(-1, D)), loglikes[:, :done].reshape(-1),
-                                   derived_samples=derived[:, :done].reshape(-1, nd))
-        ncall += N * S
-        if route == 'fused' or dlike is not None:   # (the host protocol counts its own calls in self.loglike)
-            self.total_calls += ncall
-        self.total_accepted += n_acc
-        self.total_rejected += N * S - n_acc
+                res = netG.ensemble_steps(target.like_id, z, k, lp=lp, step0=done, **kw)
+                return ((res['z'], res['lp'], None), dict(z=res['hist_z'], x=res['hist_x'], logl=res['hist_lp']),
+                        int(res['n_accept'].sum().item()))
+            acc0 = 0 if rounds is None else int(rounds.n_accept.sum().item())
+            rounds, h = ensemble_rounds(netG, z, k, state=rounds, lp=lp, step0=done, **kw,
+                                        **(host if target is None else dict(like_id=target.like_id)))
+            return ((z, lp, rounds), dict(z=h['hist_z'], x=h['hist_x'], logl=h['hist_lp'], derived=h['hist_derived']),
+                    int(rounds.n_accept.sum().item()) - acc0)
+
+        # (the host protocol counts its own calls in self.loglike)
+        self._run_in_launches(launch, (z, lp0, None), dict(x=samples, z=latent, logl=loglikes, derived=derived), S, chunk_steps,
+                              output_interval, ncall=0 if target is None else ncall)
         self.ensemble_route = route
         return samples, latent, derived, loglikes, ncall
 
@@ -1097,7 +1060,6 @@ class Sampler(object):
         (ensemble_rounds on an IdentityFlow) otherwise: a Python likelihood, another prior, derived parameters, a larger
         population; `route` pins one, for tests.  Cut into launches like `_ensemble_sample`.  Returns (samples [N, S, D],
         loglikes [N, S] (the log target), derived [N, S, nd], ncall).  `moves`: as `_ensemble_sample` (nnest_ensemble_x_moves_steps)."""
-        from . import _lib
         from . import flow as _flow
         mv = _lib.ens_moves(moves)
         from .ensemble_rounds import IdentityFlow, ensemble_rounds
@@ -1116,51 +1078,37 @@ class Sampler(object):
         x = _flow._as_dev_f32(init_samples, dev).contiguous()
         lp0 = None if init_loglikes is None else torch.as_tensor(np.asarray(init_loglikes, np.float64)).to(dev)
         seed = self._next_seed() if seed is None else int(seed)
-        dlike = self._ensemble_device_like(affine)
-        fused_ok = dlike is not None and D <= 128 and N <= _flow.ensemble_x_max_walkers(D, dlike[0], device=dev, **mkw)
+        target, _ = self._device_target(affine)
+        fused_ok = target is not None and D <= 128 and N <= _flow.ensemble_x_max_walkers(D, target.like_id, device=dev, **mkw)
         if route is None:
             route = 'fused' if fused_ok else 'rounds'
         elif route == 'fused' and not fused_ok:
             raise ValueError('ensemble: the fused x-space route does not take this likelihood, prior or population')
-        if chunk_steps is None:
-            chunk_steps = max(1, self.ENSEMBLE_HISTORY_BYTES // (N * (8 * D + 8)))
-        chunk_steps = max(1, min(int(chunk_steps), S if S > 0 else 1))
-        if output_interval:
-            chunk_steps = min(chunk_steps, int(output_interval))
         samples = np.empty((N, S, D), np.float32)
         loglikes = np.empty((N, S))
         derived = np.zeros((N, S, nd))
-        ncall = 0 if init_loglikes is not None else N
+        ncall = (0 if init_loglikes is not None else N) + N * S
         ident = IdentityFlow(dev)
-        state, n_acc, done = None, 0, 0
-        while done < S:
-            k = min(chunk_steps, S - done)
+        kw = dict(loglstar=loglstar, seed=seed, **mkw)
+        if target is not None:
+            kw.update(target.launch_kwargs(dev))
+        else:
+            host = dict(loglike=self.loglike, prior=self.prior if self._user_prior is not None else None, num_derived=nd)
+
+        def launch(k, done, state):
+            x, lp, rounds = state
             if route == 'fused':
-                like_id, params, lo, hi = dlike
-                res = _flow.ensemble_x_steps(like_id, x, k, t_std=affine[0], t_mean=affine[1], lo=lo, hi=hi, lp=lp0, loglstar=loglstar,
-                                             seed=seed, step0=done, like_params=params, device=dev, **mkw)
-                x, lp0 = res['x'], res['lp']
-                hx, hl = res['hist_x'], res['hist_lp']
-                n_acc += int(res['n_accept'].sum().item())
-            else:
-                kw = dict(loglstar=loglstar, seed=seed, step0=done, **mkw)
-                if dlike is not None:
-                    kw.update(like_id=dlike[0], like_params=dlike[1], t_std=affine[0], t_mean=affine[1], lo=dlike[2], hi=dlike[3])
-                else:
-                    kw.update(loglike=self.loglike, prior=self.prior if self._user_prior is not None else None, num_derived=nd)
-                acc0 = 0 if state is None else int(state.n_accept.sum().item())
-                state, h = ensemble_rounds(ident, x, k, state=state, lp=lp0, **kw)
-                hx, hl = h['hist_z'], h['hist_lp']
-                n_acc += int(state.n_accept.sum().item()) - acc0
-                derived[:, done:done + k] = h['hist_derived']
-            samples[:, done:done + k] = hx.cpu().numpy()
-            loglikes[:, done:done + k] = hl.cpu().numpy()
-            done += k
-        ncall += N * S
-        if route == 'fused' or dlike is not None:   # (the host protocol counts its own calls in self.loglike)
-            self.total_calls += ncall
-        self.total_accepted += n_acc
-        self.total_rejected += N * S - n_acc
+                res = _flow.ensemble_x_steps(target.like_id, x, k, lp=lp, step0=done, device=dev, **kw)
+                return (res['x'], res['lp'], None), dict(x=res['hist_x'], logl=res['hist_lp']), int(res['n_accept'].sum().item())
+            acc0 = 0 if rounds is None else int(rounds.n_accept.sum().item())
+            rounds, h = ensemble_rounds(ident, x, k, state=rounds, lp=lp, step0=done, **kw,
+                                        **(host if target is None else dict(like_id=target.like_id)))
+            return ((x, lp, rounds), dict(x=h['hist_z'], logl=h['hist_lp'], derived=h['hist_derived']),
+                    int(rounds.n_accept.sum().item()) - acc0)
+
+        # (bootstrap writes the whole run itself; the host protocol counts its own calls in self.loglike)
+        self._run_in_launches(launch, (x, lp0, None), dict(x=samples, logl=loglikes, derived=derived), S, chunk_steps, output_interval,
+                              save=False, ncall=0 if target is None else ncall)
         self.ensemble_route = route
         return samples, loglikes, derived, ncall
 

@@ -6,15 +6,17 @@ Metropolis steps in the flow's latent space on the tempered target.  It needs no
 and carries separated modes from the prior instead of having to find them.
 
 Routes.  'fused': the reweighting, the resampling and every step of a stage's moves run on the device (include/nnest_hip.h
-nnest_smc_reweight, nnest_smc_resample, nnest_mcmc_tempered_steps, nnest_spline_mcmc_tempered_steps), where `_mcmc_sample_device` would
-take the sampler and the flow's family has a tempered kernel.  'host': everything else -- a Python likelihood, the other flows, another
-prior -- a plain loop with the flow passes on the GPU and the user's callables on the host, reweighted and resampled in numpy by the
-same rule (`reweight_host`, `resample_host`); derived parameters are not carried by either route.
+nnest_smc_reweight, nnest_smc_resample, nnest_mcmc_tempered_steps, nnest_spline_mcmc_tempered_steps), where
+`Sampler._device_target(entry='mcmc_tempered')` gives a target: `_mcmc_sample_device`'s conditions and a family with a tempered
+kernel.  'host': everything else -- a Python likelihood, the other flows, another prior -- a plain loop with the flow passes on the
+GPU and the user's callables on the host, reweighted and resampled in numpy by the same rule (`reweight_host`, `resample_host`);
+derived parameters are not carried by either route.
 
 CONVENTION of `logz`: log of the integral of L(theta) pi(theta) d theta with the NORMALISED prior the particles were drawn from
 (Z at beta = 0 is 1), as NestedSampler's `logz`.  For a UniformPrior on [lo, hi] this differs from `Sampler.importance_evidence`'s
 convention -- the prior as its callable returns it, the unnormalised indicator -- by sum log(hi - lo):
 logz_smc = logz_importance - sum log(hi - lo)."""
+import functools
 import logging
 import time
 
@@ -85,17 +87,6 @@ class SMCSampler(Sampler):
                                          param_names=param_names, chain_stats=chain_stats)
         self.sampler = 'smc'
 
-    def _smc_device_refusal(self):
-        """why the fused route does not take this sampler (a string), or None where it does: `_mcmc_device_refusal`'s conditions, and
-        a flow whose family binds a tempered entry (HipNVP, HipSpline)"""
-        why = self._mcmc_device_refusal()
-        if why is not None:
-            return why
-        netG = self.trainer.netG
-        if 'mcmc_tempered' not in getattr(netG, '_sym', ()):
-            return 'the flow %s (no fused tempered random-walk Metropolis kernel)' % type(netG).__name__
-        return None
-
     def run(self, num_particles=1000, mcmc_steps=25, ess_fraction=0.5, step_size=0.0, jitter=0.01, seed=None, route=None, max_stages=1000):
         """Anneal `num_particles` draws of the prior to the posterior (the module docstring has the algorithm and the convention of
         `logz`).  mcmc_steps: Metropolis steps per particle and stage, at the fixed step `step_size` (<= 0: 2 / sqrt(x_dim), as
@@ -119,15 +110,18 @@ class SMCSampler(Sampler):
         if not 0.0 < float(ess_fraction) < 1.0:
             raise ValueError('SMCSampler.run: ess_fraction=%r (inside (0, 1))' % (ess_fraction,))
         self._install_transform(np.zeros(D), np.ones(D))   # (theta itself, until the first stage installs its own)
-        why = None if route == 'host' else self._smc_device_refusal()
+        # (likelihood and box do not depend on T: resolved here, once; every stage takes a copy under its own T)
+        target, why = (None, None) if route == 'host' else self._device_target(entry='mcmc_tempered')
         if route == 'fused' and why is not None:
             raise ValueError('SMCSampler.run: the fused route does not take %s' % why)
-        route = 'fused' if (route != 'host' and why is None) else 'host'
+        route = 'host' if target is None else 'fused'
         if step_size <= 0.0:
             step_size = 2 / D ** 0.5
         seed = self._next_seed() if seed is None else int(seed)
-        stage_fn = self._smc_stage_fused if route == 'fused' else self._smc_stage_host
-        state = self._smc_start_fused(N) if route == 'fused' else self._smc_start_host(N)
+        if route == 'fused':
+            state, stage_fn = self._smc_start_fused(N, target), functools.partial(self._smc_stage_fused, target=target)
+        else:
+            state, stage_fn = self._smc_start_host(N), self._smc_stage_host
         beta, logz = 0.0, 0.0
         self.betas, self.ess, self.acceptance, self.logz_steps, self.stage_times = [], [], [], [], []
         stage = 0
@@ -173,25 +167,23 @@ class SMCSampler(Sampler):
         return normalised, mean, std
 
     # ---- the fused route: theta [N, D] float32, logL [N] float64 and z on the device ------------------------------------------------
-    def _smc_start_fused(self, N):
+    def _smc_start_fused(self, N, target):
         import torch
         from . import flow
         if N > flow.SMC_MAX_PARTICLES:
             raise ValueError('SMCSampler.run: num_particles=%d: the fused route takes up to %d' % (N, flow.SMC_MAX_PARTICLES))
         netG = self.trainer.netG
-        self._smc_like = self._ensemble_device_like(self._ensemble_affine())   # (like_id, params, lo, hi): none depends on T
         theta = torch.as_tensor(np.asarray(self.sample_prior(N), np.float32)).to(netG.device).contiguous()
-        logl = flow.loglike(self._smc_like[0], theta, 1.0, device=netG.device, like_params=self._smc_like[1])
+        logl = flow.loglike(target.like_id, theta, 1.0, device=netG.device, like_params=target.like_params)
         self.total_calls += N
         return theta, logl, None
 
-    def _smc_stage_fused(self, state, beta, ess_fraction, S, step_size, jitter, seed, stage):
+    def _smc_stage_fused(self, state, beta, ess_fraction, S, step_size, jitter, seed, stage, target):
         import torch
         from . import flow
         theta, logl, _ = state
         netG = self.trainer.netG
         N = theta.shape[0]
-        like_id, params, lo, hi = self._smc_like
         t0 = time.perf_counter()
         out, m = flow.smc_reweight(logl, beta, ess_fraction)
         _, theta, logl = flow.smc_resample(m, theta, logl, seed, stage)
@@ -201,10 +193,10 @@ class SMCSampler(Sampler):
         torch.cuda.synchronize(netG.device)
         t2 = time.perf_counter()
         z, _ = netG.forward(normalised.astype(np.float32))
-        res = netG.mcmc_steps(like_id, z.contiguous(), S, step_size, t_std=std, t_mean=mean, lo=lo, hi=hi, seed=stage_seed(seed, stage),
-                              like_params=params, history=False, beta=beta_new)
-        f32 = dict(dtype=torch.float32, device=netG.device)
-        theta = res['x'] * torch.as_tensor(std.astype(np.float32), **f32) + torch.as_tensor(mean.astype(np.float32), **f32)   # T(x), float32
+        target = target.with_transform(std, mean)   # (this stage's T)
+        res = netG.mcmc_steps(target.like_id, z.contiguous(), S, step_size, seed=stage_seed(seed, stage), history=False, beta=beta_new,
+                              **target.launch_kwargs(netG.device))
+        theta = target.transform(res['x'])
         n_acc = int(res['n_accept'].sum().item())
         t3 = time.perf_counter()
         self.total_calls += N * (1 + S)

@@ -253,20 +253,19 @@ class _UnitBox(object):
         return True
 
 
-def _bare_sampler(D, net, dlike=(3, (0.5,), None, None), cls=None):
+def _bare_sampler(D, net, agrees=True, prior=None, cls=None):
     from nnest_amd.mcmc import MCMCSampler
 
     class _Like(object):
-        hip_like_id = 3
+        hip_like_id, hip_like_params = 3, (0.5,)
 
     cls = cls or MCMCSampler
     s = cls.__new__(cls)
     s.x_dim, s.num_derived, s.num_slow, s.trainer = D, 0, 0, _StubTrainer(net)
     s.total_calls = 0
-    s._user_loglike, s._user_prior, s._user_transform, s._transform_prior, s._linear_scale = _Like(), None, None, True, 1.0
+    s._user_loglike, s._user_prior, s._user_transform, s._transform_prior, s._linear_scale = _Like(), prior, None, True, 1.0
     s.transform = lambda x: x
-    s._ensemble_device_like = lambda affine: dlike
-    s._device_likelihood = lambda affine: None if dlike is None else dlike[:2]
+    s._probe_agrees = lambda like_id, params, **kw: agrees   # (the one step of _device_target that needs a device)
     s.single_or_primary_process = True
     s.logger = logging.getLogger('test_importance_check')
     # the host route's callables: the likelihood is 0, the prior kills what the stub's weights call dead
@@ -339,19 +338,20 @@ def test_front_end_names_what_the_fused_route_does_not_take():
         with pytest.raises(ValueError, match='the fused route does not take the flow _StubFlow: importance: ' + words.split(':')[1].strip()[:12]):
             s.importance_evidence(M, route='fused')
         assert s.importance_evidence(M)['route'] == 'host' and net.calls == [] and net.asked == [3, 3]
-    s = _bare_sampler(D, _StubFlow(D), dlike=None)
+    s = _bare_sampler(D, _StubFlow(D), agrees=False)
     with pytest.raises(ValueError, match='prior'):
         s.importance_evidence(M, route='fused')
     assert s.importance_evidence(M)['route'] == 'host'
 
 
 def test_front_end_states_log_z_in_either_convention():
+    from nnest_amd.priors import UniformPrior
     D, M = 3, 500
     whole = ic.result(*ic.sums(stub_logw(np.arange(M))), M)
     # an installed affine transform: Z over theta = T(x), so sum log|t_std| is added (a UniformPrior stays the indicator it is)
     for route in ('fused', 'host'):
         net = _StubFlow(D)
-        s = _bare_sampler(D, net, dlike=(3, (0.5,), np.full(D, -5.0, np.float32), np.full(D, 5.0, np.float32)))
+        s = _bare_sampler(D, net, prior=UniformPrior(D, -5.0, 5.0))
         s._install_transform(np.array([1.0, 2.0, 3.0]), np.array([0.5, -2.0, 4.0]))
         out = s.importance_evidence(M, route=route, seed=1)
         assert out['route'] == route
@@ -371,18 +371,18 @@ def test_front_end_states_log_z_in_either_convention():
         if route == 'fused':
             assert net.calls[0][5] == (-5.0, 5.0)
     # the unit box on x under a transform that is not linear: the host route, and still the normalised prior
-    s = _bare_sampler(D, _StubFlow(D), dlike=None)
+    s = _bare_sampler(D, _StubFlow(D), agrees=False)
     s._user_prior, s._transform_prior, s._linear_scale, s._user_transform = _UnitBox(), False, None, (lambda x: x ** 3)
     out = s.importance_evidence(M)
     assert out['route'] == 'host' and out['logz'] == pytest.approx(whole['logz_x'] - D * np.log(2.0), rel=1e-12)
     # another prior evaluated on x (transform_prior=False) under an affine transform: Z over x is the evidence, nothing is added
-    s = _bare_sampler(D, _StubFlow(D), dlike=None)
+    s = _bare_sampler(D, _StubFlow(D), agrees=False)
     s._install_transform(np.array([1.0, 2.0, 3.0]), np.array([0.5, -2.0, 4.0]))
     s._user_prior, s._transform_prior = object(), False
     out = s.importance_evidence(M)
     assert out['route'] == 'host' and out['logz'] == pytest.approx(whole['logz_x'], rel=1e-12)
     # a transform that is not affine and no prior: Z stays over x
-    s = _bare_sampler(D, _StubFlow(D), dlike=None)
+    s = _bare_sampler(D, _StubFlow(D), agrees=False)
     s._linear_scale, s._user_transform = None, (lambda x: x ** 3)
     out = s.importance_evidence(M)
     assert out['route'] == 'host' and out['logz'] == pytest.approx(whole['logz_x'], rel=1e-12)

@@ -219,11 +219,11 @@ class _StubTrainer(object):
         self.netG = net
 
 
-def _bare_sampler(D, net, dlike=(3, (0.5,), None, None)):
+def _bare_sampler(D, net, agrees=True):
     from nnest_amd.mcmc import MCMCSampler
 
     class _Like(object):
-        hip_like_id = 3
+        hip_like_id, hip_like_params = 3, (0.5,)
 
     s = MCMCSampler.__new__(MCMCSampler)
     s.x_dim, s.num_derived, s.num_slow, s.trainer = D, 0, 0, _StubTrainer(net)
@@ -231,7 +231,8 @@ def _bare_sampler(D, net, dlike=(3, (0.5,), None, None)):
     s.chain_stats, s._user_loglike = False, _Like()
     s.transform = lambda x: x
     s._ensemble_affine = lambda: (np.ones(D), np.zeros(D))
-    s._ensemble_device_like = lambda affine: dlike
+    s._user_prior, s._transform_prior = None, True
+    s._probe_agrees = lambda like_id, params, **kw: agrees   # (the one step of _device_target that needs a device)
     saved = []
     s._save_samples = lambda samples, loglikes, derived_samples=None: saved.append((samples.shape, loglikes.shape, derived_samples.shape))
     return s, saved
@@ -279,6 +280,6 @@ def test_device_run_names_what_it_does_not_take():
     s, _ = _bare_sampler(D, net)
     with pytest.raises(ValueError, match='_StubFlow'):
         s._mcmc_sample_device(2, init_samples=np.zeros((4, D)))
-    s, _ = _bare_sampler(D, _StubFlow(D), dlike=None)
+    s, _ = _bare_sampler(D, _StubFlow(D), agrees=False)
     with pytest.raises(ValueError, match='prior'):
         s._mcmc_sample_device(2, init_samples=np.zeros((4, D)))

@@ -316,7 +316,7 @@ class _StubTrainer(object):
         self.trained.append((np.asarray(samples).copy(), jitter))
 
 
-def _bare_sampler(D, like, prior, net, dlike=(3, (0.5,), None, None)):
+def _bare_sampler(D, like, prior, net, agrees=True):
     from nnest_amd.smc import SMCSampler
     s = SMCSampler.__new__(SMCSampler)
     s.x_dim, s.num_derived, s.num_slow, s.trainer = D, 0, 0, _StubTrainer(net)
@@ -325,7 +325,7 @@ def _bare_sampler(D, like, prior, net, dlike=(3, (0.5,), None, None)):
     s.transform = lambda x: x
     s.loglike, s.prior = s._checked_loglike, s._checked_prior
     s.sample_prior = getattr(prior, 'sample', None)
-    s._ensemble_device_like = lambda affine: dlike
+    s._probe_agrees = lambda like_id, params, **kw: agrees   # (the one step of _device_target that needs a device)
     s.single_or_primary_process = True
     s.logger = logging.getLogger('test_smc_check')
     s._seed_gen = None
@@ -344,7 +344,7 @@ def test_exported_and_constructed_as_mcmc_sampler():
         ('num_particles', 1000), ('mcmc_steps', 25), ('ess_fraction', 0.5), ('step_size', 0.0), ('jitter', 0.01), ('seed', None), ('route', None),
         ('max_stages', 1000)]
     assert "self.sampler = 'smc'" in inspect.getsource(SMCSampler.__init__)
-    for name in ('_mcmc_sample', '_mcmc_sample_device', '_install_transform', '_mcmc_device_refusal'):   # the base class's, untouched
+    for name in ('_mcmc_sample', '_mcmc_sample_device', '_install_transform', '_device_target'):   # the base class's, untouched
         assert getattr(SMCSampler, name) is getattr(Sampler, name)
 
 
@@ -404,9 +404,9 @@ def test_front_end_chooses_and_names_its_route():
     prior = UniformPrior(2, -6.0, 6.0)
 
     def fused_stub(s, record):
-        s._smc_start_fused = lambda N: ('theta', 'logl', None)
+        s._smc_start_fused = lambda N, target: ('theta', 'logl', None)
 
-        def stage(state, beta, ess_fraction, S, step_size, jitter, seed, stage):
+        def stage(state, beta, ess_fraction, S, step_size, jitter, seed, stage, target):
             record.append((beta, ess_fraction, S, step_size, jitter, seed, stage))
             return min(1.0, beta + 0.4), -1.0, 50.0, 0.25, (np.zeros((4, 2)), np.zeros(4), np.zeros((4, 2))), dict(reweight=0, train=0, move=0)
         s._smc_stage_fused = stage
@@ -439,7 +439,7 @@ def test_front_end_chooses_and_names_its_route():
         s.run(num_particles=50, route='fused')
     s.run(num_particles=50, mcmc_steps=2, seed=3)
     assert s.smc_route == 'host' and s.betas[-1] == 1.0
-    s = _bare_sampler(2, _Like(), prior, _IdentityFlow(2), dlike=None)
+    s = _bare_sampler(2, _Like(), prior, _IdentityFlow(2), agrees=False)
     with pytest.raises(ValueError, match='prior'):
         s.run(num_particles=50, route='fused')
     # route='host' is honoured where the fused route would apply

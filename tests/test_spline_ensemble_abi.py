@@ -133,14 +133,19 @@ class _StubTrainer(object):
         self.netG = net
 
 
-def _bare_sampler(D, net, monkeypatch, dlike=(3, (0.5,), None, None)):
+def _bare_sampler(D, net, monkeypatch, agrees=True):
     from nnest_amd import ensemble_rounds
     from nnest_amd.ensemble import EnsembleSampler
+
+    class _Like(object):
+        hip_like_id, hip_like_params = 3, (0.5,)
+
     s = EnsembleSampler.__new__(EnsembleSampler)
     s.x_dim, s.num_derived, s.trainer = D, 0, _StubTrainer(net)
     s.total_calls = s.total_accepted = s.total_rejected = 0
     s._ensemble_affine = lambda: (np.ones(D), np.zeros(D))
-    s._ensemble_device_like = lambda affine: dlike
+    s._user_loglike, s._user_prior, s._transform_prior = _Like(), None, True
+    s._probe_agrees = lambda like_id, params, **kw: agrees   # (the one step of _device_target that needs a device)
     rounds = []
 
     def fake_rounds(flow, z, steps, state=None, **kw):
@@ -169,7 +174,7 @@ def test_the_spline_takes_the_fused_route_only_when_asked(monkeypatch):
     with pytest.raises(ValueError, match='fused route'):
         s._ensemble_sample(S, N, seed=1, route='fused')
     net.cap = 1 << 12
-    s2, _ = _bare_sampler(D, net, monkeypatch, dlike=None)
+    s2, _ = _bare_sampler(D, net, monkeypatch, agrees=False)
     s2.loglike, s2._user_prior = None, None
     with pytest.raises(ValueError, match='fused route'):
         s2._ensemble_sample(S, N, seed=1, route='fused')
