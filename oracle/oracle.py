@@ -457,11 +457,12 @@ class _SliceUniforms(object):
 
 
 def slice_sample(flow, like, like_scale, z0, logl0, loglstar, width, dz, seed, walker_offset=0, max_stepout=8, max_shrink=32,
-                 margins=None):
+                 margins=None, like_params=None):
     """[BUILD-DEFINED, parity unpinned: the reference proposes random-walk Metropolis moves only, nnest/sampler.py:310-316]
     CPU restatement of the slice proposal kernel (nnest_amd/csrc/nnest_solo.hip slice_kernel_solo; include/nnest_hip.h
     nnest_slice_steps): univariate slice sampling (stepping out + shrinkage) along the recorded directions dz [S, C, D] of the target
-    |det dx/dz| on {x(z) in the unit box, logL > loglstar}; `flow` is an oracle flow object (NVP).  Returns the per-step x history
+    |det dx/dz| on {x(z) in the unit box, logL > loglstar}; `flow` is an oracle flow object (NVP); like_params: the likelihood's
+    parameters as `loglike` takes them (None: a likelihood without any).  Returns the per-step x history
     [C, S + 1, D], the final z, logl, the counters, and per update the expansions of the bracket to the left / right
     n_left, n_right [C, S] and `split` [C, S]: stepping out goes to the slice's ends, left then right, if that takes at most
     B = 2 max_stepout expansions; otherwise it restarts with B split at random (slice_stepout_split).  margins [S, C] (optional): the smallest distance of any evaluated candidate of
@@ -493,7 +494,7 @@ def slice_sample(flow, like, like_scale, z0, logl0, loglstar, width, dz, seed, w
                 xp, ldp = xp[0], np.float32(ldp[0])
                 inb = bool(prior_inbox(xp[None])[0] == 0)
                 pre = inb and bool(ldp > logy)
-                lp = float(loglike(like, xp[None], like_scale)[0])
+                lp = float(loglike(like, xp[None], like_scale, like_params)[0])
                 n_eval[c] += 1
                 n_call[c] += 1 if pre else 0
                 mg[0] = min(mg[0], float(np.min(np.abs(np.abs(xp.astype(np.float64)) - 1.0))), abs(float(ldp) - float(logy)),
