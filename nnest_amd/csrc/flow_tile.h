@@ -28,6 +28,7 @@ namespace nnest {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 enum { FLOW_KIND_NVP = 0, FLOW_KIND_MAF = 1 };
+constexpr int SOLO_IMAGE_FLOATS = 3 * 80 * 64;   // [block][SOLO4_NF / 4][lane][4] (solo_tile.h)
 
 struct FlowShape {
     int D, H, B, L;
@@ -52,6 +53,12 @@ struct FlowShape {
     __host__ __device__ int nets_params() const { return B * 2 * net_params; }
     __host__ __device__ int num_params() const { return B * 2 * net_params + (scale_mode == 2 ? B : 0); }
     __host__ __device__ int image_total() const { return image_floats + (scale_mode == 2 ? B : 0); }
+    // The solo lane image (solo_tile.h: solo_image_kernel) lives in the SAME allocation as the fragment image, behind it at a 16-byte
+    // boundary, and launch_repack builds both: whoever rebuilds the fragment image rebuilds the lane image, so it is never the older.
+    // Only the shape of the one-walker-per-wave kernels has one (hidden 16, 3 blocks, 1 layer, x_dim <= 128).
+    __host__ __device__ bool has_solo_image() const { return kind == FLOW_KIND_NVP && H == 16 && B == 3 && L == 1 && NT >= 1 && NT <= 4; }
+    __host__ __device__ int solo_image_offset() const { return (image_total() + 3) & ~3; }
+    __host__ __device__ int image_alloc_floats() const { return has_solo_image() ? solo_image_offset() + SOLO_IMAGE_FLOATS : image_total(); }
 };
 
 __host__ __device__ inline int frag_off_L1() { return 0; }

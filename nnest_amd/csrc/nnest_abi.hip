@@ -125,18 +125,20 @@ int nnest_nvp_create_scaled(int D, int H, int B, int L, int scale_mode, nnest_nv
     if (e == hipSuccess) e = hipMalloc((void **)&h->adam_m, nb);
     if (e == hipSuccess) e = hipMalloc((void **)&h->adam_v, nb);
     if (e == hipSuccess) e = hipMalloc((void **)&h->best_w, nb);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->img, (size_t)s.image_total() * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&h->img, (size_t)s.image_alloc_floats() * sizeof(float));   // (+ the solo lane image behind it)
     if (e == hipSuccess) e = hipMalloc((void **)&h->adam_step, sizeof(int));
     if (e == hipSuccess) e = hipMalloc((void **)&h->train_ws, h->train_ws_floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&h->fwd_pos, nb);
     if (e == hipSuccess) e = hipMalloc((void **)&h->bwd_pos, nb);
     if (e == hipSuccess) e = launch_build_pos(h->fwd_pos, h->bwd_pos, s, 0);
+    if (e == hipSuccess) e = solo_prepare_device(h->device, 0);   // the step rule's table of this device, once per process
     if (e == hipSuccess) e = hipStreamSynchronize(0);
     if (e == hipSuccess) e = hipMemset(h->w, 0, nb);
     if (e == hipSuccess) e = hipMemset(h->adam_m, 0, nb);
     if (e == hipSuccess) e = hipMemset(h->adam_v, 0, nb);
     if (e == hipSuccess) e = hipMemset(h->adam_step, 0, sizeof(int));
-    if (e == hipSuccess) e = hipMemset(h->img, 0, (size_t)s.image_total() * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(h->img, 0, (size_t)s.image_alloc_floats() * sizeof(float));
+    // (zero weights: both images, all zeros, are those of the weights from the first moment on)
     if (e != hipSuccess) {
         nnest_nvp_destroy(h);
         return fail(NNEST_E_HIP, "device allocation failed: %s", hipGetErrorString(e));
@@ -389,7 +391,7 @@ int nnest_slice_steps(nnest_nvp_t *h, const nnest_like_t *like, float *z_dev, fl
         return fail(NNEST_E_UNSUPPORTED, "slice proposal: hidden 16, 3 blocks, 1 layer, scale '' (the one-walker-per-wave layout), x_dim <= 128");
     const SliceArgs a = {z_dev, x_dev, logl_dev, loglstar, width, steps, C, max_stepout, max_shrink, lk, seed, walker_offset, noise_dz_dev,
                          hist_x_dev, nullptr, n_call_dev, n_move_dev, n_eval_dev};
-    hipError_t e = launch_slice_solo(h->s, h->w, a, (hipStream_t)stream);
+    hipError_t e = launch_slice_solo(h->s, h->img + h->s.solo_image_offset(), a, (hipStream_t)stream);
     if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_slice_solo: %s", hipGetErrorString(e));
     return NNEST_OK;
 }

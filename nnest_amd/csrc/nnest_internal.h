@@ -28,6 +28,10 @@ bool quad_form_eligible(const MhArgs &a, int num_cu);        // nnest_quad.hip
 hipError_t launch_mh_quad(const MhArgs &a, int num_cu, hipStream_t st);  // nnest_quad.hip
 bool solo_form_eligible(const MhArgs &a, int num_cu);        // nnest_solo.hip
 hipError_t launch_mh_solo(const MhArgs &a, int num_cu, hipStream_t st);  // nnest_solo.hip
+// nnest_solo.hip: the solo lane image of a handle's weights (solo_tile.h; launch_repack calls it: s.has_solo_image()), and the step
+// rule's exp(1 / (1 + k)) table of a device, filled on it once per process (handle creation calls it)
+hipError_t launch_solo_image(const float *packed, float *limg, const FlowShape &s, hipStream_t st);
+hipError_t solo_prepare_device(int device, hipStream_t st);
 int mh_form_for(const FlowShape &s, int C, int flags, int num_cu);
 bool maf_shape_supported(const FlowShape &s);   // maf_kernels.h (nnest_kernels.hip)
 hipError_t launch_maf_repack(const float *packed, float *imgf, float *imgb, const FlowShape &s, hipStream_t st);
@@ -85,7 +89,7 @@ hipError_t launch_maf_loss_grad(const FlowShape &s, const float *imgf, const flo
 hipError_t launch_training_jitter(const double *samples, int N, int D, double *out, hipStream_t st);
 // slice proposal in latent space (nnest_solo.hip; build-defined: the reference has none)
 bool slice_form_eligible(const FlowShape &s);
-hipError_t launch_slice_solo(const FlowShape &s, const float *packed, const SliceArgs &a, hipStream_t st);
+hipError_t launch_slice_solo(const FlowShape &s, const float *limg, const SliceArgs &a, hipStream_t st);   // limg: the handle's solo lane image
 hipError_t launch_slice_fill_noise(float *dz, int steps, int C, int D, uint64_t seed, uint64_t walker_offset, hipStream_t st);
 // ensemble sampler, emcee's stretch move in latent space (nnest_ensemble.hip)
 size_t ensemble_work_words(int C, int S);

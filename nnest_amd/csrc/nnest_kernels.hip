@@ -756,7 +756,11 @@ hipError_t launch_repack(const float *packed, float *img, const FlowShape &s, hi
     int block = 256, grid = (s.image_floats + block - 1) / block;
     if (grid > 1024) grid = 1024;
     hipLaunchKernelGGL(repack_fragments_kernel, dim3(grid), dim3(block), 0, st, packed, img, s);
-    return hipGetLastError();
+    hipError_t e = hipGetLastError();
+    // the one-walker-per-wave kernels' lane image, behind the fragments in the same allocation (flow_tile.h): one rule for both --
+    // every route that rebuilds the fragment image from changed weights comes through here
+    if (e == hipSuccess && s.has_solo_image()) e = launch_solo_image(packed, img + s.solo_image_offset(), s, st);
+    return e;
 }
 
 static hipError_t launch_maf_pass(const PassArgs &a, int num_cu, hipStream_t st);   // maf_kernels.h

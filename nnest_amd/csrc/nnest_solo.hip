@@ -29,6 +29,7 @@
 // Summation order differs from the other forms (K split in two halves, left to right), so results agree with them (and with a
 // CPU restatement) to rounding, not bitwise; decisions on the same noise are the same except at rounding-borderline ratios.
 #include <string.h>
+#include <mutex>
 #include "mh_common.h"
 #include "nnest_internal.h"
 #include "solo_loglike.h"
@@ -36,7 +37,60 @@
 
 namespace nnest {
 
+// NNEST_STAMP (tools/build_stamp.sh, tools/stamp_prologue.py): what a launch spends OUTSIDE the step loop -- stamps around the phases of
+// the prologue and the epilogue of tile 0's first net wave and its noise wave.  The per-step stamps (tools/stamp_run.py) slow the loop
+// and are compiled only with NNEST_STAMP_STEPS beside it.
+#ifdef NNEST_STAMP
+#define PSTAMP(v) do { __builtin_amdgcn_sched_barrier(0); v = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define PSTAMP_DRAINED(v) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0x0070); v = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); } while (0)
+#ifndef NNEST_STAMP_STEPS
+#undef STAMP
+#define STAMP(v) do { } while (0)
+#endif
+#else
+#define PSTAMP(v) do { } while (0)
+#define PSTAMP_DRAINED(v) do { } while (0)
+#endif
+
 static constexpr int SOLO_ETAB = 1024;   // steps + 2 <= SOLO_ETAB: exp(1 / (1 + k)) from a table
+// The table is a constant of the kernel: filled once per process and device -- ON the device, with the expression the relay wave
+// evaluates where the table does not reach (a host exp need not give the same bits) -- and copied into LDS by every workgroup.
+__device__ double solo_etab_dev[SOLO_ETAB];
+__global__ void solo_etab_kernel() {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < SOLO_ETAB) solo_etab_dev[k] = exp(1.0 / (double)(1 + k));
+}
+hipError_t solo_prepare_device(int device, hipStream_t st) {
+    static std::mutex mu;
+    static bool done[64];
+    std::lock_guard<std::mutex> g(mu);
+    if (device < 0 || device >= 64) return hipErrorInvalidDevice;
+    if (done[device]) return hipSuccess;
+    hipLaunchKernelGGL(solo_etab_kernel, dim3(SOLO_ETAB / 256), dim3(256), 0, st);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);   // (another stream may launch the first kernel that reads it)
+    done[device] = e == hipSuccess;
+    return e;
+}
+
+// the lane image of a handle's weights (solo_tile.h): wave b gathers block b's lane shares, as the kernels did at every launch
+template <int U>
+__global__ void __launch_bounds__(192) solo_image_kernel(const float *__restrict__ packed, float *__restrict__ limg, int D, int net_params) {
+    const int lane = threadIdx.x & 63, b = threadIdx.x >> 6;
+    SoloNet<U> nb;
+    solo_gather<U>(nb, packed + (size_t)(b * 2 + (lane >= 32 ? 1 : 0)) * net_params, D, (b + 1) & 1, b & 1, lane);
+    solo4_store<U>(limg, b, nb, lane);
+}
+hipError_t launch_solo_image(const float *packed, float *limg, const FlowShape &s, hipStream_t st) {
+    if (!s.has_solo_image()) return hipErrorInvalidConfiguration;
+    switch (s.NT) {
+        case 1: hipLaunchKernelGGL(solo_image_kernel<1>, dim3(1), dim3(192), 0, st, packed, limg, s.D, s.net_params); break;
+        case 2: hipLaunchKernelGGL(solo_image_kernel<2>, dim3(1), dim3(192), 0, st, packed, limg, s.D, s.net_params); break;
+        case 3: hipLaunchKernelGGL(solo_image_kernel<3>, dim3(1), dim3(192), 0, st, packed, limg, s.D, s.net_params); break;
+        case 4: hipLaunchKernelGGL(solo_image_kernel<4>, dim3(1), dim3(192), 0, st, packed, limg, s.D, s.net_params); break;
+    }
+    return hipGetLastError();
+}
 
 // WPG = walkers (= net waves) per workgroup: 4 (one per SIMD: populations up to 4 x CUs), 8 or 12 (two / three per SIMD; round 4).
 // Beyond one wave per SIMD the register file no longer holds a lane's 132 weights beside the state (9 waves -> 168 registers, 13
@@ -47,7 +101,7 @@ template <int U, int WPG> constexpr int solo_reg_blocks() { return !solo_lds_wei
 enum { MH_SOLO_LAG_INTERNAL = 8 };   // the relay's schedule under lag 0 (no lagged step exists then: only its bookkeeping uses it)
 template <int U, bool DBG, int LK, int WPG>
 __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float wlds[];  // the packed weights
+    extern __shared__ __attribute__((aligned(16))) float wlds[];  // the LDS-weight forms' copy of the lane image (the register form: none)
     __shared__ __attribute__((aligned(16))) float nbuf[2][WPG][16][2 * U];
     __shared__ float ubuf[2][WPG];
     __shared__ __attribute__((aligned(16))) uint32_t rawbuf[4 * WPG * 8 * U];   // the noise wave's raw draws of a step, stream-major
@@ -57,6 +111,7 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
     __shared__ float fs_cand[2];    // ... and the two values it can take: the batch votes up / down
     __shared__ int vote_sel;        // which of the two it was
     __shared__ double etab[SOLO_ETAB];
+    __shared__ __attribute__((aligned(16))) float x0buf[WPG][16][2 * U];   // the chains' first x (the usable-chain test at the end)
 
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int tile = blockIdx.x;
@@ -90,21 +145,45 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         }
         return;
     }
-    {
-        if constexpr (!LDSW) {
-            const int n = a.s.nets_params();
-            for (int i = threadIdx.x; i < n; i += blockDim.x) wlds[i] = a.packed[i];
-        } else {   // net wave b (of waves 0..2) gathers block b's lane shares from the packed vector into the field-major LDS copy
-            if (wave < 3) {
-                SoloNet<U> nb;
-                solo_gather<U>(nb, a.packed + (size_t)(wave * 2 + (lane >= 32 ? 1 : 0)) * a.s.net_params, D, (wave + 1) & 1, wave & 1, lane);
-                solo4_store<U>(wlds, wave, nb, lane);
-            }
+    unsigned long long p0 = 0, p1 = 0, p2 = 0, p3 = 0, p4 = 0, p5 = 0, p6 = 0, p7 = 0, p8 = 0;
+    (void)p0; (void)p1; (void)p2; (void)p3; (void)p4; (void)p5; (void)p6; (void)p7; (void)p8;
+    PSTAMP(p0);
+    // The launch's reads from global memory, all issued here in front of the first barrier and waited for once.  The weights come from
+    // the handle's lane image (solo_tile.h: built once per weight change), not from the packed vector: a net wave's register blocks
+    // straight into its registers, the LDS-weight forms' copy 16 bytes a thread; the step rule's table from the device's copy.
+    const float *limg = a.img + a.s.solo_image_offset();
+    const int j = wave;
+    const int pos = lane & 15;
+    const bool translate_half = lane >= 32;
+    const bool writer_lane = lane < 16;  // row (n = 0, h = 0) does the stores
+    const int row = tile * WPG + j;
+    const bool ok = row < C;
+    SoloNet<U> net[RB > 0 ? RB : 1];   // (weights in LDS: blocks 0 and 2 stay there, block 1 in registers where they fit, solo_coupling_inverse4)
+    float z[2][U];
+    double logl = 0.0;
+    if (wave < WPG) {   // ---- one walker per wave ----
+        if constexpr (LDSW) {
+            if constexpr (RB == 1) solo_image_load<U>(net[0], limg + (size_t)1 * SOLO4_NF * 64, lane);
+        } else {
+#pragma unroll
+            for (int b = 0; b < 3; ++b) solo_image_load<U>(net[b], limg + (size_t)b * SOLO4_NF * 64, lane);
         }
-        if (dynamic && use_tab)
-            for (int k = threadIdx.x; k < S + 2; k += blockDim.x) etab[k] = exp(1.0 / (double)(1 + k));
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int d = 2 * U * pos + 2 * u + c;
+                z[c][u] = (ok && d < D) ? a.z[(size_t)row * D + d] : 0.f;
+            }
+        logl = ok ? a.logl[row] : 0.0;
     }
+    if constexpr (LDSW) solo_image_to_lds<64 * (WPG + 2)>(wlds, limg);
+    PSTAMP(p1);
+    if (dynamic && use_tab)
+        for (int k = threadIdx.x; k < S + 2; k += blockDim.x) etab[k] = solo_etab_dev[k];
+    PSTAMP(p2);
     __syncthreads();
+    PSTAMP(p3);
 
     if (wave == WPG) {
         // proposal noise: the streams of the 16-walker forms -- per (walker, lane group g) 8 normals for dims
@@ -161,7 +240,9 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         };
         STAMP(n2);
         draw(0);
+        PSTAMP(p4);
         solo_barrier();                    // P0
+        PSTAMP(p5);
         if (S >= 1) {
             draw(1);
             solo_barrier();                // P1
@@ -181,7 +262,14 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         { unsigned long long n3 = 0; STAMP(n3); n_all = n3 - n2; }
 #endif
 #ifdef NNEST_STAMP
-        if (a.scale_out && lane == 0 && tile == 0) { a.scale_out[4] = (float)n_gen; a.scale_out[5] = (float)n_all; }
+        PSTAMP(p8);
+        if (a.scale_out && lane == 0 && tile == 0) {
+            float *o = a.scale_out;
+            o[4] = (float)n_gen; o[5] = (float)n_all;
+            // the noise wave's launch: staging, etab, the first barrier, seeds + draw(0), the wait at P0, everything behind it
+            o[32] = (float)(p1 - p0); o[33] = (float)(p2 - p1); o[34] = (float)(p3 - p2); o[35] = (float)(p4 - p3); o[36] = (float)(p5 - p4);
+            o[37] = (float)(p8 - p5); o[38] = (float)(p8 - p0);
+        }
 #endif
 #ifndef NNEST_STAMP
         if (!dynamic && a.scale_out && lane == 0) {   // scale_out has one entry per 16 walkers (nnest_mh_num_groups): the tile that holds a group's first walker reports
@@ -319,26 +407,11 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         return;
     }
 
-    // ---- one walker per wave ----
-    const int j = wave;
-    const int pos = lane & 15;
-    const bool translate_half = lane >= 32;
-    const bool writer_lane = lane < 16;  // row (n = 0, h = 0) does the stores
-    const int row = tile * WPG + j;
-    const bool ok = row < C;
+    // ---- one walker per wave (its weights, z and logl were asked for in front of the first barrier) ----
     const LikeSpec like = a.like;
     const double loglstar = a.loglstar;
     const bool free_mode = (a.flags & NNEST_MH_UNCONSTRAINED) != 0;
-
-    SoloNet<U> net[RB > 0 ? RB : 1];   // (weights in LDS: blocks 0 and 2 stay there, block 1 in registers where they fit, solo_coupling_inverse4)
-    if constexpr (LDSW) {
-        if constexpr (RB == 1)
-            solo_gather<U>(net[0], a.packed + (size_t)(1 * 2 + (translate_half ? 1 : 0)) * a.s.net_params, D, (1 + 1) & 1, 1 & 1, lane);
-    } else {
-#pragma unroll
-        for (int b = 0; b < 3; ++b)
-            solo_gather<U>(net[b], wlds + (size_t)(b * 2 + (translate_half ? 1 : 0)) * a.s.net_params, D, (b + 1) & 1, b & 1, lane);
-    }
+    PSTAMP(p4);
     // NormalizingFlow.inverse (networks.py:34-42), num_blocks = 3: blocks 2, 1, 0; block b conditions on class (b+1)&1 and
     // transforms class b&1
     const unsigned sel = translate_half ? 0xffffffffu : 0u;
@@ -359,17 +432,12 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         }
     };
 
-    float z[2][U], x[2][U];
+    float x[2][U];
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int d = 2 * U * pos + 2 * u + c;
-            z[c][u] = (ok && d < D) ? a.z[(size_t)row * D + d] : 0.f;
-            x[c][u] = z[c][u];
-        }
+        for (int c = 0; c < 2; ++c) x[c][u] = z[c][u];
     float ld = solo_logdet_total(inverse(x));  // x = f^-1(z), log_det_J  (sampler.py:266, :295)
-    double logl = ok ? a.logl[row] : 0.0;
     int n_acc = 0, n_call = 0;
 
     auto store_row = [&](float *base, size_t r, const float (&v)[2][U]) {
@@ -381,9 +449,14 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
                 if (d < D) base[r * D + d] = v[c][u];
             }
     };
-    // the chain's first x stays in the x output buffer for the launch: the reference counts a chain only if EVERY coordinate of its
-    // last x differs from its first (nested.py:432), tested at the end (no register is held for it)
-    if (writer_lane && ok && a.x) store_row(a.x, (size_t)row, x);
+    // the chain's first x waits in LDS for the launch: the reference counts a chain only if EVERY coordinate of its last x differs
+    // from its first (nested.py:432), tested at the end (no register is held for it; a lane reads back what it wrote itself)
+    if (writer_lane && a.x) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) x0buf[j][pos][2 * u + c] = x[c][u];
+    }
     if (DBG && writer_lane && ok) {
         if (a.hist_x) store_row(a.hist_x, (size_t)row * (S + 1), x);
         if (a.hist_logl && pos == 0) a.hist_logl[(size_t)row * (S + 1)] = logl;
@@ -401,7 +474,9 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         fs_next = fsbuf[kbuf & 1];
         ++kbuf;
     };
+    PSTAMP(p5);
     fetch_noise();
+    PSTAMP(p6);
 
     unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, a_prop = 0, a_inv = 0, a_post = 0, a_tot = 0;
     (void)st0; (void)st1; (void)st2; (void)st3; (void)a_prop; (void)a_inv; (void)a_post; (void)a_tot;
@@ -517,6 +592,7 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
 #endif
     }
     if (exact_all) solo_barrier();   // (the relay wave reads the last step's accepts behind it)
+    PSTAMP(p7);
 #ifdef NNEST_STAMP
     if (a.scale_out && lane == 0 && tile == 0) {
         float *o = a.scale_out;
@@ -533,7 +609,7 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     const int d = 2 * U * pos + 2 * u + c;
-                    const float x0 = (ok && d < D) ? a.x[(size_t)row * D + d] : 0.f;
+                    const float x0 = x0buf[j][pos][2 * u + c];
                     mine = mine && (d >= D || x[c][u] != x0);
                 }
         }
@@ -548,6 +624,16 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
             if (a.n_call) a.n_call[row] = n_call;
         }
     }
+#ifdef NNEST_STAMP
+    PSTAMP_DRAINED(p8);   // (the stores have landed)
+    if (a.scale_out && lane == 0 && tile == 0 && j == 0) {
+        // the first net wave's launch: staging, etab, the first barrier, the lane's weights, z / logl + the first inverse, the wait at
+        // P0, the step loop, the epilogue from loop exit to the last store, the whole
+        float *o = a.scale_out;
+        o[16] = (float)(p1 - p0); o[17] = (float)(p2 - p1); o[18] = (float)(p3 - p2); o[19] = (float)(p4 - p3); o[20] = (float)(p5 - p4);
+        o[21] = (float)(p6 - p5); o[22] = (float)(p7 - p6); o[23] = (float)(p8 - p7); o[24] = (float)(p8 - p0);
+    }
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -588,22 +674,18 @@ static __device__ __forceinline__ void slice_normals(uint64_t seed, uint64_t wal
 }
 
 template <int U, int LK>
-__global__ void __launch_bounds__(256) slice_kernel_solo(SliceArgs a, FlowShape s, const float *packed) {
+__global__ void __launch_bounds__(256) slice_kernel_solo(SliceArgs a, FlowShape s, const float *limg) {
     extern __shared__ __attribute__((aligned(16))) float wlds[];
+    __shared__ __attribute__((aligned(16))) float x0buf[4][16][2 * U];   // the chains' first x (the usable-chain test at the end)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int D = s.D, S = a.steps, C = a.C;
     constexpr bool LDSW = solo_lds_weights<U, 4>();
-    {
-        if constexpr (!LDSW) {
-            const int n = s.nets_params();
-            for (int i = threadIdx.x; i < n; i += blockDim.x) wlds[i] = packed[i];
-        } else if (wave < 3) {
-            SoloNet<U> nb;
-            solo_gather<U>(nb, packed + (size_t)(wave * 2 + (lane >= 32 ? 1 : 0)) * s.net_params, D, (wave + 1) & 1, wave & 1, lane);
-            solo4_store<U>(wlds, wave, nb, lane);
-        }
+    // the weights from the handle's lane image (solo_tile.h), as in mh_kernel_solo: x_dim > 64 copies it to LDS, else the lanes load
+    // their shares of it below and the kernel has neither an LDS copy nor a barrier
+    if constexpr (LDSW) {
+        solo_image_to_lds<256>(wlds, limg);
+        __syncthreads();
     }
-    __syncthreads();
     const int pos = lane & 15;
     const bool translate_half = lane >= 32, writer_lane = lane < 16;
     const int row = blockIdx.x * 4 + wave;
@@ -614,8 +696,7 @@ __global__ void __launch_bounds__(256) slice_kernel_solo(SliceArgs a, FlowShape 
     SoloNet<U> net[LDSW ? 1 : 3];
     if constexpr (!LDSW) {
 #pragma unroll
-        for (int b = 0; b < 3; ++b)
-            solo_gather<U>(net[b], wlds + (size_t)(b * 2 + (translate_half ? 1 : 0)) * s.net_params, D, (b + 1) & 1, b & 1, lane);
+        for (int b = 0; b < 3; ++b) solo_image_load<U>(net[b], limg + (size_t)b * SOLO4_NF * 64, lane);
     }
     const unsigned sel = translate_half ? 0xffffffffu : 0u;
     const bool h1 = (lane & 16) != 0;
@@ -653,7 +734,12 @@ __global__ void __launch_bounds__(256) slice_kernel_solo(SliceArgs a, FlowShape 
         }
     float ld = solo_logdet_total(inverse(x));
     double logl = a.logl[row];
-    if (writer_lane && a.x) store_row(a.x, (size_t)row, x);   // the chain's first x (usable-chain test at the end, nested.py:432)
+    if (writer_lane && a.x) {   // the chain's first x waits in LDS (usable-chain test at the end, nested.py:432; a lane reads back its own)
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) x0buf[wave][pos][2 * u + c] = x[c][u];
+    }
     if (writer_lane && a.hist_x) store_row(a.hist_x, (size_t)row * (S + 1), x);
     const uint64_t walker = a.walker_offset + (uint64_t)row;
     int n_call = 0, n_move = 0, n_eval = 0;
@@ -734,7 +820,7 @@ __global__ void __launch_bounds__(256) slice_kernel_solo(SliceArgs a, FlowShape 
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     const int d = 2 * U * pos + 2 * u + c;
-                    const float x0 = d < D ? a.x[(size_t)row * D + d] : 0.f;
+                    const float x0 = x0buf[wave][pos][2 * u + c];
                     mine = mine && (d >= D || x[c][u] != x0);
                 }
         }
@@ -767,11 +853,11 @@ __global__ void slice_fill_noise_kernel(float *__restrict__ dz, int steps, int C
 }
 
 template <int U, int LK>
-static hipError_t launch_slice_k(const FlowShape &s, const float *packed, const SliceArgs &a, hipStream_t st) {
-    const size_t lds = solo_lds_weights<U, 4>() ? (size_t)3 * SOLO4_NF * 64 * sizeof(float) : (size_t)s.nets_params() * sizeof(float);
+static hipError_t launch_slice_k(const FlowShape &s, const float *limg, const SliceArgs &a, hipStream_t st) {
+    const size_t lds = solo_lds_weights<U, 4>() ? (size_t)3 * SOLO4_NF * 64 * sizeof(float) : 0;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(slice_kernel_solo<U, LK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((slice_kernel_solo<U, LK>), dim3((a.C + 3) / 4), dim3(256), lds, st, a, s, packed);
+    hipLaunchKernelGGL((slice_kernel_solo<U, LK>), dim3((a.C + 3) / 4), dim3(256), lds, st, a, s, limg);
     return hipGetLastError();
 }
 
@@ -779,15 +865,15 @@ bool slice_form_eligible(const FlowShape &s) {
     return s.kind == FLOW_KIND_NVP && s.H == 16 && s.B == 3 && s.L == 1 && s.scale_mode == 0 && s.NT >= 1 && s.NT <= 4;
 }
 
-hipError_t launch_slice_solo(const FlowShape &s, const float *packed, const SliceArgs &a, hipStream_t st) {
+hipError_t launch_slice_solo(const FlowShape &s, const float *limg, const SliceArgs &a, hipStream_t st) {
     if (a.C <= 0) return hipSuccess;
     if (!slice_form_eligible(s)) return hipErrorInvalidConfiguration;
     const bool rosen = a.like.id == NNEST_LIKE_ROSENBROCK;
     switch (s.NT) {
-        case 1: return rosen ? launch_slice_k<1, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : launch_slice_k<1, -1>(s, packed, a, st);
-        case 2: return rosen ? launch_slice_k<2, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : launch_slice_k<2, -1>(s, packed, a, st);
-        case 3: return rosen ? launch_slice_k<3, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : launch_slice_k<3, -1>(s, packed, a, st);
-        case 4: return rosen ? launch_slice_k<4, NNEST_LIKE_ROSENBROCK>(s, packed, a, st) : launch_slice_k<4, -1>(s, packed, a, st);
+        case 1: return rosen ? launch_slice_k<1, NNEST_LIKE_ROSENBROCK>(s, limg, a, st) : launch_slice_k<1, -1>(s, limg, a, st);
+        case 2: return rosen ? launch_slice_k<2, NNEST_LIKE_ROSENBROCK>(s, limg, a, st) : launch_slice_k<2, -1>(s, limg, a, st);
+        case 3: return rosen ? launch_slice_k<3, NNEST_LIKE_ROSENBROCK>(s, limg, a, st) : launch_slice_k<3, -1>(s, limg, a, st);
+        case 4: return rosen ? launch_slice_k<4, NNEST_LIKE_ROSENBROCK>(s, limg, a, st) : launch_slice_k<4, -1>(s, limg, a, st);
     }
     return hipErrorInvalidConfiguration;
 }
@@ -826,7 +912,7 @@ template <int U, bool DBG, int LK, int WPG>
 static hipError_t launch_solo_k(const MhArgs &a, hipStream_t st) {
     const int batch = (a.flags & NNEST_MH_DYNAMIC_BATCH) ? 1 : 0;
     const int grid = (a.C + WPG - 1) / WPG + batch;  // + the workgroup that publishes the batch-wide counts
-    const size_t lds = solo_lds_weights<U, WPG>() ? (size_t)3 * SOLO4_NF * 64 * sizeof(float) : (size_t)a.s.nets_params() * sizeof(float);
+    const size_t lds = solo_lds_weights<U, WPG>() ? (size_t)3 * SOLO4_NF * 64 * sizeof(float) : 0;   // (the register form reads the lane image itself)
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(mh_kernel_solo<U, DBG, LK, WPG>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

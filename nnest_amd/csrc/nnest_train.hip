@@ -1152,7 +1152,10 @@ hipError_t launch_train(float *packed, float *adam_m, float *adam_v, float *best
         case TRAIN_FORM_ROWS: return dispatch_train_rows(a, gridws, st);
         case TRAIN_FORM_GRID: return dispatch_train_grid(a, gridws, st);
     }
-    return dispatch_train(a, st);
+    // (the one-workgroup form rebuilds the fragment image inside the kernel, not through launch_repack: the lane image follows here)
+    hipError_t e = dispatch_train(a, st);
+    if (e == hipSuccess && s.has_solo_image()) e = launch_solo_image(a.w, img + s.solo_image_offset(), s, st);
+    return e;
 }
 
 int train_form_for(const FlowShape &s, int batch, int flags, int *detail) {

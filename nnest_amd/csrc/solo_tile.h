@@ -57,8 +57,10 @@ struct SoloNet {  // this lane's share of one coupling block (its net n, its K-h
 // U = 2 lays the LAST layer out differently (solo_block2, solo_chain_full): row h holds the 16 rotations of output slot h --
 // w3[0][t] rotation t, w3[1][t] rotation 8 + t, b3[0] the slot's bias in both rows, b3[1] = 0 -- still 44 weights per lane.
 
-// gather from the packed (block, net) region (LDS copy), state_dict layout W0[H][D] b0[H] W1[H][H] b1[H] Wo[D][H] bo[D]
-// (nnest/networks.py:271-282).  cc / ct: conditioning / transformed parity class of the block.
+// gather from the packed (block, net) region, state_dict layout W0[H][D] b0[H] W1[H][H] b1[H] Wo[D][H] bo[D]
+// (nnest/networks.py:271-282).  cc / ct: conditioning / transformed parity class of the block.  K4 and the slice kernel read the
+// result from the handle's lane image (below: built with this function once per weight change); the ensemble, random-walk and
+// importance kernels still call it at every launch, on their LDS copy of the packed vector.
 // The scale net's hidden layers (the lanes below 32) are stored times 2 log2(e): their sums then are the argument of v_exp_f32
 // itself -- tanh(a) = 1 - 2 / (2^{a 2 log2 e} + 1), solo_activate -- one multiply less per activation on the step's serial chain
 // (the translate half's relu lanes keep their weights as they are).
@@ -380,6 +382,44 @@ struct Solo4Lds {   // a block's weights where they live: the workgroup's LDS co
     __device__ __forceinline__ void load8(float (&w)[8], int f0) const { solo4_load8(w, blk, f0, lane); }
     __device__ __forceinline__ f32x4 bias(int c) const { return *reinterpret_cast<const f32x4 *>(blk + ((size_t)(18 + c) * 64 + lane) * 4); }
 };
+// ---- the LANE IMAGE: what solo_gather produces, kept per handle ---------------------------------------------------------------
+// The three blocks' fields in the layout above, [block][SOLO4_NF / 4][lane][4], in global memory behind the handle's fragment image
+// (flow_tile.h: solo_image_offset).  solo_image_kernel (nnest_solo.hip) builds it by CALLING solo_gather and solo4_store, so its
+// values are their bits -- the U = 2 whole-K last layer and the prescale included -- whenever the fragment image is rebuilt
+// (launch_repack), i.e. once per weight change.  A launch reads it instead of gathering again: a lane's share of a block is 16-byte
+// loads, a wave's load one contiguous KB; the LDS copy of the LDS-weight forms is the image itself, copied 16 bytes a thread.
+static_assert(3 * SOLO4_NF * 64 == SOLO_IMAGE_FLOATS, "flow_tile.h sizes the allocation");
+template <int U>   // this lane's share of one block: blk = the block's fields in the image (or in its LDS copy)
+static __device__ __forceinline__ void solo_image_load(SoloNet<U> &n, const float *blk, int lane) {
+    const Solo4Lds src{blk, lane};
+#pragma unroll
+    for (int u = 0; u < U; ++u) { src.load8(n.w1[u], 8 * u); src.load8(n.w3[u], 40 + 8 * u); }
+    src.load8(n.w2, 32);
+    const f32x4 bA = src.bias(0);   // b1 b2 b3[0] b3[1]
+    n.b1 = bA.x; n.b2 = bA.y; n.b3[0] = bA.z;
+    if constexpr (U >= 2) n.b3[U >= 2 ? 1 : 0] = bA.w;
+    if constexpr (U >= 3) {
+        const f32x4 bB = src.bias(1);   // b3[2] b3[3] - -
+        n.b3[U >= 3 ? 2 : 0] = bB.x;
+        if constexpr (U >= 4) n.b3[U >= 4 ? 3 : 0] = bB.y;
+    }
+}
+// the workgroup's LDS copy of the whole image, by all NTHR threads of the workgroup, in front of a barrier (every load is issued
+// before the first store waits)
+template <int NTHR>
+static __device__ __forceinline__ void solo_image_to_lds(float *wlds, const float *limg) {
+    constexpr int N4 = SOLO_IMAGE_FLOATS / 4, TRIPS = (N4 + NTHR - 1) / NTHR;
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(limg);
+    f32x4 *dst = reinterpret_cast<f32x4 *>(wlds);
+    f32x4 v[TRIPS];
+#pragma unroll
+    for (int i = 0; i < TRIPS; ++i)
+        if (N4 % NTHR == 0 || (int)threadIdx.x + i * NTHR < N4) v[i] = src[threadIdx.x + i * NTHR];
+#pragma unroll
+    for (int i = 0; i < TRIPS; ++i)
+        if (N4 % NTHR == 0 || (int)threadIdx.x + i * NTHR < N4) dst[threadIdx.x + i * NTHR] = v[i];
+}
+
 template <int U>
 struct Solo4Reg {   // ... or this lane's registers (ONE of the three blocks: a third of the LDS traffic of a step)
     const SoloNet<U> &n;

@@ -1,14 +1,18 @@
 #!/bin/bash
-# NNEST_STAMP diagnostic build of the quad / solo kernels and the training kernels into tools/ab/lib_STAMP.so (the other objects come from the normal build)
+# NNEST_STAMP diagnostic build of the quad / solo kernels and the training kernels into tools/ab/lib_STAMP.so (the other objects come
+# from the normal build, which has to be there).  The solo kernel's stamps are those of its launch prologue and epilogue
+# (tools/stamp_prologue.py); STEPS=1 adds its per-step stamps (tools/stamp_run.py), which slow the loop.
 set -e
 cd "$(dirname "$0")/../nnest_amd/csrc"
 mkdir -p ../../tools/ab
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-gpu-rdc -DNNEST_STAMP -c nnest_quad.hip -o /tmp/quad_stamp.o
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-gpu-rdc -DNNEST_STAMP -c nnest_solo.hip -o /tmp/solo_stamp.o
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-gpu-rdc -DNNEST_STAMP -c nnest_train.hip -o /tmp/train_stamp.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/ab/lib_STAMP.so nnest_abi.o nnest_kernels.o /tmp/quad_stamp.o /tmp/solo_stamp.o \
-    /tmp/train_stamp.o nnest_spline.o nnest_spline_mh.o nnest_spline_train.o nnest_spline_rows.o nnest_chol.o nnest_host.o -lpthread
+T=$(mktemp -d)
+trap 'rm -rf "$T"' EXIT
+HIPCC="/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-gpu-rdc -DNNEST_STAMP"
+$HIPCC -c nnest_quad.hip -o "$T/quad_stamp.o"
+$HIPCC ${STEPS:+-DNNEST_STAMP_STEPS} -c nnest_solo.hip -o "$T/solo_stamp.o"
+$HIPCC -c nnest_train.hip -o "$T/train_stamp.o"
+OTHERS=$(ls *.o | grep -v -x -e nnest_quad.o -e nnest_solo.o -e nnest_train.o)
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/ab/lib_STAMP.so $OTHERS "$T/quad_stamp.o" "$T/solo_stamp.o" "$T/train_stamp.o" -lpthread
 # the rows form of the spline training step with its stamps (tools/time_spline_train.py prints them through NNEST_HIP_LIB)
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-gpu-rdc -DNNEST_STAMP -c nnest_spline_rows.hip -o /tmp/rows_stamp.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/ab/lib_ROWS_STAMP.so nnest_abi.o nnest_kernels.o nnest_quad.o nnest_solo.o \
-    nnest_train.o nnest_spline.o nnest_spline_mh.o nnest_spline_train.o /tmp/rows_stamp.o nnest_chol.o nnest_host.o -lpthread
+$HIPCC -c nnest_spline_rows.hip -o "$T/rows_stamp.o"
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/ab/lib_ROWS_STAMP.so $(ls *.o | grep -v -x nnest_spline_rows.o) "$T/rows_stamp.o" -lpthread
