@@ -33,6 +33,7 @@
 #include "mh_common.h"
 #include "nnest_internal.h"
 #include "solo_loglike.h"
+#include "solo_schedule.h"
 #include "solo_tile.h"
 
 namespace nnest {
@@ -98,6 +99,15 @@ hipError_t launch_solo_image(const float *packed, float *limg, const FlowShape &
 template <int U, int WPG> constexpr bool solo_lds_weights() { return U >= 3 || WPG > 4; }
 template <int U, int WPG> constexpr int solo_reg_blocks() { return !solo_lds_weights<U, WPG>() ? 3 : (WPG == 4 ? 1 : (U <= 2 && WPG == 8 ? 1 : 0)); }
 
+// the values pass through an (empty) volatile statement: what reads them stays behind the volatile statement in front of it
+template <int U>
+static __device__ __forceinline__ void solo_pin(float (&v)[2][U]) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int u = 0; u < U; ++u) asm volatile("" : "+v"(v[c][u]));
+}
+
 enum { MH_SOLO_LAG_INTERNAL = 8 };   // the relay's schedule under lag 0 (no lagged step exists then: only its bookkeeping uses it)
 template <int U, bool DBG, int LK, int WPG>
 __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
@@ -127,7 +137,7 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
     const int lag = exact_all ? MH_SOLO_LAG_INTERNAL : mh_flag_lag(a.flags);   // otherwise >= 3 (solo_form_eligible): the rule is always relayed
     // the first `warm` steps apply the rule exactly (a grid-wide wait per step, hidden behind two evaluations) -- where its gain
     // 1 / (1 + n) is large and the scale still far from where it settles -- the rest `lag` steps behind (mh_common.h); at most S - 1
-    const int warm = dynamic ? min(exact_all ? S : mh_flag_warm(a.flags), S - 1) : 0;
+    const int warm = solo_warm_steps(S, mh_flag_warm(a.flags), dynamic, exact_all);
     constexpr bool LDSW = solo_lds_weights<U, WPG>();
     constexpr int RB = solo_reg_blocks<U, WPG>();
     const int ntiles = (C + WPG - 1) / WPG;
@@ -253,7 +263,7 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
                 draw(k + 2);
                 solo_barrier();            // B_k
             }
-            for (int k = warm > 0 ? warm + 2 : 2; k <= S; ++k) {
+            for (int k = solo_first_lagged_fetch(warm); k <= S; ++k) {
                 solo_barrier();            // P_k
                 draw(k + 1);
             }
@@ -330,7 +340,7 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
             solo_barrier(); /* publish buffer k */                                                                          \
         }
         unsigned long long qa = 0, qb = 0;
-        int k0 = 0;
+        const int k0 = solo_relay_first_iteration(warm);
         if (warm > 0) {
             // Warm-up: behind the net waves' step k (barrier A) post that step's accepts and wait for the batch's vote while the
             // net waves evaluate step k + 1 for BOTH scales it can lead to (fs_cand, written one vote ahead); at barrier B name
@@ -375,7 +385,6 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
                 }
                 solo_barrier();               // B_k
             }
-            k0 = warm + 2;
         }
         for (int k2 = k0; k2 <= S; k2 += 2) {
             SOLO_RELAY_ITERATION(k2, qa)
@@ -432,6 +441,10 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         }
     };
 
+    // x is read only behind the loop (the stores, the usable-chain test).  The register forms without history therefore do not select
+    // it step by step: they invert the last z once more at the end, through this same lambda.  The LDS-weight forms, whose copies of
+    // the inverse hipcc is free to compile differently, and the history kernels, which store x every step, keep the select.
+    constexpr bool X_LATE = !DBG && !LDSW;
     float x[2][U];
 #pragma unroll
     for (int u = 0; u < U; ++u)
@@ -463,19 +476,23 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
     }
 
     float nz[2 * U], u_next = 0.f, fs_next = a.step_size;
-    int kbuf = 0;
-    auto fetch_noise = [&]() {
-        solo_barrier();  // the noise wave has published buffer kbuf: noise, accept uniform and scale of the next step
+    // buffer k & 1 carries the noise of step k + 1: P0 publishes buffer 0, the fetch inside step k buffer k.  `par` is that parity; where
+    // the caller passes a constant (the lagged loop below, unrolled by two) the three LDS addresses are offsets of the instruction
+    // `zp`: the proposals in flight.  They pass through the barrier as operands, so that hipcc cannot start their inverse in front of
+    // it: the noise wave needs a whole step between two barriers for its draws, and a pair of steps whose barriers sit ~170 instructions
+    // late in one and at the head of the other (what the scheduler made of the unrolled loop) waits for it at every second barrier.
+    auto fetch_noise = [&](int par, auto &...zp) {
+        solo_barrier();  // the noise wave has published the buffer: noise, accept uniform and scale of the next step
+        (solo_pin(zp), ...);
         if (!recorded) {
 #pragma unroll
-            for (int k = 0; k < 2 * U; ++k) nz[k] = nbuf[kbuf & 1][j][pos][k];
-            u_next = ubuf[kbuf & 1][j];
+            for (int k = 0; k < 2 * U; ++k) nz[k] = nbuf[par][j][pos][k];
+            u_next = ubuf[par][j];
         }
-        fs_next = fsbuf[kbuf & 1];
-        ++kbuf;
+        fs_next = fsbuf[par];
     };
     PSTAMP(p5);
-    fetch_noise();
+    fetch_noise(0);                        // P0
     PSTAMP(p6);
 
     unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, a_prop = 0, a_inv = 0, a_post = 0, a_tot = 0;
@@ -537,7 +554,7 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
             r.acc = ok && ((double)u < rt);
         }
     };
-    auto apply = [&](int it, const Prop &r) {
+    auto apply = [&](int it, int par, const Prop &r) {   // par = it & 1
         n_call += (free_mode ? ok : r.pre) ? 1 : 0;
         n_acc += r.acc ? 1 : 0;
 #pragma unroll
@@ -545,29 +562,31 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
 #pragma unroll
             for (int uu = 0; uu < U; ++uu) {
                 z[c][uu] = r.acc ? r.zp[c][uu] : z[c][uu];
-                x[c][uu] = r.acc ? r.xp[c][uu] : x[c][uu];
+                if constexpr (!X_LATE) x[c][uu] = r.acc ? r.xp[c][uu] : x[c][uu];
             }
         ld = r.acc ? r.ldp : ld;
         logl = r.acc ? r.lp : logl;
-        if (dynamic && lane == 0) acc_lds[it & 1][j] = r.acc ? 1 : 0;  // sampler.py:422-431: counted by the relay wave after the next barrier
+        if (dynamic && lane == 0) acc_lds[par][j] = r.acc ? 1 : 0;  // sampler.py:422-431: counted by the relay wave after the next barrier
         if (DBG && writer_lane && ok) {
             if (a.hist_x) store_row(a.hist_x, (size_t)row * (S + 1) + it, x);
             if (a.hist_logl && pos == 0) a.hist_logl[(size_t)row * (S + 1) + it] = logl;
         }
     };
-    Prop cur;
-    bool have = false;   // `cur` already holds this step's evaluated proposal (warm-up: chosen among the two candidates)
-    for (int it = 1; it <= S; ++it) {
-        STAMP(st0);
-        if (!have) {
+    // The steps, in two loops (solo_schedule.h has the ranges and the barriers they add up to).  Steps 1 .. warm are EXACT steps: each
+    // evaluates its successor for two candidate scales, so an evaluated proposal (`cur`) travels from one to the next.  The steps behind
+    // them -- all of a fixed-step launch -- run straight through, carry no proposal between iterations, and are unrolled by two so that
+    // the parity of the noise buffer is a constant of each copy.
+    if (warm > 0) {
+        Prop cur;   // this step's evaluated proposal: step 1's own, then the one the vote chose among the two candidates
+        {
             float u;
-            propose(it, fs_next, cur.zp, u);
-            fetch_noise();
+            propose(1, fs_next, cur.zp, u);
+            fetch_noise(1, cur.zp);            // P1
             finish(cur, u);
         }
-        apply(it, cur);
-        have = false;
-        if (it <= warm) {
+        for (int it = 1; it <= warm; ++it) {
+            STAMP(st0);
+            apply(it, it & 1, cur);
             // Warm-up (round 4).  The scale of step it + 1 exists only after the whole batch's vote on step it -- a grid-wide
             // round trip (~2.5 us) that round 3 spent waiting.  There are only TWO scales it can be (the vote is up or down;
             // the relay wave works both out beforehand, in the rule's own float64 arithmetic), so step it + 1 is evaluated for
@@ -578,18 +597,40 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
             float u;
             propose(it + 1, f0, cur.zp, u);
             propose(it + 1, f1, c1.zp, u);
-            fetch_noise();                     // (the noise of step it + 2)
+            fetch_noise((it + 1) & 1, cur.zp, c1.zp);   // P: the noise of step it + 2
             finish(cur, u);
             finish(c1, u);
             solo_barrier();                    // B: the vote is in
             if (vote_sel != 0) cur = c1;
-            have = true;
             fs_next = fs_exact;                // (step warm + 2 runs at the scale the exact steps end with: no lagged vote is due yet)
+            STAMP(st3);
+#ifdef NNEST_STAMP
+            a_prop += st1 - st0; a_inv += st2 - st1; a_post += st3 - st2; a_tot += st3 - st0;
+#endif
         }
+        apply(warm + 1, (warm + 1) & 1, cur);  // step warm + 1: the candidate chosen at B_warm
+    }
+    auto straight_step = [&](int it, int par) {   // par = it & 1: propose, fetch, finish, apply
+        STAMP(st0);
+        Prop r;
+        float u;
+        propose(it, fs_next, r.zp, u);
+        fetch_noise(par, r.zp);                // P_it
+        finish(r, u);
+        apply(it, par, r);
         STAMP(st3);
 #ifdef NNEST_STAMP
         a_prop += st1 - st0; a_inv += st2 - st1; a_post += st3 - st2; a_tot += st3 - st0;
 #endif
+    };
+    {
+        int it = solo_first_straight_step(warm);
+        if (it <= S && (it & 1)) { straight_step(it, 1); ++it; }   // (an odd first step alone: the pairs below start even)
+        for (; it < S; it += 2) {
+            straight_step(it, 0);
+            straight_step(it + 1, 1);
+        }
+        if (it <= S) straight_step(it, 0);      // the odd remainder
     }
     if (exact_all) solo_barrier();   // (the relay wave reads the last step's accepts behind it)
     PSTAMP(p7);
@@ -602,6 +643,13 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
 #endif
     bool all_moved = n_acc > 0;   // (no x buffer: the accept count stands in)
     if (a.x) {
+        if constexpr (X_LATE) {   // x = f^-1(z) of the last accepted z: the statement that made every accepted x, so the same bits
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) x[c][u] = z[c][u];
+            (void)inverse(x);
+        }
         bool mine = true;
         if (writer_lane) {
 #pragma unroll
