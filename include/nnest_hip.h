@@ -590,6 +590,9 @@ int nnest_mh_fill_noise(float *dz_dev, float *u_dev, int steps, int C, int D, ui
  *              epoch_offset 0 and flags = NNEST_TRAIN_FINALIZE.
  * Adam moments and step count persist in the handle across calls (optimizer is created once,
  * trainer.py:121-122).
+ * Returns NNEST_E_UNSUPPORTED for batch > 128, for a MAF handle, and where min(batch, n_train) is more rows than one workgroup can
+ * stage: 96 at hidden_dim 64 with two hidden layers, 64 with three, 112 at hidden_dim 32 with three and x_dim > 32.  Such an epoch
+ * loop is driven from the host: nnest_nvp_loss_grad, which splits a batch over launches, and nnest_nvp_adam_step per minibatch.
  */
 typedef struct {
     int epochs_run;             /* total epochs run so far (including previous chunks) */
@@ -613,7 +616,8 @@ int nnest_nvp_train(nnest_nvp_t *nvp, const float *xtrain_dev, int n_train, cons
  * these `flags`, from the predicates of the launch itself -- 0: train_kernel, one workgroup (*detail = how many of its two fragment
  * images live in LDS: 2, 1 or 0); 1: train_kernel_grid, eight workgroups (*detail = 10 NT + L, NT = ceil(x_dim / 32), L = num_layers);
  * 2: train_kernel_rows, one workgroup per four rows (*detail = U = NT).  -1: nnest_nvp_train refuses the call (batch outside
- * [1, 128], a MAF handle).  detail may be NULL. */
+ * [1, 128], a MAF handle, or more rows than one workgroup can stage, as stated above: nnest_nvp_loss_grad and nnest_nvp_vjp split
+ * such a batch over launches, the one-launch epoch loop cannot).  detail may be NULL. */
 int nnest_nvp_train_form(const nnest_nvp_t *nvp, int batch, int flags, int *detail);
 
 /* One minibatch: loss and dloss/dw (before weight decay) into grad_dev [num_params], no update.

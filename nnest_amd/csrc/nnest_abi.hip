@@ -795,6 +795,14 @@ int nnest_nvp_train(nnest_nvp_t *h, const float *xtrain_dev, int n_train, const 
     if (batch > 128) return fail(NNEST_E_UNSUPPORTED, "batch_size=%d > 128 (one workgroup holds a minibatch)", batch);
     if (h->s.kind == FLOW_KIND_MAF)
         return fail(NNEST_E_UNSUPPORTED, "maf: the epoch loop is driven from the host (nnest_nvp_loss_grad + nnest_nvp_adam_step per minibatch)");
+    const int stage_rows = train_rows_per_launch(h->s);
+    if (stage_rows <= 0)
+        return fail(NNEST_E_UNSUPPORTED, "x_dim=%d hidden_dim=%d num_layers=%d: no training kernel is instantiated for this shape", h->s.D,
+                    h->s.H, h->s.L);
+    if ((batch < n_train ? batch : n_train) > stage_rows)
+        return fail(NNEST_E_UNSUPPORTED, "hidden_dim=%d num_layers=%d: one workgroup stages at most %d rows of a minibatch, batch_size=%d "
+                    "(drive the epoch loop from the host: nnest_nvp_loss_grad + nnest_nvp_adam_step per minibatch)", h->s.H, h->s.L,
+                    stage_rows, batch);
     HIP_TRY(launch_train(h->w, h->adam_m, h->adam_v, h->best_w, h->img, h->adam_step, h->s, xtrain_dev, n_train, xvalid_dev,
                          n_valid, perm_dev, noise_dev, seed, jitter, batch, max_epochs, patience, lr, weight_decay,
                          epoch_offset, flags, losses_dev, result_dev, h->train_ws, h->fwd_pos, h->bwd_pos, (hipStream_t)stream));
@@ -802,7 +810,7 @@ int nnest_nvp_train(nnest_nvp_t *h, const float *xtrain_dev, int n_train, const 
 }
 
 int nnest_nvp_train_form(const nnest_nvp_t *h, int batch, int flags, int *detail) {
-    if (!h || batch < 1 || batch > 128 || h->s.kind == FLOW_KIND_MAF) return -1;
+    if (!h || batch < 1 || batch > 128 || h->s.kind == FLOW_KIND_MAF || batch > train_rows_per_launch(h->s)) return -1;
     return train_form_for(h->s, batch, flags, detail);
 }
 

@@ -76,6 +76,10 @@ hipError_t launch_train(float *packed, float *adam_m, float *adam_v, float *best
                         hipStream_t st);
 // the form launch_train runs a minibatch of `batch` rows in (nnest_nvp_train_form, include/nnest_hip.h)
 int train_form_for(const FlowShape &s, int batch, int flags, int *detail);
+// rows one launch of the one-workgroup training kernel stages for this shape: 128, but 96 / 64 at hidden 64 with two / three hidden
+// layers and 112 at hidden 32 with three and x_dim > 32.  launch_loss_grad and launch_vjp split a larger batch over launches; the
+// epoch loop (launch_train) cannot
+int train_rows_per_launch(const FlowShape &s);
 hipError_t launch_build_pos(int *fwd_pos, int *bwd_pos, const FlowShape &s, hipStream_t st);
 // masked autoregressive flow (maf_train.h inside nnest_train.hip)
 size_t maf_workspace_floats(const FlowShape &s);

@@ -971,7 +971,9 @@ static hipError_t launch_train_tt(const TrainArgs &a, size_t lds, hipStream_t st
 
 // which of the two fragment images of train_kernel live in LDS next to the staging area (its IMGLDS), and the LDS bytes that takes.
 // The staging area is sized for TRAIN_MAX_ROWS rows; where that alone is more than a CU has (hidden 64 with two or three hidden
-// layers) it is sized for the rows of the launch's largest minibatch, which is all the kernel indexes (rows_pad).
+// layers; hidden 32 with three at x_dim > 32, whose 160 KB leave no room for the kernel's own __shared__ variables) it is sized for the
+// rows of the launch's largest minibatch, which is all the kernel indexes (rows_pad).
+static const size_t TRAIN_STAGE_ROOM = 160 * 1024 - 512;   // a CU's LDS less train_kernel's static __shared__ (red, ctl, ctlf, sred: 312 bytes)
 template <int NT, int NH, int L>
 static int train_imglds(const FlowShape &s, int rows, size_t &lds) {
     typedef StageMap<NT, NH, L> SM;
@@ -980,7 +982,7 @@ static int train_imglds(const FlowShape &s, int rows, size_t &lds) {
     const size_t with_fwd = stage + (size_t)s.image_floats * sizeof(float);
     if (with_img <= 160 * 1024 - 256) { lds = with_img; return 2; }
     if (with_fwd <= 160 * 1024 - 256) { lds = with_fwd; return 1; }
-    lds = stage <= 160 * 1024 ? stage : (size_t)SM::count * (size_t)((min(max(rows, 1), TRAIN_MAX_ROWS) + 15) & ~15) * 16 * sizeof(float);
+    lds = stage <= TRAIN_STAGE_ROOM ? stage : (size_t)SM::count * (size_t)((min(max(rows, 1), TRAIN_MAX_ROWS) + 15) & ~15) * 16 * sizeof(float);
     return 0;
 }
 
@@ -1018,6 +1020,20 @@ static int train_imglds_for(const FlowShape &s) {
     return -1;
 }
 
+// the rows one launch of train_kernel can stage for this shape: TRAIN_MAX_ROWS wherever that fits a CU's LDS, else (hidden 64 with two
+// or three hidden layers, hidden 32 with three at x_dim > 32) the largest multiple of 16 that does -- train_imglds' rule, solved for the
+// rows: 96, 64 and 112.  0: no kernel
+int train_rows_per_launch(const FlowShape &s) {
+#define TRY_SHAPE(nt, nh, l)                                                                                  \
+    if (s.NT == nt && s.NH == nh && s.L == l) {                                                               \
+        const size_t tile = (size_t)StageMap<nt, nh, l>::count * 16 * 16 * sizeof(float);                     \
+        return tile * (TRAIN_MAX_ROWS / 16) <= TRAIN_STAGE_ROOM ? TRAIN_MAX_ROWS : (int)(TRAIN_STAGE_ROOM / tile) * 16; \
+    }
+    TRAIN_SHAPES(TRY_SHAPE)
+#undef TRY_SHAPE
+    return 0;
+}
+
 #include "nnest_train_grid.h"
 #include "nnest_train_rows.h"
 // torch.optim.Adam (coupled weight decay), one element of the step, every operation rounded by itself (no multiply-add contraction: the choice of which product a compiler
@@ -1036,6 +1052,44 @@ __device__ __forceinline__ float adam_elem(float wi, float g, float &mref, float
 
 #include "maf_train.h"
 
+// dst = a dst + b src (src may be dst): the sum of a batch's gradient over the launches it was split into (split_rows)
+__global__ void combine_kernel(float *dst, const float *src, int n, float a, float b) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[i] = a * dst[i] + b * src[i];
+}
+
+// One batch of loss_grad / vjp as launches of at most train_rows_per_launch rows.  Both are sums over rows -- loss_grad's a mean, so a
+// launch of m of the M rows enters with weight m / M; the vjp's cotangents are per row, weight 1 -- so the launches after the first
+// write into the workspace slot that only the epoch loop uses (its gradient, behind the backward image) and are added to the
+// caller's.  Every shape but hidden 64 with two or three hidden layers and hidden 32 with three at x_dim > 32 (train_rows_per_launch:
+// 96, 64 and 112 rows) takes 128 rows in one launch and comes through here unchanged.
+static hipError_t split_rows(TrainArgs a, int M, float *workspace, hipStream_t st) {
+    const FlowShape &s = a.s;
+    const int cap = train_rows_per_launch(s);
+    if (cap <= 0) return hipErrorInvalidConfiguration;
+    if (M <= cap) return dispatch_train(a, st);
+    const int n = s.num_params(), launches = (M + cap - 1) / cap, per = (((M + launches - 1) / launches) + 15) & ~15;   // per <= cap
+    float *grad = a.grad, *loss = a.loss_out, *part = workspace + s.image_floats;
+    const float *x = a.xtrain, *gz = a.gz;
+    float *gx = a.gx;
+    const bool mean = a.mode == TRAIN_MODE_GRAD_ONLY;
+    for (int r0 = 0; r0 < M; r0 += per) {
+        const int m = min(per, M - r0);
+        const float wgt = mean ? (float)m / (float)M : 1.f;
+        a.xtrain = x + (size_t)r0 * s.D;
+        a.n_train = a.batch = m;
+        if (gz) { a.gz = gz + (size_t)r0 * s.D; a.gx = gx + (size_t)r0 * s.D; }
+        a.grad = r0 ? part : grad;
+        if (loss) a.loss_out = r0 ? part + n : loss;
+        hipError_t e = dispatch_train(a, st);
+        if (e != hipSuccess) return e;
+        if (r0 == 0 && !mean) continue;
+        hipLaunchKernelGGL(combine_kernel, dim3(64), dim3(256), 0, st, grad, a.grad, n, r0 ? 1.f : wgt, r0 ? wgt : 0.f);
+        if (loss) hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, st, loss, a.loss_out, 1, r0 ? 1.f : wgt, r0 ? wgt : 0.f);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_loss_grad(const float *packed, const FlowShape &s, const float *x, int M, float *grad, float *loss,
                             float *workspace, float *img_fwd, const int *fwd_pos, const int *bwd_pos, hipStream_t st) {
     TrainArgs a;
@@ -1053,7 +1107,7 @@ hipError_t launch_loss_grad(const float *packed, const FlowShape &s, const float
     a.batch = M;
     a.loss_out = loss;
     a.mode = TRAIN_MODE_GRAD_ONLY;
-    return dispatch_train(a, st);
+    return split_rows(a, M, workspace, st);
 }
 
 hipError_t launch_vjp(const float *packed, const FlowShape &s, const float *x, const float *gz, float gld, int M, float *grad, float *gx,
@@ -1073,7 +1127,7 @@ hipError_t launch_vjp(const float *packed, const FlowShape &s, const float *x, c
     a.batch = M;
     a.gz = gz; a.gx = gx; a.gld_in = gld;
     a.mode = TRAIN_MODE_VJP;
-    return dispatch_train(a, st);
+    return split_rows(a, M, workspace, st);
 }
 
 // torch.optim.Adam (coupled weight decay) over the packed vector from an externally supplied gradient: the optimiser step

@@ -909,17 +909,28 @@ class HipNVP(_PaddedVectors, _HipFlow):
             raise _lib.NnestHipError('nnest_nvp_train_form: no training kernel takes batch=%d on this handle' % int(batch))
         return ('single', 'grid', 'rows')[form], detail.value
 
+    def epoch_loop_on_host(self, batch, n_train):
+        """whether train_epochs drives minibatches of `batch` rows out of n_train from the host (flow.train_epochs_host: a run in ONE
+        call, no chunks -- Trainer.train asks before it cuts a run into launches).  The reference takes any batch_size (trainer.py:36,
+        :76, :185), so more than 128 rows are a slower path, not a refusal; and so is a minibatch that one workgroup cannot stage
+        (nnest_nvp_train_form answers -1: more than 96 / 64 rows at hidden 64 with two / three hidden layers, more than 112 at hidden 32
+        with three and x_dim > 32) -- loss_grad splits such a batch over launches, the one-launch epoch loop cannot"""
+        rows = max(1, min(int(batch), int(n_train)))
+        return int(batch) > TRAIN_KERNEL_MAX_BATCH or self._lib.nnest_nvp_train_form(self._h, rows, 0, None) < 0
+
     def train_epochs(self, xtrain, xvalid, perm, noise=None, seed=0, jitter=0.0, batch=100, max_epochs=1, patience=50,
                      lr=1e-3, weight_decay=1e-6, epoch_offset=0, resume=False, finalize=True, result=None, one_cu=False):
         """K5: Trainer.train's epoch loop (trainer.py:198-241) in one launch.  perm int32 [max_epochs, n_train];
         noise None (in-kernel Philox) or float32 [max_epochs, n_train, D] in loader order.
         A long train() can be split into chunks: pass the previous chunk's `result` tensor with resume=True,
-        epoch_offset = epochs already run, finalize=True only for the last chunk (see include/nnest_hip.h).
+        epoch_offset = epochs already run, finalize=True only for the last chunk (see include/nnest_hip.h) -- except where
+        epoch_loop_on_host(batch, n_train) says that the loop is driven from the host, which takes a run in one call.
         Returns dict(losses [epochs,2] tensor, epochs_run, best_epoch, best_validation_loss, last_train_loss,
         counter, stopped, result)."""
         dev = self.device
-        if int(batch) > TRAIN_KERNEL_MAX_BATCH:   # the reference takes any batch_size (trainer.py:36, :76, :185): a slower path, not a refusal
-            assert not resume and epoch_offset == 0, 'batch_size > %d: the host-driven loop takes a run in one call' % TRAIN_KERNEL_MAX_BATCH
+        if self.epoch_loop_on_host(batch, len(xtrain)):
+            if resume or epoch_offset != 0:
+                raise ValueError('batch_size %d on this flow: the host-driven epoch loop takes a run in one call (epoch_loop_on_host)' % int(batch))
             return train_epochs_host(self, chunked_epoch(self, TRAIN_KERNEL_MAX_BATCH), xtrain, xvalid, perm, noise, seed, jitter, batch,
                                      max_epochs, patience, lr, weight_decay)
         xtrain = _as_dev_f32(xtrain, dev)

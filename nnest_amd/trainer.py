@@ -204,8 +204,12 @@ class Trainer(object):
         if self.log:
             self.logger.info('Training jitter [%5.4f]' % training_jitter)
         result, res, done, all_losses = None, None, 0, []
+        epoch_chunk = getattr(self.netG, 'epoch_chunk', EPOCH_CHUNK)
+        on_host = getattr(self.netG, 'epoch_loop_on_host', None)   # (HipNVP: by batch_size and, for the deep wide nets, by the rows
+        if on_host is not None and on_host(self.batch_size, n_train):   # one workgroup can stage)
+            epoch_chunk = 1 << 30   # the host-driven epoch loop (flow.train_epochs_host) takes a run in one call
         while done < max_iters:
-            chunk = min(getattr(self.netG, 'epoch_chunk', EPOCH_CHUNK), max_iters - done)
+            chunk = min(epoch_chunk, max_iters - done)
             if perms is not None:
                 perm = torch.as_tensor(perms[done:done + chunk])
             else:  # DataLoader(shuffle=True): a fresh permutation per epoch (trainer.py:185)
