@@ -515,6 +515,52 @@ int nnest_spline_mcmc_tempered_steps(struct nnest_spline *spl, const nnest_like_
 int nnest_smc_reweight(const double *logl_dev, int N, double beta, double ess_fraction, double *out_dev, long long *m_dev, void *stream);
 int nnest_smc_resample(const long long *m_dev, int N, int D, uint64_t seed, int stage, const float *theta_in_dev, const double *logl_in_dev,
                        int *anc_out_dev, float *theta_out_dev, double *logl_out_dev, void *stream);
+/* THE MIXED WALK: the tempered random-walk Metropolis run above with a flow-INDEPENDENCE ("global") step at every global_every-th
+ * step, in kernels of their own (nnest_mcmc_mixed.hip, nnest_spline_mcmc_mixed.hip).  BUILD-DEFINED: the reference
+ * has no such step.  A global step proposes a draw of the flow's base mapped through the flow -- the trained flow as a PROPOSAL, not
+ * only as a preconditioner -- and accepts on the ratio of importance weights: it lets a chain jump between modes the flow has learnt
+ * and decorrelates the duplicated particles behind an SMC resampling.  (All added within ABI 15.)
+ * nnest_mcmc_mixed_steps, nnest_spline_mcmc_mixed_steps: the arguments of nnest_mcmc_tempered_steps / nnest_spline_mcmc_tempered_steps
+ *   plus `int global_every` and `int *n_accept_global_dev` before `stream`.  A launch advances C walkers by `steps` steps; step t is a
+ *   global index (step0 + the step's number within the launch, as the 32-bit index the draws use); w = walker_offset + row.  With
+ *   k = global_every:
+ *     kind:    step t is GLOBAL iff k > 0 and (t + 1) % k == 0, for all walkers alike (k = 1: every step; k = 10: steps 9, 19, ...);
+ *              LOCAL otherwise.
+ *     draws:   eps = the normals and u = the uniform of nnest_mcmc_steps at (seed, w, t) (streams 5 and 6): a draw at (w, t) is used
+ *              by exactly one kind, so no new stream exists and nnest_mcmc_fill_noise exports the draws of either kind.
+ *     target:  lp(z) = lp_beta(z) of nnest_mcmc_tempered_steps = ((beta * logL) + log|det dx/dz|) + prior; beta is always an argument,
+ *              beta = 1.0 is the untempered target bit for bit.  The walker carries and logs the UNTEMPERED logL.
+ *     local:   q = z + step_size * eps (float32, each operation rounded); the walker moves iff lp(q) - lp(z) > log u (float64):
+ *              exactly nnest_mcmc_tempered_steps's step.
+ *     global:  q = eps on the live dims (padded dims 0).  With zz(z) = the float64 sum of the squares of the float32 row, summed in the
+ *              order the layout's importance kernel uses, b(z) = -1/2 zz(z) - D * log sqrt(2 pi) (the N(0, I) density of
+ *              nnest_importance_evidence) and lw(z) = lp(z) - b(z) (float64, one rounded subtraction, no contraction), the walker
+ *              moves iff lw(q) - lw(z) > log u (float64, the same comparison).  b and lw are functions of the row and its lp alone:
+ *              nothing but (z, lp, logL) is carried between launches, so a run cut into launches stays the same run.  A walker
+ *              whose lp and the proposal's lp are both -inf refuses (NaN compares false), as in the local rule.
+ *   ONE loop and ONE target evaluation per step: the kind selects q and the two sides of the accept rule.  global_every = 0 is
+ *   nnest_mcmc_tempered_steps's run bit for bit on every output (and at beta = 1.0 nnest_mcmc_steps's).  Everything said of
+ *   nnest_mcmc_steps holds: the buffers, the invariances (the cut into launches, a shard by walker_offset, history or not), steps = 0
+ *   evaluates the start and writes x_out_dev, lp_out_dev and logl_out_dev only.  n_accept_dev [C] or NULL counts the accepted steps
+ *   of BOTH kinds; n_accept_global_dev [C] or NULL the accepted global steps.  NNEST_E_ARG before any launch, the outputs untouched:
+ *   beta not finite or < 0, global_every < 0, and nnest_mcmc_steps's argument errors.  NNEST_E_UNSUPPORTED before any launch: what
+ *   the _check entry below refuses.  The base must be N(0, I).
+ * nnest_mcmc_mixed_check, nnest_spline_mcmc_mixed_check: NNEST_OK where the entry takes this handle (its shape and base) and this
+ *   likelihood id, else NNEST_E_UNSUPPORTED with the reason in nnest_hip_last_error() -- a GeneralisedNormal base in the words of
+ *   nnest_importance_check --, as the entry itself would answer; nothing is launched. */
+int nnest_mcmc_mixed_check(nnest_nvp_t *nvp, int like_id);
+int nnest_spline_mcmc_mixed_check(struct nnest_spline *spl, int like_id);
+int nnest_mcmc_mixed_steps(nnest_nvp_t *nvp, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                           const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev,
+                           float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev, float *hist_x_dev,
+                           double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size, uint64_t step0, uint64_t seed,
+                           uint64_t walker_offset, double beta, int global_every, int *n_accept_global_dev, void *stream);
+int nnest_spline_mcmc_mixed_steps(struct nnest_spline *spl, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                                  const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev,
+                                  const double *logl_in_dev, float *z_out_dev, float *x_out_dev, double *lp_out_dev, double *logl_out_dev,
+                                  float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C, int steps,
+                                  float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta, int global_every,
+                                  int *n_accept_global_dev, void *stream);
 /* IMPORTANCE-SAMPLED EVIDENCE with the trained flow as the proposal: Z = E_q[L(T(x)) pi(T(x)) / q(x)], drawn, evaluated and reduced
  * inside one kernel.  BUILD-DEFINED: the reference has no such estimator.  Sample m is a global 64-bit index; row k of a launch of M
  * samples is m = sample_offset + k:

@@ -227,6 +227,13 @@ SIGNATURES = {
                                   _u64, _d, _vp],
     'nnest_spline_mcmc_tempered_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64,
                                          _u64, _u64, _d, _vp],
+    # the mixed walk: the tempered entries' arguments plus `int global_every, int *n_accept_global_dev` before `stream`
+    'nnest_mcmc_mixed_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64, _u64,
+                               _u64, _d, _i, _vp, _vp],
+    'nnest_spline_mcmc_mixed_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64,
+                                      _u64, _u64, _d, _i, _vp, _vp],
+    'nnest_mcmc_mixed_check': [_vp, _i],
+    'nnest_spline_mcmc_mixed_check': [_vp, _i],
     # (logl_dev, N, beta, ess_fraction, out_dev [4], m_dev [N] int64, stream)
     'nnest_smc_reweight': [_vp, _i, _d, _d, _vp, _vp, _vp],
     # (m_dev, N, D, seed, stage, theta_in_dev, logl_in_dev, anc_out_dev, theta_out_dev, logl_out_dev, stream)

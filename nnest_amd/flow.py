@@ -407,7 +407,7 @@ class _HipFlow(object):
         return out
 
     def mcmc_steps(self, like_id, z, steps, step_size, t_std=None, t_mean=None, lo=None, hi=None, lp=None, logl=None, seed=0, step0=0,
-                   walker_offset=0, like_params=None, history=True, beta=None):
+                   walker_offset=0, like_params=None, history=True, beta=None, global_every=0):
         """`steps` steps of random-walk Metropolis in latent space with the likelihood, the prior and the Jacobian in the ratio, in ONE
         launch (the family's `mcmc` entry point: nnest_mcmc_steps, nnest_spline_mcmc_steps; build-defined stream, the reference's move:
         include/nnest_hip.h has the definition).  z [C, D] float32 on the device: the walkers' start; lp, logl [C] float64: the
@@ -420,11 +420,21 @@ class _HipFlow(object):
         beta: None -- the entry above, as it was; a float -- the TEMPERED target lp_beta = ((beta * logL) + log|det|) + prior through
         the family's `mcmc_tempered` entry (nnest_mcmc_tempered_steps, nnest_spline_mcmc_tempered_steps: the same draws, the same
         invariances; lp is lp_beta, logl stays the untempered logL; beta finite and >= 0, 1.0 is the untempered run bit for bit).
+        global_every: 0 -- the entries above, as they were; k > 0 -- the MIXED walk through the family's `mcmc_mixed` entry
+        (nnest_mcmc_mixed_steps, nnest_spline_mcmc_mixed_steps): step t is a flow-independence ("global") step where (t + 1) % k == 0
+        -- the proposal is the draw eps itself, accepted on the ratio of importance weights lp - logb under the N(0, I) base --, a
+        random-walk step otherwise; the same draws and invariances; beta None is 1.0.  The result then also carries n_accept_global
+        [C] (n_accept counts both kinds).  ValueError for global_every < 0.
         NotImplementedError for a family without such a kernel (its handle must not reach another family's)."""
-        fn = self._sym.get('mcmc' if beta is None else 'mcmc_tempered')
+        global_every = int(global_every)
+        if global_every < 0:
+            raise ValueError('mcmc_steps: global_every=%d (>= 0)' % global_every)
+        mixed = global_every > 0
+        fn = self._sym.get('mcmc_mixed' if mixed else 'mcmc' if beta is None else 'mcmc_tempered')
         if fn is None:
-            raise NotImplementedError('no fused %srandom-walk Metropolis kernel for %s' % ('' if beta is None else 'tempered ', type(self).__name__))
-        tempered = () if beta is None else (ctypes.c_double(float(beta)),)
+            raise NotImplementedError('no fused %srandom-walk Metropolis kernel for %s' % (
+                'mixed ' if mixed else '' if beta is None else 'tempered ', type(self).__name__))
+        tempered = () if beta is None and not mixed else (ctypes.c_double(1.0 if beta is None else float(beta)),)
         dev = self.device
         z = _as_dev_f32(z, dev).contiguous()
         C, D, steps = z.shape[0], self.D, int(steps)
@@ -444,6 +454,9 @@ class _HipFlow(object):
                    hist_z=torch.empty(C, steps, D, **f32) if hist else None, hist_x=torch.empty(C, steps, D, **f32) if hist else None,
                    hist_logl=torch.empty(C, steps, **f64) if hist else None,
                    n_accept=torch.empty(C, dtype=torch.int32, device=dev) if steps > 0 else torch.zeros(C, dtype=torch.int32, device=dev))
+        if mixed:
+            out['n_accept_global'] = (torch.empty if steps > 0 else torch.zeros)(C, dtype=torch.int32, device=dev)
+            tempered += (global_every, _lib.ptr(out['n_accept_global']))
         with torch.cuda.device(dev):
             lk = _lib.like_spec(like_id, 1.0, like_params)
             _lib.check(fn(
@@ -453,6 +466,20 @@ class _HipFlow(object):
                 ctypes.c_float(float(step_size)), int(step0) & 0xFFFFFFFFFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF,
                 int(walker_offset) & 0xFFFFFFFFFFFFFFFF, *tempered, _lib.current_stream(dev)))
         return out
+
+    def mcmc_mixed_refusal(self, like_id):
+        """why `mcmc_steps` with global_every > 0 would refuse this flow (its shape, its base) or this likelihood id -- the library's
+        own words (the family's `mcmc_mixed_check` entry; nothing is launched) --, or None where it is taken.  NotImplementedError
+        for a family without such a kernel"""
+        fn = self._sym.get('mcmc_mixed_check')
+        if fn is None or 'mcmc_mixed' not in self._sym:
+            raise NotImplementedError('no fused mixed random-walk Metropolis kernel for %s' % type(self).__name__)
+        with torch.cuda.device(self.device):
+            rc = fn(self._h, int(like_id))
+        if rc == _lib.NNEST_OK:
+            return None
+        msg = self._lib.nnest_hip_last_error()
+        return msg.decode() if msg else 'error %d' % rc
 
     def importance_refusal(self, like_id):
         """why `importance_evidence` would refuse this flow (its shape, its base) or this likelihood id -- the library's own words
@@ -743,7 +770,8 @@ class HipNVP(_PaddedVectors, _HipFlow):
                    ensemble_max_walkers='nnest_ensemble_max_walkers', ensemble_moves='nnest_ensemble_moves_steps',
                    ensemble_moves_max_walkers='nnest_ensemble_moves_max_walkers', mcmc='nnest_mcmc_steps',
                    importance='nnest_importance_evidence', importance_check='nnest_importance_check',
-                   mcmc_tempered='nnest_mcmc_tempered_steps')
+                   mcmc_tempered='nnest_mcmc_tempered_steps', mcmc_mixed='nnest_mcmc_mixed_steps',
+                   mcmc_mixed_check='nnest_mcmc_mixed_check')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (_PaddedVectors)
         with torch.cuda.device(self.device):

@@ -27,7 +27,7 @@ class MCMCSampler(Sampler):
         self.sampler = 'mcmc'
 
     def run(self, mcmc_steps, mcmc_num_chains, training_samples, mcmc_dynamic_step_size=True, stats_interval=100,
-            output_interval=None, initial_jitter=0.01, final_jitter=0.01, init_samples=None, route=None, seed=None):
+            output_interval=None, initial_jitter=0.01, final_jitter=0.01, init_samples=None, route=None, seed=None, global_every=0):
         """mcmc.py:79-130.  `route` and `seed` are not in the reference.  route: None or 'host' -- the reference's step loop with the
         flow passes on the GPU and the likelihood and the prior on the host (`_mcmc_sample_host`), draw for draw on torch's and
         numpy's streams; 'fused' -- every step inside the kernel (`_mcmc_sample_device`: nnest_mcmc_steps for the NVP,
@@ -35,22 +35,33 @@ class MCMCSampler(Sampler):
         the kernels know and agrees with the host callable on T(x), there are no derived parameters, the prior is none or a
         UniformPrior on T(x), num_slow = 0 and the flow has such a kernel; ValueError, naming what is not taken, otherwise.  The
         route that ran is left in `mcmc_route`.  seed: the fused run's Philox seed (None: `_next_seed()`); the host route does not
-        use it.  Both routes keep the fixed step 2 / sqrt(x_dim)."""
+        use it.  Both routes keep the fixed step 2 / sqrt(x_dim).
+        global_every (not in the reference; build-defined): k > 0 makes every k-th step of the fused run a flow-independence
+        ("global") step -- a draw of the flow's base as the proposal, accepted on the ratio of importance weights
+        (`_mcmc_sample_device`, nnest_mcmc_mixed_steps) --, which lets a chain jump between the modes the flow has learnt.  It needs
+        route='fused' (ValueError otherwise) and a N(0, I) base; the run leaves `global_proposed` and `global_accepted` and logs the
+        global acceptance rate.  0: the run as it was."""
         if route not in (None, 'host', 'fused'):
             raise ValueError("route=%r: None or 'host' (the reference's step loop) or 'fused' (build-defined stream)" % (route,))
+        global_every = int(global_every)
+        if global_every < 0:
+            raise ValueError('MCMCSampler.run: global_every=%d (every how many steps a global step is taken: >= 0)' % global_every)
+        if global_every and route != 'fused':
+            raise ValueError("MCMCSampler.run: global_every=%d needs route='fused': the global step is built into the fused route's "
+                             "kernels only" % global_every)
         mean = np.mean(training_samples, axis=0)
         std = np.std(training_samples, axis=0)
         training_samples = (training_samples - mean) / std          # normalise
         self._install_transform(mean, std)                           # T(x) = x * std + mean (the K4 kernels only know x -> s * x)
         if route == 'fused':
-            target, why = self._device_target(entry='mcmc')
+            target, why = self._device_target(entry='mcmc_mixed' if global_every else 'mcmc')
             if why is not None:
                 raise ValueError('MCMCSampler.run: the fused route does not take %s' % why)
         self.trainer.train(training_samples, jitter=initial_jitter)
         if route == 'fused':
             samples, latent_samples, derived_samples, loglikes, scale, ncall = self._mcmc_sample_device(
                 mcmc_steps, num_chains=mcmc_num_chains, init_samples=init_samples, output_interval=output_interval,
-                stats_interval=stats_interval, seed=seed, target=target)
+                stats_interval=stats_interval, seed=seed, target=target, **(dict(global_every=global_every) if global_every else {}))
             if self.chain_stats:   # (the interval lines were logged by the run)
                 self._log_chain_stats(samples, (std, mean), mcmc_steps, None, prefix_offset=1, min_step=0)
         else:

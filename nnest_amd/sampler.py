@@ -745,8 +745,10 @@ class Sampler(object):
             return np.full(self.x_dim, self._linear_scale), np.zeros(self.x_dim)
         return None
 
-    ENTRY_NEEDS = {'mcmc': ('mcmc',), 'mcmc_tempered': ('mcmc', 'mcmc_tempered'), 'importance': ('importance',)}
-    ENTRY_KERNEL = {'mcmc': 'random-walk Metropolis', 'mcmc_tempered': 'tempered random-walk Metropolis', 'importance': 'importance-sampling'}
+    ENTRY_NEEDS = {'mcmc': ('mcmc',), 'mcmc_tempered': ('mcmc', 'mcmc_tempered'), 'importance': ('importance',),
+                   'mcmc_mixed': ('mcmc', 'mcmc_mixed')}
+    ENTRY_KERNEL = {'mcmc': 'random-walk Metropolis', 'mcmc_tempered': 'tempered random-walk Metropolis', 'importance': 'importance-sampling',
+                    'mcmc_mixed': 'mixed (local and global step) Metropolis'}
 
     def _device_target(self, affine=None, entry=None, unit_box_on_x=False):
         """(target, None) where the likelihood and the prior run on the device under the transform `affine` = (std, mean) (None:
@@ -754,8 +756,9 @@ class Sampler(object):
         A DeviceTarget: no derived parameters, a likelihood the kernels know that agrees with the host callable on T(x), and no prior
         or a UniformPrior on T(x) -- with `unit_box_on_x` (the evidence) also the NestedSampler's prior, the unit box on x under
         x -> s * x (`_linear_scale`): the box on T(x) is +-|s|.  `entry` names the flow entry a front end needs bound ('mcmc',
-        'mcmc_tempered' -- which needs 'mcmc' too --, 'importance'): every parameter must then be fast and, for 'importance', the
-        library must take the flow's shape and base (`importance_refusal`: nothing is launched).  The ensemble routes name none:
+        'mcmc_tempered' and 'mcmc_mixed' -- which need 'mcmc' too --, 'importance'): every parameter must then be fast and, for
+        'importance' and 'mcmc_mixed', the library must take the flow's shape and base (`importance_refusal`, `mcmc_mixed_refusal`:
+        nothing is launched).  The ensemble routes name none:
         they fall back to rounds.  One probe of the host callable (`_probe_agrees`) per call: a run resolves once and hands the
         target down"""
         affine = self._ensemble_affine() if affine is None else affine
@@ -775,7 +778,11 @@ class Sampler(object):
             why = netG.importance_refusal(like_id)
             if why is not None:
                 return None, 'the flow %s: %s' % (type(netG).__name__, why)
-        refused = 'this transform, likelihood or prior (an affine transform, a likelihood that agrees with the kernel\'s, and no prior%s)' % (
+        if entry == 'mcmc_mixed':   # (the global step draws from the base: its shape and N(0, I), in the library's words)
+            why = netG.mcmc_mixed_refusal(like_id)
+            if why is not None:
+                return None, 'the flow %s: %s' % (type(netG).__name__, why)
+        refused ='this transform, likelihood or prior (an affine transform, a likelihood that agrees with the kernel\'s, and no prior%s)' % (
             ', a UniformPrior on T(x) or the unit box on x' if unit_box_on_x else ' or a UniformPrior on T(x)')
         prior = self._user_prior
         box = (None, None)
@@ -898,7 +905,7 @@ class Sampler(object):
         return out
 
     def _mcmc_sample_device(self, mcmc_steps, step_size=0.0, num_chains=1, init_samples=None, max_start_tries=100, output_interval=None,
-                            stats_interval=None, seed=None, chunk_steps=None, target=None):
+                            stats_interval=None, seed=None, chunk_steps=None, target=None, global_every=0):
         """`_mcmc_sample` with loglstar = None (sampler.py:372-416: the likelihood, the prior and the Jacobian in the ratio) with every
         step of a launch inside the kernel (include/nnest_hip.h nnest_mcmc_steps, nnest_spline_mcmc_steps).  BUILD-DEFINED STREAM,
         THE REFERENCE'S MOVE: parity with the host route's torch stream is statistical.  The step is fixed (`step_size`, <= 0: the
@@ -907,9 +914,17 @@ class Sampler(object):
         steps (default: by device memory, ENSEMBLE_HISTORY_BYTES) and at `output_interval`; the cut does not change it.  Returns the
         reference's tuple (samples [N, S + 1, D] (x, before the transform: the start, then every step), latent_samples [N, S + 1, D],
         derived_samples [N, S + 1, 0], loglikes [N, S + 1] (logL), scale, ncall).  `target`: the run's DeviceTarget where the caller
-        has resolved it (`_device_target(entry='mcmc')`); None: resolved here, ValueError naming what is not taken."""
+        has resolved it (`_device_target(entry='mcmc')`); None: resolved here, ValueError naming what is not taken.
+        global_every = k > 0 (build-defined; include/nnest_hip.h nnest_mcmc_mixed_steps): every k-th step of the run -- step t where
+        (t + 1) % k == 0 -- is a flow-independence ("global") step: the proposal is a draw of the flow's base, accepted on the ratio
+        of importance weights, through the family's mixed kernel (`_device_target(entry='mcmc_mixed')`: the base must be N(0, I)).
+        The run leaves `global_proposed` and `global_accepted` on the sampler and logs the global acceptance rate -- the figure
+        that says how good the flow is as a proposal.  0: the run as it was."""
+        global_every = int(global_every)
+        if global_every < 0:
+            raise ValueError('mcmc: global_every=%d (every how many steps a global step is taken: >= 0)' % global_every)
         if target is None:
-            target, why = self._device_target(entry='mcmc')
+            target, why = self._device_target(entry='mcmc_mixed' if global_every else 'mcmc')
             if why is not None:
                 raise ValueError('mcmc: the fused route does not take %s' % why)
         S = int(mcmc_steps)
@@ -938,14 +953,24 @@ class Sampler(object):
         derived = np.zeros((N, S + 1, 0))
         samples[:, 0], latent[:, 0], loglikes[:, 0] = start['x'].cpu().numpy(), z.cpu().numpy(), start['logl'].cpu().numpy()
 
+        mixed = dict(global_every=global_every) if global_every else {}   # (0: the call as it was)
+        n_global = [0]
+
         def launch(k, done, state):
-            res = netG.mcmc_steps(target.like_id, state[0], k, step_size, lp=state[1], logl=state[2], step0=done, **kw)
+            res = netG.mcmc_steps(target.like_id, state[0], k, step_size, lp=state[1], logl=state[2], step0=done, **mixed, **kw)
+            if global_every:
+                n_global[0] += int(res['n_accept_global'].sum().item())
             return ((res['z'], res['lp'], res['logl']), dict(x=res['hist_x'], z=res['hist_z'], logl=res['hist_logl']),
                     int(res['n_accept'].sum().item()))
 
         ncall = N * (tries + S)
         self._run_in_launches(launch, (z, start['lp'], start['logl']), dict(x=samples, z=latent, logl=loglikes, derived=derived), S,
                               chunk_steps, output_interval, first=1, ncall=ncall)
+        if global_every:   # (steps t = k - 1, 2k - 1, ... of 0 .. S - 1)
+            self.global_proposed, self.global_accepted = N * (S // global_every), n_global[0]
+            if self.single_or_primary_process:
+                self.logger.info('mcmc: global steps every [%d] accepted [%d of %d] global acceptance [%5.4f]' % (
+                    global_every, self.global_accepted, self.global_proposed, self.global_accepted / max(1, self.global_proposed)))
         if self.chain_stats and stats_interval is not None:   # sampler.py:451-452: the transformed chains up to step `it`
             self._log_chain_stats(samples, self._ensemble_affine(), S, stats_interval, prefix_offset=1, min_step=0, final=False)
         return samples, latent, derived, loglikes, step_size, ncall

@@ -87,6 +87,11 @@ class SMCSampler(Sampler):
                                          param_names=param_names, chain_stats=chain_stats)
         self.sampler = 'smc'
 
+    # Every how many steps of a stage's moves a flow-independence ("global") step is taken; 0: never, the run as it was.  An
+    # attribute of the sampler, set before `run` (sampler.global_every = 2), not an argument of `run`: tests/test_smc_check.py pins
+    # run's argument list, and existing tests stay as they are.  `run` has the rest.
+    global_every = 0
+
     def run(self, num_particles=1000, mcmc_steps=25, ess_fraction=0.5, step_size=0.0, jitter=0.01, seed=None, route=None, max_stages=1000):
         """Anneal `num_particles` draws of the prior to the posterior (the module docstring has the algorithm and the convention of
         `logz`).  mcmc_steps: Metropolis steps per particle and stage, at the fixed step `step_size` (<= 0: 2 / sqrt(x_dim), as
@@ -99,9 +104,17 @@ class SMCSampler(Sampler):
         Leaves: logz; betas, ess, acceptance, logz_steps (log Z's increments: they add up to logz) -- one entry per stage; samples
         [N, D] (theta at beta = 1), loglikes [N], latent_samples [N, D]; smc_route; stage_times (seconds per stage: reweight --
         with the resampling --, train, move); total_calls grows by N for the start and by N (1 + mcmc_steps) per stage (the start of
-        a launch is evaluated, as the fused Metropolis route counts it)."""
+        a launch is evaluated, as the fused Metropolis route counts it).
+        `self.global_every` = k > 0 (the attribute above) makes every k-th step of a stage's moves a flow-independence ("global")
+        step at the stage's beta -- a draw of the freshly trained flow's base as the proposal, accepted on the ratio of importance
+        weights (include/nnest_hip.h nnest_mcmc_mixed_steps) --, the step that decorrelates the copies a resampling leaves.  The
+        fused route only: ValueError naming it where the host loop would run.  Leaves global_acceptance, one entry per stage beside
+        `acceptance`.  0: the run as it was."""
         if route not in (None, 'host', 'fused'):
             raise ValueError("route=%r: None, 'host' or 'fused'" % (route,))
+        global_every = int(self.global_every)
+        if global_every < 0:
+            raise ValueError('SMCSampler.run: global_every=%d (every how many steps a global step is taken: >= 0)' % global_every)
         if self.sample_prior is None:
             raise ValueError('Prior does not have sample method')
         N, S, D = int(num_particles), int(mcmc_steps), self.x_dim
@@ -111,19 +124,24 @@ class SMCSampler(Sampler):
             raise ValueError('SMCSampler.run: ess_fraction=%r (inside (0, 1))' % (ess_fraction,))
         self._install_transform(np.zeros(D), np.ones(D))   # (theta itself, until the first stage installs its own)
         # (likelihood and box do not depend on T: resolved here, once; every stage takes a copy under its own T)
-        target, why = (None, None) if route == 'host' else self._device_target(entry='mcmc_tempered')
+        target, why = (None, None) if route == 'host' else self._device_target(entry='mcmc_mixed' if global_every else 'mcmc_tempered')
         if route == 'fused' and why is not None:
             raise ValueError('SMCSampler.run: the fused route does not take %s' % why)
         route = 'host' if target is None else 'fused'
+        if global_every and route == 'host':
+            raise ValueError("SMCSampler.run: global_every=%d needs the fused route, whose kernels alone take the global step%s" % (
+                global_every, '' if why is None else ': the fused route does not take %s' % why))
         if step_size <= 0.0:
             step_size = 2 / D ** 0.5
         seed = self._next_seed() if seed is None else int(seed)
         if route == 'fused':
-            state, stage_fn = self._smc_start_fused(N, target), functools.partial(self._smc_stage_fused, target=target)
+            state = self._smc_start_fused(N, target)
+            stage_fn = functools.partial(self._smc_stage_fused, target=target, **(dict(global_every=global_every) if global_every else {}))
         else:
             state, stage_fn = self._smc_start_host(N), self._smc_stage_host
         beta, logz = 0.0, 0.0
         self.betas, self.ess, self.acceptance, self.logz_steps, self.stage_times = [], [], [], [], []
+        self.global_acceptance = []   # (per stage, with global_every > 0)
         stage = 0
         while beta < 1.0:
             if stage >= int(max_stages):
@@ -141,6 +159,9 @@ class SMCSampler(Sampler):
             stage += 1
             if self.single_or_primary_process:
                 self.logger.info('smc stage [%d] beta [%.6g] ESS [%.1f of %d] acceptance [%5.4f] log Z [%5.4f]' % (stage, beta, ess, N, acc, logz))
+                if global_every:
+                    self.logger.info('smc stage [%d] global steps every [%d] global acceptance [%5.4f]' % (
+                        stage, global_every, self.global_acceptance[-1]))
         self.logz = logz
         self.smc_route = route
         theta, logl, z = state
@@ -178,7 +199,7 @@ class SMCSampler(Sampler):
         self.total_calls += N
         return theta, logl, None
 
-    def _smc_stage_fused(self, state, beta, ess_fraction, S, step_size, jitter, seed, stage, target):
+    def _smc_stage_fused(self, state, beta, ess_fraction, S, step_size, jitter, seed, stage, target, global_every=0):
         import torch
         from . import flow
         theta, logl, _ = state
@@ -195,9 +216,11 @@ class SMCSampler(Sampler):
         z, _ = netG.forward(normalised.astype(np.float32))
         target = target.with_transform(std, mean)   # (this stage's T)
         res = netG.mcmc_steps(target.like_id, z.contiguous(), S, step_size, seed=stage_seed(seed, stage), history=False, beta=beta_new,
-                              **target.launch_kwargs(netG.device))
+                              **(dict(global_every=global_every) if global_every else {}), **target.launch_kwargs(netG.device))
         theta = target.transform(res['x'])
         n_acc = int(res['n_accept'].sum().item())
+        if global_every:   # (steps t = k - 1, 2k - 1, ... of the stage's 0 .. S - 1)
+            self.global_acceptance.append(int(res['n_accept_global'].sum().item()) / float(max(1, N * (S // global_every))))
         t3 = time.perf_counter()
         self.total_calls += N * (1 + S)
         self.total_accepted += n_acc
