@@ -561,6 +561,54 @@ int nnest_spline_mcmc_mixed_steps(struct nnest_spline *spl, const nnest_like_t *
                                   float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C, int steps,
                                   float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta, int global_every,
                                   int *n_accept_global_dev, void *stream);
+/* THE ADAPTIVE WALK: the mixed walk above with the step of the local proposal adapted PER WALKER, in kernels of their own
+ * (nnest_mcmc_adapt.hip, nnest_spline_mcmc_adapt.hip).  BUILD-DEFINED: the reference's mcmc_dynamic_step_size is a
+ * batch-wide rule, and its MCMCSampler never forwards it.  (All added within ABI 15.)
+ * nnest_mcmc_adapt_steps, nnest_spline_mcmc_adapt_steps: the arguments of nnest_mcmc_mixed_steps / nnest_spline_mcmc_mixed_steps up to
+ *   n_accept_global_dev, then `const double *step_in_dev, double *step_out_dev, double *hist_step_dev, uint32_t adapt_steps,
+ *   double adapt_rate, double target_accept` before `stream`.  Kind, draws, target and the accept rule of a step are the mixed
+ *   walk's.  Every walker carries a float64 `sigma`:
+ *     start:   sigma = min(max(step_in_dev[row], NNEST_ADAPT_STEP_MIN), NNEST_ADAPT_STEP_MAX) with step_in_dev given (the max and
+ *              the min each keep their second operand where the comparison is false: a NaN loads as NNEST_ADAPT_STEP_MIN), else
+ *              (double)step_size.
+ *     local:   q = z + (float)sigma * eps (float32, each operation rounded: the mixed walk's proposal at the float32 rounding of the
+ *              walker's own sigma); the walker moves iff lp(q) - lp(z) > log u.  After the decision acc, iff t < adapt_steps:
+ *                g     = adapt_rate / sqrt((double)t + 1.0)
+ *                sigma = sigma * (1.0 + g * ((acc ? 1.0 : 0.0) - target_accept))
+ *                sigma = min(max(sigma, NNEST_ADAPT_STEP_MIN), NNEST_ADAPT_STEP_MAX)
+ *              in float64, each operation rounded, no contraction; division and square root are correctly rounded.  The update
+ *              uses the BINARY decision, not the acceptance probability: no transcendental enters, and the rule replayed from the
+ *              decisions reproduces sigma to the bit.  A refusal because both sides are -inf counts as a rejection.
+ *     global:  the mixed walk's step; it uses no step and leaves sigma alone.
+ *     frozen:  a step with t >= adapt_steps leaves sigma alone: from there on each chain is a Metropolis chain at a fixed step.
+ *   The run stays a function of (seed, w, t) and the start alone; the state carried between launches is (z, lp, logL, sigma), so a
+ *   run cut into launches with step_out_dev handed to step_in_dev is the same run, and the invariances of nnest_mcmc_steps hold.
+ *   adapt_steps = 0 with step_in_dev NULL is nnest_mcmc_mixed_steps's run bit for bit; adapt_steps = 0 with step_in_dev given runs
+ *   every walker at its own fixed step.  step_in_dev [C] or NULL; step_out_dev [C] or NULL, written iff steps > 0, as z_out_dev is;
+ *   hist_step_dev [C, steps] or NULL, independent of the history trio: sigma after each step, global steps included.  The other
+ *   buffers and counters are the mixed entry's.  NNEST_E_ARG before any launch, the outputs untouched: adapt_rate not finite or
+ *   outside [0, 1], target_accept not strictly inside (0, 1) -- with these the factor stays inside (0, 2) --, and the mixed entry's
+ *   argument errors.  NNEST_E_UNSUPPORTED before any launch: what the _check entry below refuses.
+ * nnest_mcmc_adapt_check, nnest_spline_mcmc_adapt_check: as nnest_mcmc_mixed_check / nnest_spline_mcmc_mixed_check answer; nothing is
+ *   launched. */
+#define NNEST_ADAPT_STEP_MIN 1e-8
+#define NNEST_ADAPT_STEP_MAX 1e2
+int nnest_mcmc_adapt_check(nnest_nvp_t *nvp, int like_id);
+int nnest_spline_mcmc_adapt_check(struct nnest_spline *spl, int like_id);
+int nnest_mcmc_adapt_steps(nnest_nvp_t *nvp, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                           const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev,
+                           float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev, float *hist_x_dev,
+                           double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size, uint64_t step0, uint64_t seed,
+                           uint64_t walker_offset, double beta, int global_every, int *n_accept_global_dev, const double *step_in_dev,
+                           double *step_out_dev, double *hist_step_dev, uint32_t adapt_steps, double adapt_rate, double target_accept,
+                           void *stream);
+int nnest_spline_mcmc_adapt_steps(struct nnest_spline *spl, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                                  const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev,
+                                  const double *logl_in_dev, float *z_out_dev, float *x_out_dev, double *lp_out_dev, double *logl_out_dev,
+                                  float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C, int steps,
+                                  float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta, int global_every,
+                                  int *n_accept_global_dev, const double *step_in_dev, double *step_out_dev, double *hist_step_dev,
+                                  uint32_t adapt_steps, double adapt_rate, double target_accept, void *stream);
 /* IMPORTANCE-SAMPLED EVIDENCE with the trained flow as the proposal: Z = E_q[L(T(x)) pi(T(x)) / q(x)], drawn, evaluated and reduced
  * inside one kernel.  BUILD-DEFINED: the reference has no such estimator.  Sample m is a global 64-bit index; row k of a launch of M
  * samples is m = sample_offset + k:

@@ -114,6 +114,7 @@ _i = ctypes.c_int
 _f = ctypes.c_float
 _d = ctypes.c_double
 _u64 = ctypes.c_uint64
+_u32 = ctypes.c_uint32
 
 # name -> argtypes; every entry point include/nnest_hip.h declares (checked by tests/test_abi.py)
 SIGNATURES = {
@@ -234,6 +235,14 @@ SIGNATURES = {
                                       _u64, _u64, _d, _i, _vp, _vp],
     'nnest_mcmc_mixed_check': [_vp, _i],
     'nnest_spline_mcmc_mixed_check': [_vp, _i],
+    # the adaptive walk: the mixed entries' arguments up to n_accept_global_dev, then `const double *step_in_dev, double *step_out_dev,
+    # double *hist_step_dev, uint32_t adapt_steps, double adapt_rate, double target_accept` before `stream`
+    'nnest_mcmc_adapt_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64, _u64,
+                               _u64, _d, _i, _vp, _vp, _vp, _vp, _u32, _d, _d, _vp],
+    'nnest_spline_mcmc_adapt_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64,
+                                      _u64, _u64, _d, _i, _vp, _vp, _vp, _vp, _u32, _d, _d, _vp],
+    'nnest_mcmc_adapt_check': [_vp, _i],
+    'nnest_spline_mcmc_adapt_check': [_vp, _i],
     # (logl_dev, N, beta, ess_fraction, out_dev [4], m_dev [N] int64, stream)
     'nnest_smc_reweight': [_vp, _i, _d, _d, _vp, _vp, _vp],
     # (m_dev, N, D, seed, stage, theta_in_dev, logl_in_dev, anc_out_dev, theta_out_dev, logl_out_dev, stream)

@@ -11,6 +11,7 @@
 #include "mcmc_walk.h"
 #include "importance_walk.h"
 #include "mcmc_mixed.h"
+#include "mcmc_adapt.h"
 
 using namespace nnest;
 
@@ -437,6 +438,13 @@ int nnest::mcmc_mixed_every_ok(int global_every) {
         return fail(NNEST_E_ARG, "mcmc mixed: global_every=%d (every how many steps a global step is taken: >= 0, 0: never)", global_every);
     return NNEST_OK;
 }
+int nnest::mcmc_adapt_rule_ok(double adapt_rate, double target_accept) {
+    if (!isfinite(adapt_rate) || adapt_rate < 0.0 || adapt_rate > 1.0)
+        return fail(NNEST_E_ARG, "mcmc adapt: adapt_rate=%g (the gain of the step-size rule: finite, in [0, 1])", adapt_rate);
+    if (!(target_accept > 0.0 && target_accept < 1.0))
+        return fail(NNEST_E_ARG, "mcmc adapt: target_accept=%g (the acceptance the rule aims at: strictly inside (0, 1))", target_accept);
+    return NNEST_OK;
+}
 int nnest::importance_args(ImpArgs *a, const float *t_std, const float *t_mean, const float *lo, const float *hi, float *z_out, float *x_out,
                            double *logl_out, double *logw_out, double *partials, double *sums, int M, uint64_t seed, uint64_t sample_offset) {
     if (M < 0 || M > (1 << 30)) return fail(NNEST_E_ARG, "importance: M=%d (0 .. 2^30 samples a launch)", M);
@@ -597,6 +605,56 @@ int nnest_mcmc_mixed_steps(nnest_nvp_t *h, const nnest_like_t *like, const float
     hipError_t e = launch_mcmc_mixed(h->s, h->w, a, (hipStream_t)stream);
     if (e == hipErrorInvalidConfiguration) return fail(NNEST_E_UNSUPPORTED, "mcmc mixed: x_dim=%d not instantiated", h->s.D);
     if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_mcmc_mixed: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+// what nnest_mcmc_adapt_steps takes, asked before a launch (and by the entry itself): as nnest_mcmc_mixed_check answers
+int nnest_mcmc_adapt_check(nnest_nvp_t *h, int like_id) {
+    if (!h) return fail(NNEST_E_ARG, "NULL handle");
+    if (like_id < 0 || like_id >= NNEST_LIKE_COUNT) return fail(NNEST_E_UNSUPPORTED, "mcmc adapt: unknown likelihood id %d", like_id);
+    if (h->s.base_beta != 0.f)
+        return fail(NNEST_E_UNSUPPORTED, "mcmc adapt: GeneralisedNormal base (beta=%g): the kernel draws from N(0, I) only", (double)h->s.base_beta);
+    if (!ensemble_form_eligible(h->s))
+        return fail(NNEST_E_UNSUPPORTED, "mcmc adapt: x_dim=%d hidden=%d blocks=%d layers=%d scale mode %d: the kernel takes hidden 16, 3 blocks, "
+                    "1 layer, scale '' (the one-walker-per-wave layout), x_dim <= 128", h->s.D, h->s.H, h->s.B, h->s.L, h->s.scale_mode);
+    if (h->s.NT < 1 || h->s.NT > 4) return fail(NNEST_E_UNSUPPORTED, "mcmc adapt: x_dim=%d not instantiated", h->s.D);
+    return NNEST_OK;
+}
+
+// (as nnest_mcmc_mixed_steps: the checks that need no handle come first)
+int nnest_mcmc_adapt_steps(nnest_nvp_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                           const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev,
+                           float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev, float *hist_x_dev,
+                           double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size, uint64_t step0, uint64_t seed,
+                           uint64_t walker_offset, double beta, int global_every, int *n_accept_global_dev, const double *step_in_dev,
+                           double *step_out_dev, double *hist_step_dev, uint32_t adapt_steps, double adapt_rate, double target_accept,
+                           void *stream) {
+    if (!like) return fail(NNEST_E_ARG, "like is NULL");
+    if (like->id < 0 || like->id >= NNEST_LIKE_COUNT) return fail(NNEST_E_ARG, "unknown likelihood id %d", like->id);
+    int rc;
+    if ((rc = mcmc_beta_ok(beta))) return rc;
+    if ((rc = mcmc_mixed_every_ok(global_every))) return rc;
+    if ((rc = mcmc_adapt_rule_ok(adapt_rate, target_accept))) return rc;
+    McmcAdaptArgs a;
+    memset(&a, 0, sizeof(a));
+    a.beta = beta;
+    a.global_every = global_every;
+    a.n_accept_global = n_accept_global_dev;
+    a.step_in = step_in_dev;
+    a.step_out = step_out_dev;
+    a.hist_step = hist_step_dev;
+    a.adapt_steps = adapt_steps;
+    a.adapt_rate = adapt_rate;
+    a.target_accept = target_accept;
+    rc = mcmc_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev, lp_out_dev,
+                   logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0, seed, walker_offset);
+    if (rc) return rc;
+    if ((rc = nnest_mcmc_adapt_check(h, like->id))) return rc;
+    if ((rc = check_like(like, h->s.D, &a.like))) return rc;
+    a.like.scale = 1.0f;
+    hipError_t e = launch_mcmc_adapt(h->s, h->w, a, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(NNEST_E_UNSUPPORTED, "mcmc adapt: x_dim=%d not instantiated", h->s.D);
+    if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_mcmc_adapt: %s", hipGetErrorString(e));
     return NNEST_OK;
 }
 

@@ -18,6 +18,7 @@
 #include "mcmc_walk.h"
 #include "importance_walk.h"
 #include "mcmc_mixed.h"
+#include "mcmc_adapt.h"
 #include "nnest_internal.h"
 #include "mh_common.h"
 
@@ -513,6 +514,57 @@ int nnest_spline_mcmc_mixed_steps(nnest_spline_t *h, const nnest_like_t *like, c
     a.like.scale = 1.0f;
     const hipError_t e = launch_spline_mcmc_mixed(SplArgs{h->img, h->s}, a, (hipStream_t)stream);
     if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_mcmc_mixed: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+// what nnest_spline_mcmc_adapt_steps takes, asked before a launch (and by the entry itself): as nnest_spline_mcmc_mixed_check answers
+int nnest_spline_mcmc_adapt_check(nnest_spline_t *h, int like_id) {
+    if (!h) return spline_fail(NNEST_E_ARG, "NULL handle");
+    if (like_id < 0 || like_id >= NNEST_LIKE_COUNT) return spline_fail(NNEST_E_UNSUPPORTED, "mcmc adapt: unknown likelihood id %d", like_id);
+    if (h->s.base_beta != 0.f)
+        return spline_fail(NNEST_E_UNSUPPORTED, "mcmc adapt: GeneralisedNormal base (beta=%g): the kernel draws from N(0, I) only",
+                           (double)h->s.base_beta);
+    McmcAdaptArgs probe;
+    memset(&probe, 0, sizeof(probe));   // (C = 0: the shape's verdict, nothing is launched)
+    if (launch_spline_mcmc_adapt(SplArgs{h->img, h->s}, probe, nullptr) == hipErrorInvalidConfiguration)
+        return spline_fail(NNEST_E_UNSUPPORTED, "spline mcmc adapt: x_dim=%d hidden_dim=%d not instantiated (the team tile's shapes)", h->s.D,
+                           h->s.H);
+    return NNEST_OK;
+}
+
+// the adaptive walk through the spline flow (nnest_spline_mcmc_adapt.hip); the argument checks of nnest_mcmc_adapt_steps
+int nnest_spline_mcmc_adapt_steps(nnest_spline_t *h, const nnest_like_t *like, const float *t_std_dev, const float *t_mean_dev,
+                                  const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev,
+                                  const double *logl_in_dev, float *z_out_dev, float *x_out_dev, double *lp_out_dev, double *logl_out_dev,
+                                  float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C, int steps,
+                                  float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta, int global_every,
+                                  int *n_accept_global_dev, const double *step_in_dev, double *step_out_dev, double *hist_step_dev,
+                                  uint32_t adapt_steps, double adapt_rate, double target_accept, void *stream) {
+    if (!like) return spline_fail(NNEST_E_ARG, "like is NULL");
+    if (like->id < 0 || like->id >= NNEST_LIKE_COUNT) return spline_fail(NNEST_E_ARG, "unknown likelihood id %d", like->id);
+    int rc;
+    if ((rc = mcmc_beta_ok(beta))) return rc;
+    if ((rc = mcmc_mixed_every_ok(global_every))) return rc;
+    if ((rc = mcmc_adapt_rule_ok(adapt_rate, target_accept))) return rc;
+    McmcAdaptArgs a;
+    memset(&a, 0, sizeof(a));
+    a.beta = beta;
+    a.global_every = global_every;
+    a.n_accept_global = n_accept_global_dev;
+    a.step_in = step_in_dev;
+    a.step_out = step_out_dev;
+    a.hist_step = hist_step_dev;
+    a.adapt_steps = adapt_steps;
+    a.adapt_rate = adapt_rate;
+    a.target_accept = target_accept;
+    rc = mcmc_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev, lp_out_dev,
+                   logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0, seed, walker_offset);
+    if (rc) return rc;
+    if ((rc = nnest_spline_mcmc_adapt_check(h, like->id))) return rc;
+    if ((rc = scheck_like(like, h->s.D, &a.like))) return rc;
+    a.like.scale = 1.0f;
+    const hipError_t e = launch_spline_mcmc_adapt(SplArgs{h->img, h->s}, a, (hipStream_t)stream);
+    if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_mcmc_adapt: %s", hipGetErrorString(e));
     return NNEST_OK;
 }
 

@@ -407,7 +407,8 @@ class _HipFlow(object):
         return out
 
     def mcmc_steps(self, like_id, z, steps, step_size, t_std=None, t_mean=None, lo=None, hi=None, lp=None, logl=None, seed=0, step0=0,
-                   walker_offset=0, like_params=None, history=True, beta=None, global_every=0):
+                   walker_offset=0, like_params=None, history=True, beta=None, global_every=0, step_in=None, adapt_steps=0, adapt_rate=1.0,
+                   target_accept=0.234):
         """`steps` steps of random-walk Metropolis in latent space with the likelihood, the prior and the Jacobian in the ratio, in ONE
         launch (the family's `mcmc` entry point: nnest_mcmc_steps, nnest_spline_mcmc_steps; build-defined stream, the reference's move:
         include/nnest_hip.h has the definition).  z [C, D] float32 on the device: the walkers' start; lp, logl [C] float64: the
@@ -425,16 +426,29 @@ class _HipFlow(object):
         -- the proposal is the draw eps itself, accepted on the ratio of importance weights lp - logb under the N(0, I) base --, a
         random-walk step otherwise; the same draws and invariances; beta None is 1.0.  The result then also carries n_accept_global
         [C] (n_accept counts both kinds).  ValueError for global_every < 0.
+        step_in, adapt_steps, adapt_rate, target_accept: adapt_steps == 0 and step_in None -- the entries above, as they were;
+        otherwise the ADAPTIVE walk through the family's `mcmc_adapt` entry (nnest_mcmc_adapt_steps, nnest_spline_mcmc_adapt_steps):
+        the mixed walk (global_every 0 included, beta None is 1.0) in which every walker proposes its local steps at its own float64
+        step -- step_in [C] float64 (clamped to [1e-8, 1e2]), or `step_size` for all -- and, after each local step t < adapt_steps,
+        multiplies it by 1 + adapt_rate / sqrt(t + 1) * (accepted - target_accept); steps t >= adapt_steps and global steps leave
+        it alone.  The same draws and invariances, with the step handed from launch to launch: the result then also carries step
+        [C] float64 (the walkers' steps after the launch; step_in itself, or `step_size`, at steps = 0) and, with history=True,
+        hist_step [C, steps] (after every step; None at steps = 0).  ValueError for adapt_steps < 0 or a misshapen step_in; the
+        library refuses adapt_rate outside [0, 1] and target_accept outside (0, 1).
         NotImplementedError for a family without such a kernel (its handle must not reach another family's)."""
         global_every = int(global_every)
         if global_every < 0:
             raise ValueError('mcmc_steps: global_every=%d (>= 0)' % global_every)
+        adapt_steps = int(adapt_steps)
+        if adapt_steps < 0:
+            raise ValueError('mcmc_steps: adapt_steps=%d (>= 0)' % adapt_steps)
+        adapt = adapt_steps > 0 or step_in is not None
         mixed = global_every > 0
-        fn = self._sym.get('mcmc_mixed' if mixed else 'mcmc' if beta is None else 'mcmc_tempered')
+        fn = self._sym.get('mcmc_adapt' if adapt else 'mcmc_mixed' if mixed else 'mcmc' if beta is None else 'mcmc_tempered')
         if fn is None:
             raise NotImplementedError('no fused %srandom-walk Metropolis kernel for %s' % (
-                'mixed ' if mixed else '' if beta is None else 'tempered ', type(self).__name__))
-        tempered = () if beta is None and not mixed else (ctypes.c_double(1.0 if beta is None else float(beta)),)
+                'adaptive ' if adapt else 'mixed ' if mixed else '' if beta is None else 'tempered ', type(self).__name__))
+        tempered = () if beta is None and not mixed and not adapt else (ctypes.c_double(1.0 if beta is None else float(beta)),)
         dev = self.device
         z = _as_dev_f32(z, dev).contiguous()
         C, D, steps = z.shape[0], self.D, int(steps)
@@ -457,6 +471,20 @@ class _HipFlow(object):
         if mixed:
             out['n_accept_global'] = (torch.empty if steps > 0 else torch.zeros)(C, dtype=torch.int32, device=dev)
             tempered += (global_every, _lib.ptr(out['n_accept_global']))
+        if adapt:
+            if step_in is not None:
+                step_in = torch.as_tensor(step_in, dtype=torch.float64).to(dev).contiguous()
+                if step_in.shape != (C,):
+                    raise ValueError('mcmc_steps: step_in must be shaped [%d], got %s' % (C, tuple(step_in.shape)))
+            if steps > 0:
+                out['step'] = torch.empty(C, **f64)
+            else:   # (nothing is stepped: the start's steps, unclamped)
+                out['step'] = step_in if step_in is not None else torch.full((C,), float(np.float32(step_size)), **f64)
+            out['hist_step'] = torch.empty(C, steps, **f64) if hist else None
+            if not mixed:
+                tempered += (0, None)
+            tempered += (_lib.ptr(step_in), _lib.ptr(out['step']) if steps > 0 else None, _lib.ptr(out['hist_step']),
+                         ctypes.c_uint32(min(adapt_steps, 0xFFFFFFFF)), ctypes.c_double(float(adapt_rate)), ctypes.c_double(float(target_accept)))
         with torch.cuda.device(dev):
             lk = _lib.like_spec(like_id, 1.0, like_params)
             _lib.check(fn(
@@ -474,6 +502,20 @@ class _HipFlow(object):
         fn = self._sym.get('mcmc_mixed_check')
         if fn is None or 'mcmc_mixed' not in self._sym:
             raise NotImplementedError('no fused mixed random-walk Metropolis kernel for %s' % type(self).__name__)
+        with torch.cuda.device(self.device):
+            rc = fn(self._h, int(like_id))
+        if rc == _lib.NNEST_OK:
+            return None
+        msg = self._lib.nnest_hip_last_error()
+        return msg.decode() if msg else 'error %d' % rc
+
+    def mcmc_adapt_refusal(self, like_id):
+        """why `mcmc_steps` with adapt_steps > 0 or a step_in would refuse this flow (its shape, its base) or this likelihood id --
+        the library's own words (the family's `mcmc_adapt_check` entry; nothing is launched) --, or None where it is taken.
+        NotImplementedError for a family without such a kernel"""
+        fn = self._sym.get('mcmc_adapt_check')
+        if fn is None or 'mcmc_adapt' not in self._sym:
+            raise NotImplementedError('no fused adaptive random-walk Metropolis kernel for %s' % type(self).__name__)
         with torch.cuda.device(self.device):
             rc = fn(self._h, int(like_id))
         if rc == _lib.NNEST_OK:
@@ -771,7 +813,8 @@ class HipNVP(_PaddedVectors, _HipFlow):
                    ensemble_moves_max_walkers='nnest_ensemble_moves_max_walkers', mcmc='nnest_mcmc_steps',
                    importance='nnest_importance_evidence', importance_check='nnest_importance_check',
                    mcmc_tempered='nnest_mcmc_tempered_steps', mcmc_mixed='nnest_mcmc_mixed_steps',
-                   mcmc_mixed_check='nnest_mcmc_mixed_check')
+                   mcmc_mixed_check='nnest_mcmc_mixed_check', mcmc_adapt='nnest_mcmc_adapt_steps',
+                   mcmc_adapt_check='nnest_mcmc_adapt_check')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (_PaddedVectors)
         with torch.cuda.device(self.device):

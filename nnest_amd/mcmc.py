@@ -27,7 +27,8 @@ class MCMCSampler(Sampler):
         self.sampler = 'mcmc'
 
     def run(self, mcmc_steps, mcmc_num_chains, training_samples, mcmc_dynamic_step_size=True, stats_interval=100,
-            output_interval=None, initial_jitter=0.01, final_jitter=0.01, init_samples=None, route=None, seed=None, global_every=0):
+            output_interval=None, initial_jitter=0.01, final_jitter=0.01, init_samples=None, route=None, seed=None, global_every=0, adapt_steps=0,
+            target_accept=0.234):
         """mcmc.py:79-130.  `route` and `seed` are not in the reference.  route: None or 'host' -- the reference's step loop with the
         flow passes on the GPU and the likelihood and the prior on the host (`_mcmc_sample_host`), draw for draw on torch's and
         numpy's streams; 'fused' -- every step inside the kernel (`_mcmc_sample_device`: nnest_mcmc_steps for the NVP,
@@ -40,7 +41,13 @@ class MCMCSampler(Sampler):
         ("global") step -- a draw of the flow's base as the proposal, accepted on the ratio of importance weights
         (`_mcmc_sample_device`, nnest_mcmc_mixed_steps) --, which lets a chain jump between the modes the flow has learnt.  It needs
         route='fused' (ValueError otherwise) and a N(0, I) base; the run leaves `global_proposed` and `global_accepted` and logs the
-        global acceptance rate.  0: the run as it was."""
+        global acceptance rate.  0: the run as it was.
+        adapt_steps, target_accept (not in the reference, whose MCMCSampler never forwards mcmc_dynamic_step_size; build-defined):
+        adapt_steps = A > 0 lets every chain of the fused run adapt its own step over the local steps t < A towards the acceptance
+        `target_accept` and keep it from there on (`_mcmc_sample_device`, nnest_mcmc_adapt_steps): from step A on each chain is an
+        ordinary Metropolis chain, so discard the first A steps where exactness matters.  It needs route='fused' (ValueError
+        otherwise); the run leaves `step_sizes` [mcmc_num_chains], `adapt_acceptance` and `frozen_acceptance` and logs them.  0: the
+        run as it was."""
         if route not in (None, 'host', 'fused'):
             raise ValueError("route=%r: None or 'host' (the reference's step loop) or 'fused' (build-defined stream)" % (route,))
         global_every = int(global_every)
@@ -49,19 +56,28 @@ class MCMCSampler(Sampler):
         if global_every and route != 'fused':
             raise ValueError("MCMCSampler.run: global_every=%d needs route='fused': the global step is built into the fused route's "
                              "kernels only" % global_every)
+        adapt_steps = int(adapt_steps)
+        if adapt_steps < 0:
+            raise ValueError('MCMCSampler.run: adapt_steps=%d (over how many steps the chains adapt their step: >= 0)' % adapt_steps)
+        if adapt_steps and route != 'fused':
+            raise ValueError("MCMCSampler.run: adapt_steps=%d needs route='fused': the per-chain step adaptation is built into the fused "
+                             "route's kernels only" % adapt_steps)
+        if adapt_steps and not 0.0 < float(target_accept) < 1.0:
+            raise ValueError('MCMCSampler.run: target_accept=%r (strictly inside (0, 1))' % (target_accept,))
         mean = np.mean(training_samples, axis=0)
         std = np.std(training_samples, axis=0)
         training_samples = (training_samples - mean) / std          # normalise
         self._install_transform(mean, std)                           # T(x) = x * std + mean (the K4 kernels only know x -> s * x)
         if route == 'fused':
-            target, why = self._device_target(entry='mcmc_mixed' if global_every else 'mcmc')
+            target, why = self._device_target(entry='mcmc_adapt' if adapt_steps else 'mcmc_mixed' if global_every else 'mcmc')
             if why is not None:
                 raise ValueError('MCMCSampler.run: the fused route does not take %s' % why)
         self.trainer.train(training_samples, jitter=initial_jitter)
         if route == 'fused':
             samples, latent_samples, derived_samples, loglikes, scale, ncall = self._mcmc_sample_device(
                 mcmc_steps, num_chains=mcmc_num_chains, init_samples=init_samples, output_interval=output_interval,
-                stats_interval=stats_interval, seed=seed, target=target, **(dict(global_every=global_every) if global_every else {}))
+                stats_interval=stats_interval, seed=seed, target=target, **(dict(global_every=global_every) if global_every else {}),
+                **(dict(adapt_steps=adapt_steps, target_accept=float(target_accept)) if adapt_steps else {}))
             if self.chain_stats:   # (the interval lines were logged by the run)
                 self._log_chain_stats(samples, (std, mean), mcmc_steps, None, prefix_offset=1, min_step=0)
         else:

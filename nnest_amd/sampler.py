@@ -746,9 +746,9 @@ class Sampler(object):
         return None
 
     ENTRY_NEEDS = {'mcmc': ('mcmc',), 'mcmc_tempered': ('mcmc', 'mcmc_tempered'), 'importance': ('importance',),
-                   'mcmc_mixed': ('mcmc', 'mcmc_mixed')}
+                   'mcmc_mixed': ('mcmc', 'mcmc_mixed'), 'mcmc_adapt': ('mcmc', 'mcmc_adapt')}
     ENTRY_KERNEL = {'mcmc': 'random-walk Metropolis', 'mcmc_tempered': 'tempered random-walk Metropolis', 'importance': 'importance-sampling',
-                    'mcmc_mixed': 'mixed (local and global step) Metropolis'}
+                    'mcmc_mixed': 'mixed (local and global step) Metropolis', 'mcmc_adapt': 'adaptive-step Metropolis'}
 
     def _device_target(self, affine=None, entry=None, unit_box_on_x=False):
         """(target, None) where the likelihood and the prior run on the device under the transform `affine` = (std, mean) (None:
@@ -756,9 +756,9 @@ class Sampler(object):
         A DeviceTarget: no derived parameters, a likelihood the kernels know that agrees with the host callable on T(x), and no prior
         or a UniformPrior on T(x) -- with `unit_box_on_x` (the evidence) also the NestedSampler's prior, the unit box on x under
         x -> s * x (`_linear_scale`): the box on T(x) is +-|s|.  `entry` names the flow entry a front end needs bound ('mcmc',
-        'mcmc_tempered' and 'mcmc_mixed' -- which need 'mcmc' too --, 'importance'): every parameter must then be fast and, for
-        'importance' and 'mcmc_mixed', the library must take the flow's shape and base (`importance_refusal`, `mcmc_mixed_refusal`:
-        nothing is launched).  The ensemble routes name none:
+        'mcmc_tempered', 'mcmc_mixed' and 'mcmc_adapt' -- which need 'mcmc' too --, 'importance'): every parameter must then be fast
+        and, for 'importance', 'mcmc_mixed' and 'mcmc_adapt', the library must take the flow's shape and base (`importance_refusal`,
+        `mcmc_mixed_refusal`, `mcmc_adapt_refusal`: nothing is launched).  The ensemble routes name none:
         they fall back to rounds.  One probe of the host callable (`_probe_agrees`) per call: a run resolves once and hands the
         target down"""
         affine = self._ensemble_affine() if affine is None else affine
@@ -780,6 +780,10 @@ class Sampler(object):
                 return None, 'the flow %s: %s' % (type(netG).__name__, why)
         if entry == 'mcmc_mixed':   # (the global step draws from the base: its shape and N(0, I), in the library's words)
             why = netG.mcmc_mixed_refusal(like_id)
+            if why is not None:
+                return None, 'the flow %s: %s' % (type(netG).__name__, why)
+        if entry == 'mcmc_adapt':   # (the adaptive kernels are the mixed walk's: the same shapes and base, in the library's words)
+            why = netG.mcmc_adapt_refusal(like_id)
             if why is not None:
                 return None, 'the flow %s: %s' % (type(netG).__name__, why)
         refused ='this transform, likelihood or prior (an affine transform, a likelihood that agrees with the kernel\'s, and no prior%s)' % (
@@ -905,7 +909,8 @@ class Sampler(object):
         return out
 
     def _mcmc_sample_device(self, mcmc_steps, step_size=0.0, num_chains=1, init_samples=None, max_start_tries=100, output_interval=None,
-                            stats_interval=None, seed=None, chunk_steps=None, target=None, global_every=0):
+                            stats_interval=None, seed=None, chunk_steps=None, target=None, global_every=0, adapt_steps=0,
+                            target_accept=0.234):
         """`_mcmc_sample` with loglstar = None (sampler.py:372-416: the likelihood, the prior and the Jacobian in the ratio) with every
         step of a launch inside the kernel (include/nnest_hip.h nnest_mcmc_steps, nnest_spline_mcmc_steps).  BUILD-DEFINED STREAM,
         THE REFERENCE'S MOVE: parity with the host route's torch stream is statistical.  The step is fixed (`step_size`, <= 0: the
@@ -919,12 +924,20 @@ class Sampler(object):
         (t + 1) % k == 0 -- is a flow-independence ("global") step: the proposal is a draw of the flow's base, accepted on the ratio
         of importance weights, through the family's mixed kernel (`_device_target(entry='mcmc_mixed')`: the base must be N(0, I)).
         The run leaves `global_proposed` and `global_accepted` on the sampler and logs the global acceptance rate -- the figure
-        that says how good the flow is as a proposal.  0: the run as it was."""
-        global_every = int(global_every)
+        that says how good the flow is as a proposal.  0: the run as it was.
+        adapt_steps = A > 0 (build-defined; include/nnest_hip.h nnest_mcmc_adapt_steps): every chain adapts its own step over the
+        local steps t < A of the run -- a Robbins-Monro rule on its own decisions towards the acceptance `target_accept` -- and keeps
+        it from there on, through the family's adaptive kernel (`_device_target(entry='mcmc_adapt')`); the chains' steps are handed
+        from launch to launch, so the cut still does not change the run.  The run leaves `step_sizes` [N] (the chains' steps at its
+        end), `adapt_acceptance` (of the local steps t < A) and `frozen_acceptance` (of the local steps t >= A; nan where there are
+        none) on the sampler and logs the three.  0: the run as it was."""
+        global_every, adapt_steps = int(global_every), int(adapt_steps)
         if global_every < 0:
             raise ValueError('mcmc: global_every=%d (every how many steps a global step is taken: >= 0)' % global_every)
+        if adapt_steps < 0:
+            raise ValueError('mcmc: adapt_steps=%d (over how many steps of the run the chains adapt their step: >= 0)' % adapt_steps)
         if target is None:
-            target, why = self._device_target(entry='mcmc_mixed' if global_every else 'mcmc')
+            target, why = self._device_target(entry='mcmc_adapt' if adapt_steps else 'mcmc_mixed' if global_every else 'mcmc')
             if why is not None:
                 raise ValueError('mcmc: the fused route does not take %s' % why)
         S = int(mcmc_steps)
@@ -963,9 +976,44 @@ class Sampler(object):
             return ((res['z'], res['lp'], res['logl']), dict(x=res['hist_x'], z=res['hist_z'], logl=res['hist_logl']),
                     int(res['n_accept'].sum().item()))
 
+        n_local = [0, 0]   # (the accepted local steps: adapting, frozen)
+
+        def piece(k, done, state):   # (steps done .. done + k - 1, all on one side of adapt_steps; state: z, lp, logl, step)
+            res = netG.mcmc_steps(target.like_id, state[0], k, step_size, lp=state[1], logl=state[2], step0=done, step_in=state[3],
+                                  adapt_steps=adapt_steps, target_accept=target_accept, **mixed, **kw)
+            accepted, glob = int(res['n_accept'].sum().item()), 0
+            if global_every:
+                glob = int(res['n_accept_global'].sum().item())
+                n_global[0] += glob
+            n_local[0 if done < adapt_steps else 1] += accepted - glob
+            return (res['z'], res['lp'], res['logl'], res['step']), dict(x=res['hist_x'], z=res['hist_z'], logl=res['hist_logl']), accepted
+
+        def launch_adapt(k, done, state):   # (a launch across adapt_steps runs as two: the cut does not change the run)
+            k0 = adapt_steps - done if done < adapt_steps < done + k else k
+            state, chunk, accepted = piece(k0, done, state)
+            if k0 < k:
+                state, rest, more = piece(k - k0, done + k0, state)
+                chunk, accepted = dict((key, torch.cat([rows, rest[key]], dim=1)) for key, rows in chunk.items()), accepted + more
+            return state, chunk, accepted
+
         ncall = N * (tries + S)
-        self._run_in_launches(launch, (z, start['lp'], start['logl']), dict(x=samples, z=latent, logl=loglikes, derived=derived), S,
-                              chunk_steps, output_interval, first=1, ncall=ncall)
+        hist = dict(x=samples, z=latent, logl=loglikes, derived=derived)
+        if adapt_steps:
+            state = self._run_in_launches(launch_adapt, (z, start['lp'], start['logl'], None), hist, S, chunk_steps, output_interval,
+                                          first=1, ncall=ncall)
+            A = min(adapt_steps, S)
+            g = (lambda n: n // global_every) if global_every else (lambda n: 0)   # (the global steps among steps 0 .. n - 1)
+            n_adapting, n_frozen = N * (A - g(A)), N * ((S - A) - (g(S) - g(A)))
+            self.step_sizes = (state[3].cpu().numpy() if state[3] is not None else np.full(N, float(np.float32(step_size))))
+            self.adapt_acceptance = n_local[0] / n_adapting if n_adapting else float('nan')
+            self.frozen_acceptance = n_local[1] / n_frozen if n_frozen else float('nan')
+            if self.single_or_primary_process:
+                self.logger.info('mcmc: step adapted over [%d] steps towards acceptance [%5.4f]: step mean [%5.4f] min [%5.4f] max [%5.4f] '
+                                 'adapting acceptance [%5.4f] frozen acceptance [%5.4f]' % (
+                                     adapt_steps, target_accept, self.step_sizes.mean(), self.step_sizes.min(), self.step_sizes.max(),
+                                     self.adapt_acceptance, self.frozen_acceptance))
+        else:
+            self._run_in_launches(launch, (z, start['lp'], start['logl']), hist, S, chunk_steps, output_interval, first=1, ncall=ncall)
         if global_every:   # (steps t = k - 1, 2k - 1, ... of 0 .. S - 1)
             self.global_proposed, self.global_accepted = N * (S // global_every), n_global[0]
             if self.single_or_primary_process:

@@ -18,6 +18,7 @@ convention -- the prior as its callable returns it, the unnormalised indicator -
 logz_smc = logz_importance - sum log(hi - lo)."""
 import functools
 import logging
+import math
 import time
 
 import numpy as np
@@ -91,6 +92,10 @@ class SMCSampler(Sampler):
     # attribute of the sampler, set before `run` (sampler.global_every = 2), not an argument of `run`: tests/test_smc_check.py pins
     # run's argument list, and existing tests stay as they are.  `run` has the rest.
     global_every = 0
+    # The share of a stage's moves over which every particle adapts its own step (include/nnest_hip.h nnest_mcmc_adapt_steps), and
+    # the acceptance the rule aims at; 0.0: the fixed step, the run as it was.  Attributes for the same reason.  `run` has the rest.
+    adapt_fraction = 0.0
+    target_accept = 0.234
 
     def run(self, num_particles=1000, mcmc_steps=25, ess_fraction=0.5, step_size=0.0, jitter=0.01, seed=None, route=None, max_stages=1000):
         """Anneal `num_particles` draws of the prior to the posterior (the module docstring has the algorithm and the convention of
@@ -109,12 +114,24 @@ class SMCSampler(Sampler):
         step at the stage's beta -- a draw of the freshly trained flow's base as the proposal, accepted on the ratio of importance
         weights (include/nnest_hip.h nnest_mcmc_mixed_steps) --, the step that decorrelates the copies a resampling leaves.  The
         fused route only: ValueError naming it where the host loop would run.  Leaves global_acceptance, one entry per stage beside
-        `acceptance`.  0: the run as it was."""
+        `acceptance`.  0: the run as it was.
+        `self.adapt_fraction` = f in (0, 1] (the attribute above) adapts the step: every particle enters a stage at the population's
+        step (stage 0: `step_size`), adapts its own over the first ceil(f * mcmc_steps) steps of the stage towards the acceptance
+        `self.target_accept` and keeps it for the rest; the next stage starts from the geometric mean exp(mean(log step_i)) of this
+        stage's ends, so the step follows the ladder from the prior to the posterior.  The fused route only: ValueError naming it
+        where the host loop would run.  Leaves step_sizes, the population's step at the end of each stage, one entry per stage, and
+        logs it.  0.0: the run as it was, bit for bit."""
         if route not in (None, 'host', 'fused'):
             raise ValueError("route=%r: None, 'host' or 'fused'" % (route,))
         global_every = int(self.global_every)
         if global_every < 0:
             raise ValueError('SMCSampler.run: global_every=%d (every how many steps a global step is taken: >= 0)' % global_every)
+        adapt_fraction, target_accept = float(self.adapt_fraction), float(self.target_accept)
+        if not 0.0 <= adapt_fraction <= 1.0:
+            raise ValueError('SMCSampler.run: adapt_fraction=%r (the share of a stage over which the step adapts: inside [0, 1])' % (
+                self.adapt_fraction,))
+        if adapt_fraction and not 0.0 < target_accept < 1.0:
+            raise ValueError('SMCSampler.run: target_accept=%r (strictly inside (0, 1))' % (self.target_accept,))
         if self.sample_prior is None:
             raise ValueError('Prior does not have sample method')
         N, S, D = int(num_particles), int(mcmc_steps), self.x_dim
@@ -124,29 +141,38 @@ class SMCSampler(Sampler):
             raise ValueError('SMCSampler.run: ess_fraction=%r (inside (0, 1))' % (ess_fraction,))
         self._install_transform(np.zeros(D), np.ones(D))   # (theta itself, until the first stage installs its own)
         # (likelihood and box do not depend on T: resolved here, once; every stage takes a copy under its own T)
-        target, why = (None, None) if route == 'host' else self._device_target(entry='mcmc_mixed' if global_every else 'mcmc_tempered')
+        target, why = (None, None) if route == 'host' else self._device_target(
+            entry='mcmc_adapt' if adapt_fraction else 'mcmc_mixed' if global_every else 'mcmc_tempered')
         if route == 'fused' and why is not None:
             raise ValueError('SMCSampler.run: the fused route does not take %s' % why)
         route = 'host' if target is None else 'fused'
         if global_every and route == 'host':
             raise ValueError("SMCSampler.run: global_every=%d needs the fused route, whose kernels alone take the global step%s" % (
                 global_every, '' if why is None else ': the fused route does not take %s' % why))
+        if adapt_fraction and route == 'host':
+            raise ValueError("SMCSampler.run: adapt_fraction=%g needs the fused route, whose kernels alone adapt the step%s" % (
+                adapt_fraction, '' if why is None else ': the fused route does not take %s' % why))
         if step_size <= 0.0:
             step_size = 2 / D ** 0.5
         seed = self._next_seed() if seed is None else int(seed)
         if route == 'fused':
             state = self._smc_start_fused(N, target)
-            stage_fn = functools.partial(self._smc_stage_fused, target=target, **(dict(global_every=global_every) if global_every else {}))
+            adapt = dict(adapt_steps=int(math.ceil(adapt_fraction * S)), target_accept=target_accept) if adapt_fraction else {}
+            stage_fn = functools.partial(self._smc_stage_fused, target=target, **(dict(global_every=global_every) if global_every else {}),
+                                         **adapt)
         else:
             state, stage_fn = self._smc_start_host(N), self._smc_stage_host
         beta, logz = 0.0, 0.0
         self.betas, self.ess, self.acceptance, self.logz_steps, self.stage_times = [], [], [], [], []
         self.global_acceptance = []   # (per stage, with global_every > 0)
+        self.step_sizes = []          # (per stage, with adapt_fraction > 0: the population's step at the stage's end)
         stage = 0
         while beta < 1.0:
             if stage >= int(max_stages):
                 raise RuntimeError('SMCSampler.run: beta=%g after %d stages (max_stages)' % (beta, stage))
-            beta_new, inc, ess, acc, state, times = stage_fn(state, beta, float(ess_fraction), S, float(step_size), float(jitter), seed, stage)
+            # (with adapt_fraction > 0 a stage enters at the step the stage before it left)
+            stage_step = self.step_sizes[-1] if self.step_sizes else float(step_size)
+            beta_new, inc, ess, acc, state, times = stage_fn(state, beta, float(ess_fraction), S, stage_step, float(jitter), seed, stage)
             if not beta_new > beta:
                 raise RuntimeError('SMCSampler.run: the ladder did not advance (beta=%r -> %r)' % (beta, beta_new))
             beta = beta_new
@@ -162,6 +188,9 @@ class SMCSampler(Sampler):
                 if global_every:
                     self.logger.info('smc stage [%d] global steps every [%d] global acceptance [%5.4f]' % (
                         stage, global_every, self.global_acceptance[-1]))
+                if adapt_fraction:
+                    self.logger.info('smc stage [%d] entered at step [%.6g] adapted over [%d] steps: population step [%.6g]' % (
+                        stage, stage_step, int(math.ceil(adapt_fraction * S)), self.step_sizes[-1]))
         self.logz = logz
         self.smc_route = route
         theta, logl, z = state
@@ -199,7 +228,7 @@ class SMCSampler(Sampler):
         self.total_calls += N
         return theta, logl, None
 
-    def _smc_stage_fused(self, state, beta, ess_fraction, S, step_size, jitter, seed, stage, target, global_every=0):
+    def _smc_stage_fused(self, state, beta, ess_fraction, S, step_size, jitter, seed, stage, target, global_every=0, adapt_steps=0, target_accept=0.234):
         import torch
         from . import flow
         theta, logl, _ = state
@@ -216,7 +245,11 @@ class SMCSampler(Sampler):
         z, _ = netG.forward(normalised.astype(np.float32))
         target = target.with_transform(std, mean)   # (this stage's T)
         res = netG.mcmc_steps(target.like_id, z.contiguous(), S, step_size, seed=stage_seed(seed, stage), history=False, beta=beta_new,
-                              **(dict(global_every=global_every) if global_every else {}), **target.launch_kwargs(netG.device))
+                              **(dict(global_every=global_every) if global_every else {}),
+                              **(dict(adapt_steps=adapt_steps, target_accept=target_accept) if adapt_steps else {}),
+                              **target.launch_kwargs(netG.device))
+        if adapt_steps:   # (the population's step: the geometric mean of the particles' ends, one reduction)
+            self.step_sizes.append(float(torch.exp(torch.log(res['step']).mean()).item()))
         theta = target.transform(res['x'])
         n_acc = int(res['n_accept'].sum().item())
         if global_every:   # (steps t = k - 1, 2k - 1, ... of the stage's 0 .. S - 1)
