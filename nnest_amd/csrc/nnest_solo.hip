@@ -108,6 +108,41 @@ static __device__ __forceinline__ void solo_pin(float (&v)[2][U]) {
         for (int u = 0; u < U; ++u) asm volatile("" : "+v"(v[c][u]));
 }
 
+// The Rosenbrock branch of solo_loglike<2, 0> (with the log-det riding in its row sum), the float32 pairs chosen by hand -- for the
+// register form of mh_kernel_solo, whose lone wave pays for every instruction it issues (profiles/r10/solo_issue_costs.txt:
+// a v_pk_*_f32 costs what any 8-byte instruction costs, two operations for 4.9 cycles).  hipcc packs the 28 operations of the four
+// terms by itself, but as (th0, th1), (th2, th3): the neighbours (th1, th2), (th3, th4) straddle its pairs, and it spends copies and
+// pads on bringing them side by side.  Here a pair is a CLASS -- (th0, th2) = scale * xs[0][:], (th1, th3) = scale * xs[1][:], the
+// registers a coupling block hands over together -- so the neighbours of the first pair ARE the second pair and those of the second
+// are (th2, th4): one copy and the row rotation.  The same operations on the same operands, term by term, summed in the same order:
+// the bits are solo_loglike's (tests/test_gpu_solo_tail.py holds this kernel to the generic code at every x_dim that moves the mask).
+typedef float solo_f32x2 __attribute__((ext_vector_type(2)));
+#pragma clang fp contract(off)
+static __device__ __forceinline__ double solo_rosenbrock2_paired(const LikeSpec &lk, int D, int lane, const float (&xs)[2][2], float &ld_ride) {
+    const int i0 = 4 * (lane & 15);
+    const solo_f32x2 sc = {lk.scale, lk.scale};
+    const solo_f32x2 P = sc * solo_f32x2{xs[0][0], xs[0][1]};    // th[0], th[2]
+    const solo_f32x2 Q = sc * solo_f32x2{xs[1][0], xs[1][1]};    // th[1], th[3]
+    const solo_f32x2 R = {P.y, solo_ror<15>(P.x)};               // th[2], th[4]: the first dim of position m + 1
+    const solo_f32x2 aP = P * P, aQ = Q * Q;
+    const solo_f32x2 bP = Q - aP, bQ = R - aQ;
+    const solo_f32x2 cP = bP * bP, cQ = bQ * bQ;
+    const solo_f32x2 eP = 100.0f * cP, eQ = 100.0f * cQ;
+    const solo_f32x2 fP = 1.0f - P, fQ = 1.0f - Q;
+    const solo_f32x2 qP = fP * fP, qQ = fQ * fQ;
+    const solo_f32x2 tP = eP + qP, tQ = eQ + qQ;                 // terms 0, 2 and terms 1, 3
+    float facc = 0.f;
+    facc = facc + ((i0 + 1 < D) ? tP.x : 0.f);
+    facc = facc + ((i0 + 2 < D) ? tQ.x : 0.f);
+    facc = facc + ((i0 + 3 < D) ? tP.y : 0.f);
+    facc = facc + ((i0 + 4 < D) ? tQ.y : 0.f);
+    solo_logdet_total_and_row_sum(ld_ride, facc);
+    double acc = -(double)facc;
+    if (!(fabs(acc) <= 1.79769313486231570e308)) acc = -1e100;  // logl[~isfinite] = -1e100   sampler.py:128
+    return acc;
+}
+#pragma clang fp contract(fast)
+
 enum { MH_SOLO_LAG_INTERNAL = 8 };   // the relay's schedule under lag 0 (no lagged step exists then: only its bookkeeping uses it)
 template <int U, bool DBG, int LK, int WPG>
 __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
@@ -481,9 +516,7 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
     // `zp`: the proposals in flight.  They pass through the barrier as operands, so that hipcc cannot start their inverse in front of
     // it: the noise wave needs a whole step between two barriers for its draws, and a pair of steps whose barriers sit ~170 instructions
     // late in one and at the head of the other (what the scheduler made of the unrolled loop) waits for it at every second barrier.
-    auto fetch_noise = [&](int par, auto &...zp) {
-        solo_barrier();  // the noise wave has published the buffer: noise, accept uniform and scale of the next step
-        (solo_pin(zp), ...);
+    auto read_noise = [&](int par) {
         if (!recorded) {
 #pragma unroll
             for (int k = 0; k < 2 * U; ++k) nz[k] = nbuf[par][j][pos][k];
@@ -491,6 +524,16 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         }
         fs_next = fsbuf[par];
     };
+    auto fetch_noise = [&](int par, auto &...zp) {
+        solo_barrier();  // the noise wave has published the buffer: noise, accept uniform and scale of the next step
+        (solo_pin(zp), ...);
+        read_noise(par);
+    };
+    // The straight steps of the kernel the benchmark runs read the buffer BEHIND the step's inverse instead of behind its barrier (the
+    // values are due at the next proposal; the likelihood and the decision cover the LDS round trip).  Where the reads sit is otherwise
+    // hipcc's choice, and it costs: with all three of a step directly behind the barrier -- what the scheduler makes of this loop as
+    // soon as the likelihood's code changes -- a 218 us launch takes 229 on the same instructions (profiles/r10/k4_before_after.txt, B / C).
+    constexpr bool LATE_FETCH = LK == NNEST_LIKE_ROSENBROCK && U == 2 && !DBG && !LDSW;
     PSTAMP(p5);
     fetch_noise(0);                        // P0
     PSTAMP(p6);
@@ -522,7 +565,7 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
             u = u_next;
         }
     };
-    auto finish = [&](Prop &r, float u) {
+    auto finish = [&](Prop &r, float u, int late_par = -1) {   // late_par >= 0: the step's noise fetch, behind the inverse (LATE_FETCH)
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -532,8 +575,13 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         // the partial's reduction in its wait states (solo_logdet_total_and_row_sum); the general kernel reduces it here
         constexpr bool RIDE = LK == NNEST_LIKE_ROSENBROCK;
         r.ldp = RIDE ? inverse(r.xp) : solo_logdet_total(inverse(r.xp));
+        if (late_par >= 0) {
+            asm volatile("" : "+v"(r.ldp) : : "memory");   // (no instruction: the reads below stay behind the inverse, whose result this is)
+            read_noise(late_par);
+        }
         STAMP(st2);
-        if constexpr (RIDE) r.lp = solo_loglike<U, LK>(like, D, lane, r.xp, &r.ldp);
+        if constexpr (RIDE && U == 2 && !DBG && !LDSW) r.lp = solo_rosenbrock2_paired(like, D, lane, r.xp, r.ldp);
+        else if constexpr (RIDE) r.lp = solo_loglike<U, LK>(like, D, lane, r.xp, &r.ldp);
         // log_ratio = log_det_J' - log_det_J, -inf outside the prior box  (sampler.py:326-331); UniformPrior(D,-1,1)
         // (priors.py:39-43): NaN compares false, i.e. counts as inside; padded dims hold 0
         int okl = 1;
@@ -615,8 +663,14 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         Prop r;
         float u;
         propose(it, fs_next, r.zp, u);
-        fetch_noise(par, r.zp);                // P_it
-        finish(r, u);
+        if constexpr (LATE_FETCH) {
+            solo_barrier();                    // P_it
+            solo_pin(r.zp);
+            finish(r, u, par);
+        } else {
+            fetch_noise(par, r.zp);            // P_it
+            finish(r, u);
+        }
         apply(it, par, r);
         STAMP(st3);
 #ifdef NNEST_STAMP
