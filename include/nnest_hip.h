@@ -609,6 +609,55 @@ int nnest_spline_mcmc_adapt_steps(struct nnest_spline *spl, const nnest_like_t *
                                   float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta, int global_every,
                                   int *n_accept_global_dev, const double *step_in_dev, double *step_out_dev, double *hist_step_dev,
                                   uint32_t adapt_steps, double adapt_rate, double target_accept, void *stream);
+/* A GAUSSIAN LIKELIHOOD FROM USER DATA in the adaptive walk above, in kernels of their own (nnest_mcmc_gdata.hip,
+ * nnest_spline_mcmc_gdata.hip).  BUILD-DEFINED.  No NNEST_LIKE_* id stands for it: the likelihood is compiled into
+ * these kernels and described by nnest_gdata_t.  (All added within ABI 15.)
+ *   logL(theta) = logl0 - 1/2 (theta - mu)^T P (theta - mu),   P = R^T R symmetric positive definite.
+ * nnest_gdata_t: mu_dev [D] float32; r_dev [D, D] float32, row-major, UPPER triangular (the float32 rounding of L^T, P = L L^T in
+ *   float64; the strictly lower triangle holds zeros and is never read); logl0 finite; 1 <= D <= 128.
+ * The arithmetic, with t = T(x) the float32 row the existing evaluators produce (or a row of t_dev):
+ *     d_c  = t_c - mu_c                       float32, one rounding
+ *     y_r  = sum_{c >= r} R[r, c] * d_c       float32; the order of the sum is the kernel's own, fused multiply-adds allowed
+ *     q    = sum_r (double)y_r * (double)y_r  float64, in a fixed order: the same bits on every lane that holds the walker
+ *     logL = logl0 - 0.5 * q                  float64; -1e100 where that is not finite (the rule of the known likelihoods)
+ *   So logL <= logl0 always, a row equal to mu gives logl0 exactly, and the same row gives the same bits in any position of any
+ *   launch of one entry.  (The two walks order the sum of y_r differently: their values agree to float32 rounding, not to the bit.)
+ * nnest_loglike_gdata: the likelihood alone on N rows t_dev [N, D] float32 that are already T(x); logl_dev [N] float64.  D must be
+ *   the descriptor's.  N = 0 launches nothing.
+ * nnest_mcmc_gdata_steps, nnest_spline_mcmc_gdata_steps: the arguments of nnest_mcmc_adapt_steps / nnest_spline_mcmc_adapt_steps with
+ *   `const nnest_gdata_t *gdata` in place of `const nnest_like_t *like`.  The run is the adaptive walk's in every respect -- draws,
+ *   schedule, weight, accept rule, step rule, beta, lp_in_dev / logl_in_dev, histories, counters, steps = 0, the cut into launches,
+ *   a shard by walker_offset --; only logL differs.  With adapt_steps = 0 and step_in_dev NULL it is the mixed walk on this
+ *   likelihood, with global_every = 0 besides the tempered random walk, at beta = 1.0 the plain one.
+ * NNEST_E_ARG before any launch, the outputs untouched: gdata NULL, a NULL mu_dev or r_dev, D outside 1 .. 128 or not the flow's
+ *   x_dim (not the D argument of nnest_loglike_gdata), logl0 not finite, and every argument error of the adaptive entries.
+ *   NNEST_E_UNSUPPORTED before any launch: what the _check entry refuses.
+ * nnest_mcmc_gdata_check, nnest_spline_mcmc_gdata_check: NNEST_OK where the entry takes this handle (its shape and base: what
+ *   nnest_mcmc_adapt_check / nnest_spline_mcmc_adapt_check take) and a descriptor of dimension D, else NNEST_E_UNSUPPORTED -- or
+ *   NNEST_E_ARG for a D that is not the flow's x_dim -- with the reason in nnest_hip_last_error(); nothing is launched. */
+typedef struct nnest_gdata {
+    const float *mu_dev;
+    const float *r_dev;
+    double logl0;
+    int D;
+} nnest_gdata_t;
+int nnest_loglike_gdata(const nnest_gdata_t *gdata, const float *t_dev, double *logl_dev, int N, int D, void *stream);
+int nnest_mcmc_gdata_check(nnest_nvp_t *nvp, int D);
+int nnest_spline_mcmc_gdata_check(struct nnest_spline *spl, int D);
+int nnest_mcmc_gdata_steps(nnest_nvp_t *nvp, const nnest_gdata_t *gdata, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                           const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev,
+                           float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev, float *hist_x_dev,
+                           double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size, uint64_t step0, uint64_t seed,
+                           uint64_t walker_offset, double beta, int global_every, int *n_accept_global_dev, const double *step_in_dev,
+                           double *step_out_dev, double *hist_step_dev, uint32_t adapt_steps, double adapt_rate, double target_accept,
+                           void *stream);
+int nnest_spline_mcmc_gdata_steps(struct nnest_spline *spl, const nnest_gdata_t *gdata, const float *t_std_dev, const float *t_mean_dev,
+                                  const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev,
+                                  const double *logl_in_dev, float *z_out_dev, float *x_out_dev, double *lp_out_dev, double *logl_out_dev,
+                                  float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C, int steps,
+                                  float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta, int global_every,
+                                  int *n_accept_global_dev, const double *step_in_dev, double *step_out_dev, double *hist_step_dev,
+                                  uint32_t adapt_steps, double adapt_rate, double target_accept, void *stream);
 /* IMPORTANCE-SAMPLED EVIDENCE with the trained flow as the proposal: Z = E_q[L(T(x)) pi(T(x)) / q(x)], drawn, evaluated and reduced
  * inside one kernel.  BUILD-DEFINED: the reference has no such estimator.  Sample m is a global 64-bit index; row k of a launch of M
  * samples is m = sample_offset + k:

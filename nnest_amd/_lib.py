@@ -103,6 +103,11 @@ def moves_ref(mv):
     return None if mv is None else ctypes.byref(mv)
 
 
+class GdataSpec(ctypes.Structure):
+    """nnest_gdata_t (include/nnest_hip.h): the Gaussian likelihood from user data -- device pointers of mu [D] and R [D, D], logl0, D"""
+    _fields_ = [('mu_dev', ctypes.c_void_p), ('r_dev', ctypes.c_void_p), ('logl0', ctypes.c_double), ('D', ctypes.c_int)]
+
+
 class TrainResult(ctypes.Structure):
     _fields_ = [('epochs_run', ctypes.c_int), ('best_epoch', ctypes.c_int),
                 ('best_validation_loss', ctypes.c_float), ('last_train_loss', ctypes.c_float),
@@ -243,6 +248,15 @@ SIGNATURES = {
                                       _u64, _u64, _d, _i, _vp, _vp, _vp, _vp, _u32, _d, _d, _vp],
     'nnest_mcmc_adapt_check': [_vp, _i],
     'nnest_spline_mcmc_adapt_check': [_vp, _i],
+    # the Gaussian likelihood from user data: the adaptive entries' arguments with `const nnest_gdata_t *gdata` for `like`;
+    # (gdata, t_dev, logl_dev, N, D, stream); (handle, D)
+    'nnest_mcmc_gdata_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64, _u64,
+                               _u64, _d, _i, _vp, _vp, _vp, _vp, _u32, _d, _d, _vp],
+    'nnest_spline_mcmc_gdata_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64,
+                                      _u64, _u64, _d, _i, _vp, _vp, _vp, _vp, _u32, _d, _d, _vp],
+    'nnest_loglike_gdata': [_vp, _vp, _vp, _i, _i, _vp],
+    'nnest_mcmc_gdata_check': [_vp, _i],
+    'nnest_spline_mcmc_gdata_check': [_vp, _i],
     # (logl_dev, N, beta, ess_fraction, out_dev [4], m_dev [N] int64, stream)
     'nnest_smc_reweight': [_vp, _i, _d, _d, _vp, _vp, _vp],
     # (m_dev, N, D, seed, stage, theta_in_dev, logl_in_dev, anc_out_dev, theta_out_dev, logl_out_dev, stream)

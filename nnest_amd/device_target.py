@@ -1,9 +1,10 @@
-"""DeviceTarget: what the fused routes hand a kernel as the target -- the likelihood (an id the kernels know and its parameters), the
+"""DeviceTarget: what the fused routes hand a kernel as the target -- the likelihood (an id the kernels know and its parameters, or
+the descriptor of a Gaussian likelihood from user data: `like_data`, with like_id None), the
 affine T(x) = x * t_std + t_mean the likelihood sees, and the prior box [lo, hi] on T(x).  `Sampler._device_target` decides it, once
 per run; every launch of the run takes the same staged tensors (`launch_kwargs`)."""
 import numpy as np
 
-_FIXED = ('like_id', 'like_params', 't_std', 't_mean', 'lo', 'hi')
+_FIXED = ('like_id', 'like_params', 't_std', 't_mean', 'lo', 'hi', 'like_data')
 
 
 def affine_on_device(x, t_std, t_mean):
@@ -13,14 +14,24 @@ def affine_on_device(x, t_std, t_mean):
 
 class DeviceTarget(object):
     """like_id, like_params; t_std, t_mean: float32 [D] or both None (the identity); lo, hi: float32 [D] or both None (no prior).
+    like_data: None, or the descriptor of a Gaussian likelihood from user data (likelihoods.GaussianData.hip_like_data: mu, R,
+    logl0) -- like_id is then None, and the Metropolis bindings route on the `like_data` keyword.
     The fields are fixed once set: another transform is another target (`with_transform`), so tensors staged for one (std, mean)
     never serve another."""
 
-    def __init__(self, like_id, like_params=(), t_std=None, t_mean=None, lo=None, hi=None):
+    def __init__(self, like_id, like_params=(), t_std=None, t_mean=None, lo=None, hi=None, like_data=None):
         if (t_std is None) != (t_mean is None) or (lo is None) != (hi is None):
             raise ValueError('DeviceTarget: t_std and t_mean, and lo and hi: both or neither')
         vec = lambda v: None if v is None else np.array(v, np.float32).reshape(-1)   # (a copy, cast as the bindings cast)
-        self.like_id, self.like_params = int(like_id), tuple(like_params or ())
+        if (like_id is None) == (like_data is None):
+            raise ValueError('DeviceTarget: a like_id, or like_id None with a like_data')
+        self.like_id, self.like_params = None if like_id is None else int(like_id), tuple(like_params or ())
+        if like_data is not None:   # (copies, cast as the bindings cast)
+            like_data = dict(mu=np.array(like_data['mu'], np.float32).reshape(-1), R=np.array(like_data['R'], np.float32),
+                             logl0=float(like_data['logl0']))
+            like_data['mu'].setflags(write=False)
+            like_data['R'].setflags(write=False)
+        self.like_data = like_data
         self.t_std, self.t_mean, self.lo, self.hi = vec(t_std), vec(t_mean), vec(lo), vec(hi)
         for v in (self.t_std, self.t_mean, self.lo, self.hi):
             if v is not None:
@@ -34,16 +45,20 @@ class DeviceTarget(object):
 
     def with_transform(self, t_std, t_mean):
         """the same likelihood and box under T(x) = x * t_std + t_mean: neither depends on T, so nothing is checked again"""
-        return DeviceTarget(self.like_id, self.like_params, t_std, t_mean, self.lo, self.hi)
+        return DeviceTarget(self.like_id, self.like_params, t_std, t_mean, self.lo, self.hi, self.like_data)
 
     def launch_kwargs(self, device):
-        """the keywords the flow bindings take (t_std, t_mean, lo, hi as float32 tensors on `device`, and like_params): staged on the
-        first call for a device, the same tensors after it"""
+        """the keywords the flow bindings take (t_std, t_mean, lo, hi as float32 tensors on `device`, and like_params; with a
+        like_data, and only then, `like_data` with mu and R as float32 tensors on `device`): staged on the first call for a device,
+        the same tensors after it"""
         from . import flow
         key = str(device)
         if key not in self._staged:
             vecs = flow.target_vectors('DeviceTarget', device, self.t_std, self.t_mean, self.lo, self.hi)
             self._staged[key] = dict(zip(('t_std', 't_mean', 'lo', 'hi'), vecs), like_params=self.like_params)
+            if self.like_data is not None:
+                _, (mu, R) = flow.gdata_spec(self.like_data, device)
+                self._staged[key]['like_data'] = dict(mu=mu, R=R, logl0=self.like_data['logl0'])
         return dict(self._staged[key])
 
     def transform(self, x):

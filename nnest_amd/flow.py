@@ -408,7 +408,7 @@ class _HipFlow(object):
 
     def mcmc_steps(self, like_id, z, steps, step_size, t_std=None, t_mean=None, lo=None, hi=None, lp=None, logl=None, seed=0, step0=0,
                    walker_offset=0, like_params=None, history=True, beta=None, global_every=0, step_in=None, adapt_steps=0, adapt_rate=1.0,
-                   target_accept=0.234):
+                   target_accept=0.234, like_data=None):
         """`steps` steps of random-walk Metropolis in latent space with the likelihood, the prior and the Jacobian in the ratio, in ONE
         launch (the family's `mcmc` entry point: nnest_mcmc_steps, nnest_spline_mcmc_steps; build-defined stream, the reference's move:
         include/nnest_hip.h has the definition).  z [C, D] float32 on the device: the walkers' start; lp, logl [C] float64: the
@@ -435,6 +435,11 @@ class _HipFlow(object):
         [C] float64 (the walkers' steps after the launch; step_in itself, or `step_size`, at steps = 0) and, with history=True,
         hist_step [C, steps] (after every step; None at steps = 0).  ValueError for adapt_steps < 0 or a misshapen step_in; the
         library refuses adapt_rate outside [0, 1] and target_accept outside (0, 1).
+        like_data: None -- the entries above, as they were; the descriptor of a Gaussian likelihood from user data
+        (likelihoods.GaussianData.hip_like_data: mu [D] and R [D, D] float32, logl0) -- `like_id` must then be None, and the run goes
+        through the family's `mcmc_gdata` entry (nnest_mcmc_gdata_steps, nnest_spline_mcmc_gdata_steps: the adaptive walk with that
+        likelihood compiled in) whatever beta, global_every, adapt_steps and step_in are; the result carries the keys the same
+        arguments give above.
         NotImplementedError for a family without such a kernel (its handle must not reach another family's)."""
         global_every = int(global_every)
         if global_every < 0:
@@ -444,11 +449,16 @@ class _HipFlow(object):
             raise ValueError('mcmc_steps: adapt_steps=%d (>= 0)' % adapt_steps)
         adapt = adapt_steps > 0 or step_in is not None
         mixed = global_every > 0
-        fn = self._sym.get('mcmc_adapt' if adapt else 'mcmc_mixed' if mixed else 'mcmc' if beta is None else 'mcmc_tempered')
+        gdata = like_data is not None
+        if gdata and like_id is not None:
+            raise ValueError('mcmc_steps: like_data goes with like_id=None, got like_id=%r' % (like_id,))
+        fn = self._sym.get('mcmc_gdata' if gdata else 'mcmc_adapt' if adapt else 'mcmc_mixed' if mixed else 'mcmc' if beta is None
+                           else 'mcmc_tempered')
         if fn is None:
-            raise NotImplementedError('no fused %srandom-walk Metropolis kernel for %s' % (
-                'adaptive ' if adapt else 'mixed ' if mixed else '' if beta is None else 'tempered ', type(self).__name__))
-        tempered = () if beta is None and not mixed and not adapt else (ctypes.c_double(1.0 if beta is None else float(beta)),)
+            raise NotImplementedError('no fused %srandom-walk Metropolis kernel for %s%s' % (
+                'adaptive ' if adapt else 'mixed ' if mixed else '' if beta is None else 'tempered ', type(self).__name__,
+                ' on a Gaussian likelihood from user data' if gdata else ''))
+        tempered = () if beta is None and not mixed and not adapt and not gdata else (ctypes.c_double(1.0 if beta is None else float(beta)),)
         dev = self.device
         z = _as_dev_f32(z, dev).contiguous()
         C, D, steps = z.shape[0], self.D, int(steps)
@@ -471,6 +481,10 @@ class _HipFlow(object):
         if mixed:
             out['n_accept_global'] = (torch.empty if steps > 0 else torch.zeros)(C, dtype=torch.int32, device=dev)
             tempered += (global_every, _lib.ptr(out['n_accept_global']))
+        elif gdata:
+            tempered += (0, None)
+        if gdata and not adapt:   # (the adaptive entry's arguments with the adaptation off: the mixed walk)
+            tempered += (None, None, None, ctypes.c_uint32(0), ctypes.c_double(float(adapt_rate)), ctypes.c_double(float(target_accept)))
         if adapt:
             if step_in is not None:
                 step_in = torch.as_tensor(step_in, dtype=torch.float64).to(dev).contiguous()
@@ -481,12 +495,15 @@ class _HipFlow(object):
             else:   # (nothing is stepped: the start's steps, unclamped)
                 out['step'] = step_in if step_in is not None else torch.full((C,), float(np.float32(step_size)), **f64)
             out['hist_step'] = torch.empty(C, steps, **f64) if hist else None
-            if not mixed:
+            if not mixed and not gdata:
                 tempered += (0, None)
             tempered += (_lib.ptr(step_in), _lib.ptr(out['step']) if steps > 0 else None, _lib.ptr(out['hist_step']),
                          ctypes.c_uint32(min(adapt_steps, 0xFFFFFFFF)), ctypes.c_double(float(adapt_rate)), ctypes.c_double(float(target_accept)))
         with torch.cuda.device(dev):
-            lk = _lib.like_spec(like_id, 1.0, like_params)
+            if gdata:
+                lk, keep = gdata_spec(like_data, dev)   # (`keep`: the staged arrays, alive until the call has been enqueued)
+            else:
+                lk = _lib.like_spec(like_id, 1.0, like_params)
             _lib.check(fn(
                 self._h, ctypes.byref(lk), _lib.ptr(t_std), _lib.ptr(t_mean), _lib.ptr(lo_t), _lib.ptr(hi_t), _lib.ptr(z), _lib.ptr(lp),
                 _lib.ptr(logl), _lib.ptr(out['z']) if steps > 0 else None, _lib.ptr(out['x']), _lib.ptr(out['lp']), _lib.ptr(out['logl']),
@@ -504,6 +521,20 @@ class _HipFlow(object):
             raise NotImplementedError('no fused mixed random-walk Metropolis kernel for %s' % type(self).__name__)
         with torch.cuda.device(self.device):
             rc = fn(self._h, int(like_id))
+        if rc == _lib.NNEST_OK:
+            return None
+        msg = self._lib.nnest_hip_last_error()
+        return msg.decode() if msg else 'error %d' % rc
+
+    def mcmc_gdata_refusal(self, D=None):
+        """why `mcmc_steps` with a like_data of dimension D (None: the flow's own) would refuse this flow (its shape, its base) -- the
+        library's own words (the family's `mcmc_gdata_check` entry; nothing is launched) --, or None where it is taken.
+        NotImplementedError for a family without such a kernel"""
+        fn = self._sym.get('mcmc_gdata_check')
+        if fn is None or 'mcmc_gdata' not in self._sym:
+            raise NotImplementedError('no fused random-walk Metropolis kernel for %s on a Gaussian likelihood from user data' % type(self).__name__)
+        with torch.cuda.device(self.device):
+            rc = fn(self._h, self.D if D is None else int(D))
         if rc == _lib.NNEST_OK:
             return None
         msg = self._lib.nnest_hip_last_error()
@@ -814,7 +845,8 @@ class HipNVP(_PaddedVectors, _HipFlow):
                    importance='nnest_importance_evidence', importance_check='nnest_importance_check',
                    mcmc_tempered='nnest_mcmc_tempered_steps', mcmc_mixed='nnest_mcmc_mixed_steps',
                    mcmc_mixed_check='nnest_mcmc_mixed_check', mcmc_adapt='nnest_mcmc_adapt_steps',
-                   mcmc_adapt_check='nnest_mcmc_adapt_check')
+                   mcmc_adapt_check='nnest_mcmc_adapt_check', mcmc_gdata='nnest_mcmc_gdata_steps',
+                   mcmc_gdata_check='nnest_mcmc_gdata_check')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (_PaddedVectors)
         with torch.cuda.device(self.device):
@@ -1054,6 +1086,34 @@ def mcmc_fill_noise(steps, C, D, seed=0, step0=0, walker_offset=0, device=None):
                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset) & 0xFFFFFFFFFFFFFFFF,
                                                      _lib.current_stream(dev)))
     return dz, u
+
+
+def gdata_spec(data, device):
+    """the nnest_gdata_t of a Gaussian likelihood from user data on `device`: data = the mapping likelihoods.GaussianData.hip_like_data
+    holds (mu [D] and R [D, D] float32, arrays or tensors; logl0).  Arrays already on the device are used as they are.  Returns
+    (spec, keep): `keep` holds the staged tensors the spec points into"""
+    mu = _as_dev_f32(data['mu'], device).reshape(-1)   # (a [D] array comes back as [1, D])
+    R = _as_dev_f32(data['R'], device)
+    D = mu.shape[0]
+    if D < 1 or R.shape != (D, D):
+        raise ValueError('like_data: mu must be shaped [D] and R [D, D], got %s and %s' % (tuple(mu.shape), tuple(R.shape)))
+    return _lib.GdataSpec(mu.data_ptr(), R.data_ptr(), float(data['logl0']), D), (mu, R)
+
+
+def loglike_gdata(data, t, device=None):
+    """the Gaussian likelihood from user data alone (nnest_loglike_gdata; include/nnest_hip.h has the arithmetic): data as
+    `gdata_spec` takes it, t [N, D] rows that are already T(x) (float32 on the device, or anything convertible).  Returns logL [N]
+    float64 on the device.  Asynchronous on the current stream."""
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    t = _as_dev_f32(t, dev).contiguous()
+    if t.dim() != 2:
+        raise ValueError('loglike_gdata: t must be shaped [N, D], got %s' % (tuple(t.shape),))
+    N, D = t.shape
+    out = torch.empty(N, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        spec, keep = gdata_spec(data, dev)
+        _lib.check(_lib.load().nnest_loglike_gdata(ctypes.byref(spec), _lib.ptr(t), _lib.ptr(out), N, D, _lib.current_stream(dev)))
+    return out
 
 
 SMC_MAX_PARTICLES = 1 << 20   # the population nnest_smc_reweight and nnest_smc_resample take (one workgroup each)

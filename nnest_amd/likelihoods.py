@@ -186,3 +186,91 @@ class DoubleGaussianShell(Likelihood):
     def loglike_rows(self, x):
         return np.logaddexp(np.log(self.weights[0]) + self.shell1.loglike_rows(x),
                             np.log(self.weights[1]) + self.shell2.loglike_rows(x))
+
+
+class GaussianData(Likelihood):
+    """A multivariate Gaussian whose mean and covariance come from the user's data (build-defined: the reference has none):
+        logL(theta) = logl_max - 1/2 (theta - mean)^T P (theta - mean),
+    P the precision matrix -- `precision`, or the inverse of `cov`; exactly one of the two is given.  A linear model with Gaussian
+    noise (`from_linear_model`), a Fisher or Laplace approximation, a compressed data vector.  ValueError for a wrong shape, a
+    non-finite entry, a matrix that is not symmetric positive definite, x_dim outside 1 .. 128.
+    The host evaluation is float64 from P.  `hip_like_id` stays None -- no NNEST_LIKE_* id stands for this likelihood, and every
+    route that keys on one treats the object as a Python callable --; `hip_like_data` carries what the fused Metropolis kernels of
+    this likelihood take (include/nnest_hip.h nnest_gdata_t): mu float32 [D]; R float32 [D, D], upper triangular, the float32
+    rounding of L^T with P = L L^T in float64; logl0 = logl_max."""
+    MAX_DIM = 128
+
+    def __init__(self, mean, cov=None, precision=None, logl_max=0.0):
+        if (cov is None) == (precision is None):
+            raise ValueError('GaussianData: exactly one of cov and precision')
+        mean = np.array(mean, dtype=np.float64)
+        if mean.ndim != 1 or not 1 <= mean.shape[0] <= self.MAX_DIM:
+            raise ValueError('GaussianData: mean must be shaped [x_dim] with x_dim in 1 .. %d, got %s' % (self.MAX_DIM, mean.shape))
+        D = mean.shape[0]
+        what = 'cov' if precision is None else 'precision'
+        M = np.array(cov if precision is None else precision, dtype=np.float64)
+        if M.shape != (D, D):
+            raise ValueError('GaussianData: %s must be shaped [%d, %d], got %s' % (what, D, D, M.shape))
+        logl_max = float(logl_max)
+        if not (np.all(np.isfinite(mean)) and np.all(np.isfinite(M)) and np.isfinite(logl_max)):
+            raise ValueError('GaussianData: mean, %s and logl_max must be finite' % what)
+        # symmetric to float64 rounding: a few ulp of the entries' scale (a product such as A^T N^-1 A rounds its two triangles apart)
+        if np.max(np.abs(M - M.T)) > 64 * np.finfo(np.float64).eps * np.max(np.abs(M)):
+            raise ValueError('GaussianData: %s is not symmetric' % what)
+        M = 0.5 * (M + M.T)
+        try:
+            np.linalg.cholesky(M)
+            P = M if precision is not None else np.linalg.inv(M)
+            P = 0.5 * (P + P.T)
+            L = np.linalg.cholesky(P)
+        except np.linalg.LinAlgError:
+            raise ValueError('GaussianData: %s is not positive definite' % what)
+        super(GaussianData, self).__init__(D)
+        self.mean, self.precision, self.logl_max = mean, P, logl_max
+        R = np.triu(L.T).astype(np.float32)   # (triu: exact zeros below the diagonal)
+        self.hip_like_data = dict(mu=mean.astype(np.float32), R=R, logl0=logl_max)
+
+    @classmethod
+    def from_linear_model(cls, A, y, noise_cov):
+        """the likelihood of theta in y = A theta + noise, noise ~ N(0, N): A [n, x_dim], y [n], noise_cov a scalar variance, a vector
+        of n variances or an [n, n] covariance.  P = A^T N^-1 A, mean = P^-1 A^T N^-1 y, and logl_max the residual term, so that
+        loglike(theta) = -1/2 (A theta - y)^T N^-1 (A theta - y) to float64 rounding.  ValueError when P is singular (the data do
+        not determine theta)."""
+        A = np.array(A, dtype=np.float64)
+        y = np.array(y, dtype=np.float64)
+        if A.ndim != 2 or y.shape != (A.shape[0],):
+            raise ValueError('from_linear_model: A must be shaped [n, x_dim] and y [n], got %s and %s' % (A.shape, y.shape))
+        n = A.shape[0]
+        N = np.array(noise_cov, dtype=np.float64)
+        if not (np.all(np.isfinite(A)) and np.all(np.isfinite(y)) and np.all(np.isfinite(N))):
+            raise ValueError('from_linear_model: A, y and noise_cov must be finite')
+        try:
+            if N.ndim == 0 or N.shape == (n,):
+                if not np.all(N > 0):
+                    raise ValueError('from_linear_model: the noise variances must be positive')
+                NiA, Niy = A / (N if N.ndim == 0 else N[:, None]), y / N
+            elif N.shape == (n, n):
+                c = np.linalg.cholesky(0.5 * (N + N.T))
+                solve = lambda b: np.linalg.solve(c.T, np.linalg.solve(c, b))
+                NiA, Niy = solve(A), solve(y)
+            else:
+                raise ValueError('from_linear_model: noise_cov must be a scalar, [n] or [n, n], got %s' % (N.shape,))
+            P = A.T @ NiA
+            P = 0.5 * (P + P.T)
+            b = A.T @ Niy
+            np.linalg.cholesky(P)
+            if np.linalg.cond(P) > 1.0 / (64 * np.finfo(np.float64).eps):
+                raise np.linalg.LinAlgError('singular')
+            mean = np.linalg.solve(P, b)
+        except np.linalg.LinAlgError:
+            raise ValueError('from_linear_model: A^T N^-1 A is singular: the data do not determine theta (or noise_cov is not positive definite)')
+        res = A @ mean - y
+        return cls(mean, precision=P, logl_max=-0.5 * float(res @ (NiA @ mean - Niy)))   # (N^-1 (A mean - y))
+
+    def loglike_rows(self, x):
+        d = np.asarray(x, dtype=np.float64) - self.mean
+        return self.logl_max - 0.5 * np.einsum('ni,ij,nj->n', d, self.precision, d)
+
+    @property
+    def max_loglike(self):
+        return self.logl_max

@@ -235,6 +235,19 @@ class Sampler(object):
             self.logger.warning('%slikelihood id %d disagrees with the host callable; using the host protocol' % (warn, like_id))
         return ok
 
+    def _probe_agrees_gdata(self, data, affine, warn=''):
+        """`_probe_agrees` for a Gaussian likelihood from user data: does the kernels' evaluation of the descriptor `data`
+        (flow.loglike_gdata) agree with the host callable, on the same 32 points under the same tolerances?  Warns where it does not"""
+        from . import flow
+        x = np.random.RandomState(4321).uniform(-1, 1, size=(32, self.x_dim)).astype(np.float32)
+        x = x * np.asarray(affine[0], np.float32) + np.asarray(affine[1], np.float32)
+        dev = flow.loglike_gdata(data, x, device=self.trainer.netG.device).cpu().numpy()
+        host = np.asarray(self._user_loglike(x.astype(np.float64)), dtype=np.float64)
+        ok = bool(np.allclose(dev, host, rtol=1e-5, atol=1e-4))
+        if not ok:
+            self.logger.warning('%sthe likelihood\'s hip_like_data disagrees with the host callable; using the host protocol' % warn)
+        return ok
+
     def _next_seed(self):
         """64-bit seed for the in-kernel Philox streams.  Drawn from a PRIVATE generator seeded once from the seed of torch's
         CPU generator (torch.manual_seed): the global generator is never advanced by the build's own bookkeeping, so the
@@ -750,6 +763,8 @@ class Sampler(object):
     ENTRY_KERNEL = {'mcmc': 'random-walk Metropolis', 'mcmc_tempered': 'tempered random-walk Metropolis', 'importance': 'importance-sampling',
                     'mcmc_mixed': 'mixed (local and global step) Metropolis', 'mcmc_adapt': 'adaptive-step Metropolis'}
 
+    GDATA_ENTRIES = ('mcmc', 'mcmc_tempered', 'mcmc_mixed', 'mcmc_adapt')   # what the `mcmc_gdata` entry of a flow stands in for
+
     def _device_target(self, affine=None, entry=None, unit_box_on_x=False):
         """(target, None) where the likelihood and the prior run on the device under the transform `affine` = (std, mean) (None:
         `_ensemble_affine()`), else (None, what is not taken: the words the front ends put after 'the fused route does not take').
@@ -760,7 +775,9 @@ class Sampler(object):
         and, for 'importance', 'mcmc_mixed' and 'mcmc_adapt', the library must take the flow's shape and base (`importance_refusal`,
         `mcmc_mixed_refusal`, `mcmc_adapt_refusal`: nothing is launched).  The ensemble routes name none:
         they fall back to rounds.  One probe of the host callable (`_probe_agrees`) per call: a run resolves once and hands the
-        target down"""
+        target down.  A likelihood without an id but with a `hip_like_data` (likelihoods.GaussianData) is taken for the Metropolis
+        entries (GDATA_ENTRIES) where the flow's `mcmc_gdata` entry is bound and takes the flow (`mcmc_gdata_refusal`) and the
+        descriptor agrees with the host callable (`_probe_agrees_gdata`): the target then has like_id None and the data"""
         affine = self._ensemble_affine() if affine is None else affine
         netG = self.trainer.netG
         if self.num_derived != 0:
@@ -772,8 +789,16 @@ class Sampler(object):
                 return None, 'the flow %s (no fused %s kernel)' % (type(netG).__name__, self.ENTRY_KERNEL[need])
         like = self._user_loglike
         like_id = getattr(like, 'hip_like_id', None)
-        if like_id is None:
+        like_data = getattr(like, 'hip_like_data', None) if like_id is None else None
+        if like_data is not None and not (entry in self.GDATA_ENTRIES and 'mcmc_gdata' in getattr(netG, '_sym', ())):
+            like_data = None
+        if like_id is None and like_data is None:
             return None, 'a likelihood the kernels do not know (a Python callable)'
+        if like_data is not None:   # (one kernel per family serves the four entries: its shapes and base, in the library's words)
+            why = netG.mcmc_gdata_refusal(len(like_data['mu']))
+            if why is not None:
+                return None, 'the flow %s: %s' % (type(netG).__name__, why)
+            entry = None   # (the checks by id below are not this likelihood's)
         if entry == 'importance':
             why = netG.importance_refusal(like_id)
             if why is not None:
@@ -797,6 +822,10 @@ class Sampler(object):
             ok = self._transform_prior and isinstance(prior, UniformPrior) and type(prior).__call__ is UniformPrior.__call__
             box = (prior.minimum, prior.maximum) if ok else None
         params = tuple(getattr(like, 'hip_like_params', ()) or ())
+        if like_data is not None:
+            if affine is None or box is None or not self._probe_agrees_gdata(like_data, affine, warn='mcmc: '):
+                return None, refused
+            return DeviceTarget(None, (), affine[0], affine[1], *box, like_data=like_data), None
         if affine is None or box is None or not self._probe_agrees(like_id, params, affine=affine, warn='ensemble: '):
             return None, refused
         return DeviceTarget(like_id, params, affine[0], affine[1], *box), None

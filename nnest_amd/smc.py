@@ -224,7 +224,10 @@ class SMCSampler(Sampler):
             raise ValueError('SMCSampler.run: num_particles=%d: the fused route takes up to %d' % (N, flow.SMC_MAX_PARTICLES))
         netG = self.trainer.netG
         theta = torch.as_tensor(np.asarray(self.sample_prior(N), np.float32)).to(netG.device).contiguous()
-        logl = flow.loglike(target.like_id, theta, 1.0, device=netG.device, like_params=target.like_params)
+        if target.like_data is not None:   # (a Gaussian likelihood from user data: no id, its own evaluator)
+            logl = flow.loglike_gdata(target.launch_kwargs(netG.device)['like_data'], theta, device=netG.device)
+        else:
+            logl = flow.loglike(target.like_id, theta, 1.0, device=netG.device, like_params=target.like_params)
         self.total_calls += N
         return theta, logl, None
 
