@@ -658,6 +658,65 @@ int nnest_spline_mcmc_gdata_steps(struct nnest_spline *spl, const nnest_gdata_t 
                                   float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta, int global_every,
                                   int *n_accept_global_dev, const double *step_in_dev, double *step_out_dev, double *hist_step_dev,
                                   uint32_t adapt_steps, double adapt_rate, double target_accept, void *stream);
+/* A GENERALISED LINEAR MODEL OF USER DATA -- logistic or Poisson (log-link) regression -- in the adaptive walk above, in kernels of
+ * their own (nnest_mcmc_glm.hip, nnest_spline_mcmc_glm.hip, glm_data.h).  BUILD-DEFINED.  No NNEST_LIKE_* id stands
+ * for it: the likelihood is compiled into these kernels, one per family, and described by nnest_glm_t.  (All added within ABI 15.)
+ *   eta_i = o_i + sum_c A[i, c] theta_c,   logL(theta) = logl0 + sum_{i < n} l_i,
+ *   NNEST_GLM_LOGISTIC: y_i in {0, 1},  l_i = -softplus((1 - 2 y_i) eta_i),  softplus(s) = max(s, 0) + log1p(exp(-|s|));
+ *   NNEST_GLM_POISSON:  y_i >= 0,       l_i = y_i eta_i - exp(eta_i)   (the caller puts -sum lgamma(y_i + 1) into logl0).
+ * nnest_glm_t: at_dev [D, ld] float32 = A^T with leading dimension ld (rows of A along the fast axis), y_dev [ld] and o_dev [ld]
+ *   float32 (o the offset: zeros for none); 1 <= n <= 65536 rows, ld >= n a multiple of 64, 1 <= D <= 128; logl0 finite.  What the
+ *   arrays hold at rows n .. ld - 1 does not matter: those rows are masked (softplus(0) is not 0).  The values of y are the
+ *   caller's business (likelihoods.GLMData checks them on the host).
+ * The arithmetic, with t = T(x) the float32 row the existing evaluators produce (or a row of t_dev):
+ *     eta_i = o_i + sum_c A[i, c] * t_c       float32; fused multiply-adds, in the kernel's own order
+ *     l_i                                     float64 from (double)eta_i, as written above; NaN where eta_i is not finite
+ *     logL  = logl0 + sum_{i < n} l_i         float64, in a fixed order per entry; -1e100 where that is not finite
+ *   So a logistic logL <= logl0 always, a row with a non-finite coordinate gives -1e100, and the same row gives the same bits in
+ *   any position of any launch of one entry.  (The two walks order the sums differently: their values agree to rounding.)
+ * nnest_loglike_glm: the likelihood alone on N rows t_dev [N, D] float32 that are already T(x); logl_dev [N] float64.  D must be
+ *   the descriptor's.  N = 0 launches nothing.
+ * nnest_mcmc_glm_steps, nnest_spline_mcmc_glm_steps: the arguments of nnest_mcmc_adapt_steps / nnest_spline_mcmc_adapt_steps with
+ *   `const nnest_glm_t *glm` in place of `const nnest_like_t *like`.  The run is the adaptive walk's in every respect -- draws,
+ *   schedule, weight, accept rule, step rule, beta, lp_in_dev / logl_in_dev, histories, counters, steps = 0, the cut into launches,
+ *   a shard by walker_offset --; only logL differs.  With adapt_steps = 0 and step_in_dev NULL it is the mixed walk on this
+ *   likelihood, with global_every = 0 besides the tempered random walk, at beta = 1.0 the plain one.
+ * NNEST_E_ARG before any launch, the outputs untouched: glm NULL, a NULL at_dev, y_dev or o_dev, D outside 1 .. 128 or not the
+ *   flow's x_dim (not the D argument of nnest_loglike_glm), n outside 1 .. 65536, ld < n or not a multiple of 64 or above 65536, a
+ *   family that is neither of the two, logl0 not finite, and every argument error of the adaptive entries.
+ *   NNEST_E_UNSUPPORTED before any launch: what the _check entry refuses.
+ * nnest_mcmc_glm_check, nnest_spline_mcmc_glm_check: NNEST_OK where the entry takes this handle (its shape and base: what
+ *   nnest_mcmc_adapt_check / nnest_spline_mcmc_adapt_check take) and a descriptor of dimension D, else NNEST_E_UNSUPPORTED -- or
+ *   NNEST_E_ARG for a D that is not the flow's x_dim -- with the reason in nnest_hip_last_error(); nothing is launched. */
+#define NNEST_GLM_LOGISTIC 0
+#define NNEST_GLM_POISSON 1
+typedef struct nnest_glm {
+    const float *at_dev;
+    const float *y_dev;
+    const float *o_dev;
+    double logl0;
+    int n;
+    int ld;
+    int D;
+    int family;
+} nnest_glm_t;
+int nnest_loglike_glm(const nnest_glm_t *glm, const float *t_dev, double *logl_dev, int N, int D, void *stream);
+int nnest_mcmc_glm_check(nnest_nvp_t *nvp, int D);
+int nnest_spline_mcmc_glm_check(struct nnest_spline *spl, int D);
+int nnest_mcmc_glm_steps(nnest_nvp_t *nvp, const nnest_glm_t *glm, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                         const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev,
+                         float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev, float *hist_x_dev,
+                         double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size, uint64_t step0, uint64_t seed,
+                         uint64_t walker_offset, double beta, int global_every, int *n_accept_global_dev, const double *step_in_dev,
+                         double *step_out_dev, double *hist_step_dev, uint32_t adapt_steps, double adapt_rate, double target_accept,
+                         void *stream);
+int nnest_spline_mcmc_glm_steps(struct nnest_spline *spl, const nnest_glm_t *glm, const float *t_std_dev, const float *t_mean_dev,
+                                const float *lo_dev, const float *hi_dev, const float *z_in_dev, const double *lp_in_dev,
+                                const double *logl_in_dev, float *z_out_dev, float *x_out_dev, double *lp_out_dev, double *logl_out_dev,
+                                float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C, int steps,
+                                float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta, int global_every,
+                                int *n_accept_global_dev, const double *step_in_dev, double *step_out_dev, double *hist_step_dev,
+                                uint32_t adapt_steps, double adapt_rate, double target_accept, void *stream);
 /* IMPORTANCE-SAMPLED EVIDENCE with the trained flow as the proposal: Z = E_q[L(T(x)) pi(T(x)) / q(x)], drawn, evaluated and reduced
  * inside one kernel.  BUILD-DEFINED: the reference has no such estimator.  Sample m is a global 64-bit index; row k of a launch of M
  * samples is m = sample_offset + k:

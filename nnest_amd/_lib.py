@@ -108,6 +108,16 @@ class GdataSpec(ctypes.Structure):
     _fields_ = [('mu_dev', ctypes.c_void_p), ('r_dev', ctypes.c_void_p), ('logl0', ctypes.c_double), ('D', ctypes.c_int)]
 
 
+class GlmSpec(ctypes.Structure):
+    """nnest_glm_t (include/nnest_hip.h): a regression likelihood of user data -- device pointers of A^T [D, ld], y [ld] and the
+    offset [ld], logl0, n, ld, D, family (GLM_FAMILIES)"""
+    _fields_ = [('at_dev', ctypes.c_void_p), ('y_dev', ctypes.c_void_p), ('o_dev', ctypes.c_void_p), ('logl0', ctypes.c_double),
+                ('n', ctypes.c_int), ('ld', ctypes.c_int), ('D', ctypes.c_int), ('family', ctypes.c_int)]
+
+
+GLM_FAMILIES = {'logistic': 0, 'poisson': 1}   # NNEST_GLM_LOGISTIC, NNEST_GLM_POISSON
+
+
 class TrainResult(ctypes.Structure):
     _fields_ = [('epochs_run', ctypes.c_int), ('best_epoch', ctypes.c_int),
                 ('best_validation_loss', ctypes.c_float), ('last_train_loss', ctypes.c_float),
@@ -257,6 +267,14 @@ SIGNATURES = {
     'nnest_loglike_gdata': [_vp, _vp, _vp, _i, _i, _vp],
     'nnest_mcmc_gdata_check': [_vp, _i],
     'nnest_spline_mcmc_gdata_check': [_vp, _i],
+    # the regression likelihoods of user data: the same three forms with `const nnest_glm_t *glm`
+    'nnest_mcmc_glm_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64, _u64,
+                             _u64, _d, _i, _vp, _vp, _vp, _vp, _u32, _d, _d, _vp],
+    'nnest_spline_mcmc_glm_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64,
+                                    _u64, _u64, _d, _i, _vp, _vp, _vp, _vp, _u32, _d, _d, _vp],
+    'nnest_loglike_glm': [_vp, _vp, _vp, _i, _i, _vp],
+    'nnest_mcmc_glm_check': [_vp, _i],
+    'nnest_spline_mcmc_glm_check': [_vp, _i],
     # (logl_dev, N, beta, ess_fraction, out_dev [4], m_dev [N] int64, stream)
     'nnest_smc_reweight': [_vp, _i, _d, _d, _vp, _vp, _vp],
     # (m_dev, N, D, seed, stage, theta_in_dev, logl_in_dev, anc_out_dev, theta_out_dev, logl_out_dev, stream)

@@ -13,6 +13,7 @@
 #include "mcmc_mixed.h"
 #include "mcmc_adapt.h"
 #include "mcmc_gdata.h"
+#include "glm_data.h"
 
 using namespace nnest;
 
@@ -456,6 +457,22 @@ int nnest::gdata_ok(const nnest_gdata_t *g, int D, GdataSpec *out) {
     out->mu = g->mu_dev; out->r = g->r_dev; out->logl0 = g->logl0; out->D = g->D;
     return NNEST_OK;
 }
+// D: what the descriptor's dimension must be (the flow's x_dim, or the D argument of nnest_loglike_glm)
+int nnest::glm_ok(const nnest_glm_t *g, int D, GlmSpec *out) {
+    if (!g) return fail(NNEST_E_ARG, "glm is NULL");
+    if (!g->at_dev || !g->y_dev || !g->o_dev) return fail(NNEST_E_ARG, "glm: NULL at_dev, y_dev or o_dev");
+    if (g->D < 1 || g->D > 128) return fail(NNEST_E_ARG, "glm: D=%d (1 .. 128)", g->D);
+    if (g->D != D) return fail(NNEST_E_ARG, "glm: the likelihood's D=%d is not D=%d", g->D, D);
+    if (g->n < 1 || g->n > GLM_MAX_ROWS) return fail(NNEST_E_ARG, "glm: n=%d (1 .. %d rows)", g->n, GLM_MAX_ROWS);
+    if (g->ld < g->n || g->ld > GLM_MAX_ROWS || g->ld % 64 != 0)
+        return fail(NNEST_E_ARG, "glm: ld=%d (a multiple of 64, n=%d .. %d)", g->ld, g->n, GLM_MAX_ROWS);
+    if (g->family != NNEST_GLM_LOGISTIC && g->family != NNEST_GLM_POISSON)
+        return fail(NNEST_E_ARG, "glm: family=%d (NNEST_GLM_LOGISTIC = 0, NNEST_GLM_POISSON = 1)", g->family);
+    if (!isfinite(g->logl0)) return fail(NNEST_E_ARG, "glm: logl0=%g (finite)", g->logl0);
+    out->at = g->at_dev; out->y = g->y_dev; out->o = g->o_dev; out->logl0 = g->logl0;
+    out->n = g->n; out->ld = g->ld; out->D = g->D; out->family = g->family;
+    return NNEST_OK;
+}
 int nnest::importance_args(ImpArgs *a, const float *t_std, const float *t_mean, const float *lo, const float *hi, float *z_out, float *x_out,
                            double *logl_out, double *logw_out, double *partials, double *sums, int M, uint64_t seed, uint64_t sample_offset) {
     if (M < 0 || M > (1 << 30)) return fail(NNEST_E_ARG, "importance: M=%d (0 .. 2^30 samples a launch)", M);
@@ -727,6 +744,67 @@ int nnest_mcmc_gdata_steps(nnest_nvp_t *h, const nnest_gdata_t *gdata, const flo
     hipError_t e = launch_mcmc_gdata(h->s, h->w, a, (hipStream_t)stream);
     if (e == hipErrorInvalidConfiguration) return fail(NNEST_E_UNSUPPORTED, "mcmc gdata: x_dim=%d not instantiated", h->s.D);
     if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_mcmc_gdata: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+// the regression likelihoods of the user's data (nnest_mcmc_glm.hip, glm_data.h): the likelihood alone
+int nnest_loglike_glm(const nnest_glm_t *glm, const float *t_dev, double *logl_dev, int N, int D, void *stream) {
+    GlmSpec gl;
+    int rc;
+    if ((rc = glm_ok(glm, D, &gl))) return rc;
+    if (N < 0) return fail(NNEST_E_ARG, "loglike glm: N=%d (>= 0)", N);
+    if (N > 0 && (!t_dev || !logl_dev)) return fail(NNEST_E_ARG, "NULL device buffer");
+    hipError_t e = launch_loglike_glm(gl, t_dev, logl_dev, N, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_loglike_glm: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+// what nnest_mcmc_glm_steps takes, asked before a launch (and by the entry itself): the shapes and the base of
+// nnest_mcmc_adapt_check, and a descriptor of the flow's x_dim
+int nnest_mcmc_glm_check(nnest_nvp_t *h, int D) {
+    if (!h) return fail(NNEST_E_ARG, "NULL handle");
+    if (h->s.base_beta != 0.f)
+        return fail(NNEST_E_UNSUPPORTED, "mcmc glm: GeneralisedNormal base (beta=%g): the kernel draws from N(0, I) only", (double)h->s.base_beta);
+    if (!ensemble_form_eligible(h->s))
+        return fail(NNEST_E_UNSUPPORTED, "mcmc glm: x_dim=%d hidden=%d blocks=%d layers=%d scale mode %d: the kernel takes hidden 16, 3 blocks, "
+                    "1 layer, scale '' (the one-walker-per-wave layout), x_dim <= 128", h->s.D, h->s.H, h->s.B, h->s.L, h->s.scale_mode);
+    if (h->s.NT < 1 || h->s.NT > 4) return fail(NNEST_E_UNSUPPORTED, "mcmc glm: x_dim=%d not instantiated", h->s.D);
+    if (D != h->s.D) return fail(NNEST_E_ARG, "mcmc glm: the likelihood's D=%d is not the flow's x_dim=%d", D, h->s.D);
+    return NNEST_OK;
+}
+
+// (as nnest_mcmc_adapt_steps: the checks that need no handle come first)
+int nnest_mcmc_glm_steps(nnest_nvp_t *h, const nnest_glm_t *glm, const float *t_std_dev, const float *t_mean_dev, const float *lo_dev,
+                           const float *hi_dev, const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev,
+                           float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev, float *hist_x_dev,
+                           double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size, uint64_t step0, uint64_t seed,
+                           uint64_t walker_offset, double beta, int global_every, int *n_accept_global_dev, const double *step_in_dev,
+                           double *step_out_dev, double *hist_step_dev, uint32_t adapt_steps, double adapt_rate, double target_accept,
+                           void *stream) {
+    McmcGlmArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc;
+    if ((rc = glm_ok(glm, glm ? glm->D : 0, &a.gl))) return rc;
+    if ((rc = mcmc_beta_ok(beta))) return rc;
+    if ((rc = mcmc_mixed_every_ok(global_every))) return rc;
+    if ((rc = mcmc_adapt_rule_ok(adapt_rate, target_accept))) return rc;
+    a.beta = beta;
+    a.global_every = global_every;
+    a.n_accept_global = n_accept_global_dev;
+    a.step_in = step_in_dev;
+    a.step_out = step_out_dev;
+    a.hist_step = hist_step_dev;
+    a.adapt_steps = adapt_steps;
+    a.adapt_rate = adapt_rate;
+    a.target_accept = target_accept;
+    rc = mcmc_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev, lp_out_dev,
+                   logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0, seed, walker_offset);
+    if (rc) return rc;
+    if ((rc = nnest_mcmc_glm_check(h, a.gl.D))) return rc;
+    a.like.scale = 1.0f;
+    hipError_t e = launch_mcmc_glm(h->s, h->w, a, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(NNEST_E_UNSUPPORTED, "mcmc glm: x_dim=%d not instantiated", h->s.D);
+    if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_mcmc_glm: %s", hipGetErrorString(e));
     return NNEST_OK;
 }
 

@@ -1,10 +1,11 @@
 """DeviceTarget: what the fused routes hand a kernel as the target -- the likelihood (an id the kernels know and its parameters, or
-the descriptor of a Gaussian likelihood from user data: `like_data`, with like_id None), the
+the descriptor of a Gaussian likelihood from user data: `like_data`, or of a regression likelihood of user data: `like_glm`, with
+like_id None), the
 affine T(x) = x * t_std + t_mean the likelihood sees, and the prior box [lo, hi] on T(x).  `Sampler._device_target` decides it, once
 per run; every launch of the run takes the same staged tensors (`launch_kwargs`)."""
 import numpy as np
 
-_FIXED = ('like_id', 'like_params', 't_std', 't_mean', 'lo', 'hi', 'like_data')
+_FIXED = ('like_id', 'like_params', 't_std', 't_mean', 'lo', 'hi', 'like_data', 'like_glm')
 
 
 def affine_on_device(x, t_std, t_mean):
@@ -16,15 +17,17 @@ class DeviceTarget(object):
     """like_id, like_params; t_std, t_mean: float32 [D] or both None (the identity); lo, hi: float32 [D] or both None (no prior).
     like_data: None, or the descriptor of a Gaussian likelihood from user data (likelihoods.GaussianData.hip_like_data: mu, R,
     logl0) -- like_id is then None, and the Metropolis bindings route on the `like_data` keyword.
+    like_glm: None, or the descriptor of a regression likelihood of user data (likelihoods.GLMData.hip_like_glm: at, y, o, logl0, n,
+    family) -- like_id and like_data are then None, and the Metropolis bindings route on the `like_glm` keyword.
     The fields are fixed once set: another transform is another target (`with_transform`), so tensors staged for one (std, mean)
     never serve another."""
 
-    def __init__(self, like_id, like_params=(), t_std=None, t_mean=None, lo=None, hi=None, like_data=None):
+    def __init__(self, like_id, like_params=(), t_std=None, t_mean=None, lo=None, hi=None, like_data=None, like_glm=None):
         if (t_std is None) != (t_mean is None) or (lo is None) != (hi is None):
             raise ValueError('DeviceTarget: t_std and t_mean, and lo and hi: both or neither')
         vec = lambda v: None if v is None else np.array(v, np.float32).reshape(-1)   # (a copy, cast as the bindings cast)
-        if (like_id is None) == (like_data is None):
-            raise ValueError('DeviceTarget: a like_id, or like_id None with a like_data')
+        if (like_id is not None) + (like_data is not None) + (like_glm is not None) != 1:
+            raise ValueError('DeviceTarget: a like_id, or like_id None with a like_data or with a like_glm')
         self.like_id, self.like_params = None if like_id is None else int(like_id), tuple(like_params or ())
         if like_data is not None:   # (copies, cast as the bindings cast)
             like_data = dict(mu=np.array(like_data['mu'], np.float32).reshape(-1), R=np.array(like_data['R'], np.float32),
@@ -32,6 +35,13 @@ class DeviceTarget(object):
             like_data['mu'].setflags(write=False)
             like_data['R'].setflags(write=False)
         self.like_data = like_data
+        if like_glm is not None:   # (copies, cast as the bindings cast)
+            like_glm = dict(at=np.array(like_glm['at'], np.float32), y=np.array(like_glm['y'], np.float32).reshape(-1),
+                            o=np.array(like_glm['o'], np.float32).reshape(-1), logl0=float(like_glm['logl0']), n=int(like_glm['n']),
+                            family=like_glm['family'])
+            for k in ('at', 'y', 'o'):
+                like_glm[k].setflags(write=False)
+        self.like_glm = like_glm
         self.t_std, self.t_mean, self.lo, self.hi = vec(t_std), vec(t_mean), vec(lo), vec(hi)
         for v in (self.t_std, self.t_mean, self.lo, self.hi):
             if v is not None:
@@ -45,11 +55,12 @@ class DeviceTarget(object):
 
     def with_transform(self, t_std, t_mean):
         """the same likelihood and box under T(x) = x * t_std + t_mean: neither depends on T, so nothing is checked again"""
-        return DeviceTarget(self.like_id, self.like_params, t_std, t_mean, self.lo, self.hi, self.like_data)
+        return DeviceTarget(self.like_id, self.like_params, t_std, t_mean, self.lo, self.hi, self.like_data, self.like_glm)
 
     def launch_kwargs(self, device):
         """the keywords the flow bindings take (t_std, t_mean, lo, hi as float32 tensors on `device`, and like_params; with a
-        like_data, and only then, `like_data` with mu and R as float32 tensors on `device`): staged on the first call for a device,
+        like_data, and only then, `like_data` with mu and R as float32 tensors on `device`; with a like_glm, and only then,
+        `like_glm` with at, y and o likewise): staged on the first call for a device,
         the same tensors after it"""
         from . import flow
         key = str(device)
@@ -59,6 +70,9 @@ class DeviceTarget(object):
             if self.like_data is not None:
                 _, (mu, R) = flow.gdata_spec(self.like_data, device)
                 self._staged[key]['like_data'] = dict(mu=mu, R=R, logl0=self.like_data['logl0'])
+            if self.like_glm is not None:
+                _, (at, y, o) = flow.glm_spec(self.like_glm, device)
+                self._staged[key]['like_glm'] = dict(self.like_glm, at=at, y=y, o=o)
         return dict(self._staged[key])
 
     def transform(self, x):

@@ -408,7 +408,7 @@ class _HipFlow(object):
 
     def mcmc_steps(self, like_id, z, steps, step_size, t_std=None, t_mean=None, lo=None, hi=None, lp=None, logl=None, seed=0, step0=0,
                    walker_offset=0, like_params=None, history=True, beta=None, global_every=0, step_in=None, adapt_steps=0, adapt_rate=1.0,
-                   target_accept=0.234, like_data=None):
+                   target_accept=0.234, like_data=None, like_glm=None):
         """`steps` steps of random-walk Metropolis in latent space with the likelihood, the prior and the Jacobian in the ratio, in ONE
         launch (the family's `mcmc` entry point: nnest_mcmc_steps, nnest_spline_mcmc_steps; build-defined stream, the reference's move:
         include/nnest_hip.h has the definition).  z [C, D] float32 on the device: the walkers' start; lp, logl [C] float64: the
@@ -440,6 +440,10 @@ class _HipFlow(object):
         through the family's `mcmc_gdata` entry (nnest_mcmc_gdata_steps, nnest_spline_mcmc_gdata_steps: the adaptive walk with that
         likelihood compiled in) whatever beta, global_every, adapt_steps and step_in are; the result carries the keys the same
         arguments give above.
+        like_glm: None -- the entries above, as they were; the descriptor of a regression likelihood of user data
+        (likelihoods.GLMData.hip_like_glm: at [D, ld], y [ld], o [ld] float32, logl0, n, family) -- `like_id` and `like_data` must
+        then be None, and the run goes through the family's `mcmc_glm` entry (nnest_mcmc_glm_steps, nnest_spline_mcmc_glm_steps)
+        in the same way, with the same keys.
         NotImplementedError for a family without such a kernel (its handle must not reach another family's)."""
         global_every = int(global_every)
         if global_every < 0:
@@ -449,15 +453,18 @@ class _HipFlow(object):
             raise ValueError('mcmc_steps: adapt_steps=%d (>= 0)' % adapt_steps)
         adapt = adapt_steps > 0 or step_in is not None
         mixed = global_every > 0
-        gdata = like_data is not None
+        glm = like_glm is not None
+        if glm and (like_id is not None or like_data is not None):
+            raise ValueError('mcmc_steps: like_glm goes with like_id=None and like_data=None')
+        gdata = like_data is not None or glm   # (either descriptor: the adaptive entry's arguments, whatever the options)
         if gdata and like_id is not None:
             raise ValueError('mcmc_steps: like_data goes with like_id=None, got like_id=%r' % (like_id,))
-        fn = self._sym.get('mcmc_gdata' if gdata else 'mcmc_adapt' if adapt else 'mcmc_mixed' if mixed else 'mcmc' if beta is None
+        fn = self._sym.get('mcmc_glm' if glm else 'mcmc_gdata' if gdata else 'mcmc_adapt' if adapt else 'mcmc_mixed' if mixed else 'mcmc' if beta is None
                            else 'mcmc_tempered')
         if fn is None:
             raise NotImplementedError('no fused %srandom-walk Metropolis kernel for %s%s' % (
                 'adaptive ' if adapt else 'mixed ' if mixed else '' if beta is None else 'tempered ', type(self).__name__,
-                ' on a Gaussian likelihood from user data' if gdata else ''))
+                ' on a regression likelihood of user data' if glm else ' on a Gaussian likelihood from user data' if gdata else ''))
         tempered = () if beta is None and not mixed and not adapt and not gdata else (ctypes.c_double(1.0 if beta is None else float(beta)),)
         dev = self.device
         z = _as_dev_f32(z, dev).contiguous()
@@ -500,7 +507,9 @@ class _HipFlow(object):
             tempered += (_lib.ptr(step_in), _lib.ptr(out['step']) if steps > 0 else None, _lib.ptr(out['hist_step']),
                          ctypes.c_uint32(min(adapt_steps, 0xFFFFFFFF)), ctypes.c_double(float(adapt_rate)), ctypes.c_double(float(target_accept)))
         with torch.cuda.device(dev):
-            if gdata:
+            if glm:
+                lk, keep = glm_spec(like_glm, dev)   # (`keep`, as below)
+            elif gdata:
                 lk, keep = gdata_spec(like_data, dev)   # (`keep`: the staged arrays, alive until the call has been enqueued)
             else:
                 lk = _lib.like_spec(like_id, 1.0, like_params)
@@ -533,6 +542,20 @@ class _HipFlow(object):
         fn = self._sym.get('mcmc_gdata_check')
         if fn is None or 'mcmc_gdata' not in self._sym:
             raise NotImplementedError('no fused random-walk Metropolis kernel for %s on a Gaussian likelihood from user data' % type(self).__name__)
+        with torch.cuda.device(self.device):
+            rc = fn(self._h, self.D if D is None else int(D))
+        if rc == _lib.NNEST_OK:
+            return None
+        msg = self._lib.nnest_hip_last_error()
+        return msg.decode() if msg else 'error %d' % rc
+
+    def mcmc_glm_refusal(self, D=None):
+        """why `mcmc_steps` with a like_glm of dimension D (None: the flow's own) would refuse this flow (its shape, its base) -- the
+        library's own words (the family's `mcmc_glm_check` entry; nothing is launched) --, or None where it is taken.
+        NotImplementedError for a family without such a kernel"""
+        fn = self._sym.get('mcmc_glm_check')
+        if fn is None or 'mcmc_glm' not in self._sym:
+            raise NotImplementedError('no fused random-walk Metropolis kernel for %s on a regression likelihood of user data' % type(self).__name__)
         with torch.cuda.device(self.device):
             rc = fn(self._h, self.D if D is None else int(D))
         if rc == _lib.NNEST_OK:
@@ -846,7 +869,8 @@ class HipNVP(_PaddedVectors, _HipFlow):
                    mcmc_tempered='nnest_mcmc_tempered_steps', mcmc_mixed='nnest_mcmc_mixed_steps',
                    mcmc_mixed_check='nnest_mcmc_mixed_check', mcmc_adapt='nnest_mcmc_adapt_steps',
                    mcmc_adapt_check='nnest_mcmc_adapt_check', mcmc_gdata='nnest_mcmc_gdata_steps',
-                   mcmc_gdata_check='nnest_mcmc_gdata_check')
+                   mcmc_gdata_check='nnest_mcmc_gdata_check', mcmc_glm='nnest_mcmc_glm_steps',
+                   mcmc_glm_check='nnest_mcmc_glm_check')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (_PaddedVectors)
         with torch.cuda.device(self.device):
@@ -1113,6 +1137,42 @@ def loglike_gdata(data, t, device=None):
     with torch.cuda.device(dev):
         spec, keep = gdata_spec(data, dev)
         _lib.check(_lib.load().nnest_loglike_gdata(ctypes.byref(spec), _lib.ptr(t), _lib.ptr(out), N, D, _lib.current_stream(dev)))
+    return out
+
+
+def glm_spec(data, device):
+    """the nnest_glm_t of a regression likelihood of user data on `device`: data = the mapping likelihoods.GLMData.hip_like_glm holds
+    (at [D, ld], y [ld], o [ld] float32, arrays or tensors; logl0; n; family 'logistic' | 'poisson' or the library's number).  Arrays
+    already on the device are used as they are.  Returns (spec, keep): `keep` holds the staged tensors the spec points into.
+    ValueError for misshapen arrays or an unknown family name; the ranges are the library's to refuse"""
+    at = _as_dev_f32(data['at'], device)
+    y = _as_dev_f32(data['y'], device).reshape(-1)   # (a [ld] array comes back as [1, ld])
+    o = _as_dev_f32(data['o'], device).reshape(-1)
+    if at.dim() != 2 or at.shape[0] < 1 or y.shape != (at.shape[1],) or o.shape != (at.shape[1],):
+        raise ValueError('like_glm: at must be shaped [D, ld], y and o [ld], got %s, %s and %s' % (tuple(at.shape), tuple(y.shape), tuple(o.shape)))
+    at, y, o = at.contiguous(), y.contiguous(), o.contiguous()
+    fam = data['family']
+    if isinstance(fam, str):
+        if fam not in _lib.GLM_FAMILIES:
+            raise ValueError('like_glm: family=%r (one of %s)' % (fam, sorted(_lib.GLM_FAMILIES)))
+        fam = _lib.GLM_FAMILIES[fam]
+    D, ld = at.shape
+    return _lib.GlmSpec(at.data_ptr(), y.data_ptr(), o.data_ptr(), float(data['logl0']), int(data['n']), ld, D, int(fam)), (at, y, o)
+
+
+def loglike_glm(data, t, device=None):
+    """a regression likelihood of user data alone (nnest_loglike_glm; include/nnest_hip.h has the arithmetic): data as `glm_spec`
+    takes it, t [N, D] rows that are already T(x) (float32 on the device, or anything convertible).  Returns logL [N] float64 on the
+    device.  Asynchronous on the current stream."""
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    t = _as_dev_f32(t, dev).contiguous()
+    if t.dim() != 2:
+        raise ValueError('loglike_glm: t must be shaped [N, D], got %s' % (tuple(t.shape),))
+    N, D = t.shape
+    out = torch.empty(N, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        spec, keep = glm_spec(data, dev)
+        _lib.check(_lib.load().nnest_loglike_glm(ctypes.byref(spec), _lib.ptr(t), _lib.ptr(out), N, D, _lib.current_stream(dev)))
     return out
 
 

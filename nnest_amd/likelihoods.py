@@ -274,3 +274,74 @@ class GaussianData(Likelihood):
     @property
     def max_loglike(self):
         return self.logl_max
+
+
+class GLMData(Likelihood):
+    """A generalised linear model of the user's data (build-defined: the reference has none): with the linear predictor
+    eta_i = offset_i + sum_c A[i, c] theta_c over the n rows of the design matrix A [n, x_dim],
+        family 'logistic': y_i in {0, 1},            logL = logl_const + sum_i -softplus((1 - 2 y_i) eta_i)
+        family 'poisson':  y_i in {0, 1, 2, ...},    logL = logl_const + sum_i (y_i eta_i - exp(eta_i) - lgamma(y_i + 1))
+    -- Bayesian logistic regression and Poisson regression with the log link, normalised.  ValueError for a wrong shape, a
+    non-finite entry, a y the family does not take, x_dim outside 1 .. 128, n outside 1 .. 65536, an unknown family.
+    The host evaluation is float64 from the float64 data (-1e100 where it is not finite, the kernels' rule).  `hip_like_id` stays
+    None -- no NNEST_LIKE_* id stands for this likelihood, and every route that keys on one treats the object as a Python callable
+    --; `hip_like_glm` carries what the fused Metropolis kernels of this likelihood take (include/nnest_hip.h nnest_glm_t): float32
+    at [x_dim, ld] = A^T with ld = n rounded up to a multiple of 64, zero padded, y [ld], o [ld]; logl0 (Poisson: logl_const -
+    sum_i lgamma(y_i + 1)); n; family."""
+    MAX_DIM = 128
+    MAX_ROWS = 65536
+    FAMILIES = ('logistic', 'poisson')
+
+    def __init__(self, A, y, family='logistic', offset=None, logl_const=0.0):
+        if family not in self.FAMILIES:
+            raise ValueError('GLMData: family=%r (one of %s)' % (family, ', '.join(self.FAMILIES)))
+        A = np.array(A, dtype=np.float64)
+        y = np.array(y, dtype=np.float64)
+        if A.ndim != 2 or not 1 <= A.shape[1] <= self.MAX_DIM or not 1 <= A.shape[0] <= self.MAX_ROWS:
+            raise ValueError('GLMData: A must be shaped [n, x_dim] with n in 1 .. %d and x_dim in 1 .. %d, got %s'
+                             % (self.MAX_ROWS, self.MAX_DIM, A.shape))
+        n, D = A.shape
+        if y.shape != (n,):
+            raise ValueError('GLMData: y must be shaped [%d], got %s' % (n, y.shape))
+        o = np.zeros(n) if offset is None else np.array(offset, dtype=np.float64)
+        if o.shape != (n,):
+            raise ValueError('GLMData: offset must be shaped [%d], got %s' % (n, o.shape))
+        logl_const = float(logl_const)
+        if not (np.all(np.isfinite(A)) and np.all(np.isfinite(y)) and np.all(np.isfinite(o)) and np.isfinite(logl_const)):
+            raise ValueError('GLMData: A, y, offset and logl_const must be finite')
+        if family == 'logistic' and not np.all((y == 0) | (y == 1)):
+            raise ValueError('GLMData: family logistic takes y in {0, 1}')
+        if family == 'poisson' and not (np.all(y >= 0) and np.all(y == np.round(y)) and np.all(y < 2 ** 24)):
+            raise ValueError('GLMData: family poisson takes y in {0, 1, 2, ...} (counts below 2^24: exact in float32)')
+        super(GLMData, self).__init__(D)
+        self.A, self.y, self.offset, self.family, self.logl_const = A, y, o, family, logl_const
+        self.logl0 = logl_const - (float(np.sum(scipy.special.gammaln(y + 1.0))) if family == 'poisson' else 0.0)
+        at, yy, oo = self.layout(A, y, o)
+        self.hip_like_glm = dict(at=at, y=yy, o=oo, logl0=self.logl0, n=n, family=family)
+
+    @staticmethod
+    def layout(A, y, offset=None):
+        """the float32 arrays of nnest_glm_t: A [n, D], y [n], offset [n] or None -> (at [D, ld] = A^T, y [ld], o [ld]), ld = n
+        rounded up to a multiple of 64, zero padded"""
+        A = np.asarray(A, np.float64)
+        n, D = A.shape
+        ld = (n + 63) // 64 * 64
+        at = np.zeros((D, ld), np.float32)
+        at[:, :n] = A.T
+        yy = np.zeros(ld, np.float32)
+        yy[:n] = np.asarray(y, np.float64)
+        oo = np.zeros(ld, np.float32)
+        if offset is not None:
+            oo[:n] = np.asarray(offset, np.float64)
+        return at, yy, oo
+
+    def loglike_rows(self, x):
+        with np.errstate(over='ignore', invalid='ignore'):
+            eta = self.offset + np.asarray(x, dtype=np.float64) @ self.A.T
+            if self.family == 'logistic':
+                s = (1.0 - 2.0 * self.y) * eta
+                terms = -(np.maximum(s, 0.0) + np.log1p(np.exp(-np.abs(s))))
+            else:
+                terms = self.y * eta - np.exp(eta)
+            logl = self.logl0 + np.sum(terms, axis=1)
+        return np.where(np.isfinite(logl), logl, -1e100)

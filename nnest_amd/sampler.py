@@ -248,6 +248,19 @@ class Sampler(object):
             self.logger.warning('%sthe likelihood\'s hip_like_data disagrees with the host callable; using the host protocol' % warn)
         return ok
 
+    def _probe_agrees_glm(self, data, affine, warn=''):
+        """`_probe_agrees_gdata` for a regression likelihood of user data: the kernels' evaluation of the descriptor `data`
+        (flow.loglike_glm) against the host callable, on the same 32 points under the same tolerances.  Warns where it does not"""
+        from . import flow
+        x = np.random.RandomState(4321).uniform(-1, 1, size=(32, self.x_dim)).astype(np.float32)
+        x = x * np.asarray(affine[0], np.float32) + np.asarray(affine[1], np.float32)
+        dev = flow.loglike_glm(data, x, device=self.trainer.netG.device).cpu().numpy()
+        host = np.asarray(self._user_loglike(x.astype(np.float64)), dtype=np.float64)
+        ok = bool(np.allclose(dev, host, rtol=1e-5, atol=1e-4))
+        if not ok:
+            self.logger.warning('%sthe likelihood\'s hip_like_glm disagrees with the host callable; using the host protocol' % warn)
+        return ok
+
     def _next_seed(self):
         """64-bit seed for the in-kernel Philox streams.  Drawn from a PRIVATE generator seeded once from the seed of torch's
         CPU generator (torch.manual_seed): the global generator is never advanced by the build's own bookkeeping, so the
@@ -777,7 +790,9 @@ class Sampler(object):
         they fall back to rounds.  One probe of the host callable (`_probe_agrees`) per call: a run resolves once and hands the
         target down.  A likelihood without an id but with a `hip_like_data` (likelihoods.GaussianData) is taken for the Metropolis
         entries (GDATA_ENTRIES) where the flow's `mcmc_gdata` entry is bound and takes the flow (`mcmc_gdata_refusal`) and the
-        descriptor agrees with the host callable (`_probe_agrees_gdata`): the target then has like_id None and the data"""
+        descriptor agrees with the host callable (`_probe_agrees_gdata`): the target then has like_id None and the data.  Likewise
+        a likelihood with a `hip_like_glm` (likelihoods.GLMData): the flow's `mcmc_glm` entry, `mcmc_glm_refusal`,
+        `_probe_agrees_glm`"""
         affine = self._ensemble_affine() if affine is None else affine
         netG = self.trainer.netG
         if self.num_derived != 0:
@@ -792,8 +807,16 @@ class Sampler(object):
         like_data = getattr(like, 'hip_like_data', None) if like_id is None else None
         if like_data is not None and not (entry in self.GDATA_ENTRIES and 'mcmc_gdata' in getattr(netG, '_sym', ())):
             like_data = None
-        if like_id is None and like_data is None:
+        like_glm = getattr(like, 'hip_like_glm', None) if like_id is None and like_data is None else None
+        if like_glm is not None and not (entry in self.GDATA_ENTRIES and 'mcmc_glm' in getattr(netG, '_sym', ())):
+            like_glm = None
+        if like_id is None and like_data is None and like_glm is None:
             return None, 'a likelihood the kernels do not know (a Python callable)'
+        if like_glm is not None:   # (as below for like_data: one kernel per flow and family serves the four entries)
+            why = netG.mcmc_glm_refusal(np.shape(like_glm['at'])[0])
+            if why is not None:
+                return None, 'the flow %s: %s' % (type(netG).__name__, why)
+            entry = None
         if like_data is not None:   # (one kernel per family serves the four entries: its shapes and base, in the library's words)
             why = netG.mcmc_gdata_refusal(len(like_data['mu']))
             if why is not None:
@@ -822,6 +845,10 @@ class Sampler(object):
             ok = self._transform_prior and isinstance(prior, UniformPrior) and type(prior).__call__ is UniformPrior.__call__
             box = (prior.minimum, prior.maximum) if ok else None
         params = tuple(getattr(like, 'hip_like_params', ()) or ())
+        if like_glm is not None:
+            if affine is None or box is None or not self._probe_agrees_glm(like_glm, affine, warn='mcmc: '):
+                return None, refused
+            return DeviceTarget(None, (), affine[0], affine[1], *box, like_glm=like_glm), None
         if like_data is not None:
             if affine is None or box is None or not self._probe_agrees_gdata(like_data, affine, warn='mcmc: '):
                 return None, refused

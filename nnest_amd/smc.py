@@ -226,6 +226,8 @@ class SMCSampler(Sampler):
         theta = torch.as_tensor(np.asarray(self.sample_prior(N), np.float32)).to(netG.device).contiguous()
         if target.like_data is not None:   # (a Gaussian likelihood from user data: no id, its own evaluator)
             logl = flow.loglike_gdata(target.launch_kwargs(netG.device)['like_data'], theta, device=netG.device)
+        elif target.like_glm is not None:   # (a regression likelihood of user data, likewise)
+            logl = flow.loglike_glm(target.launch_kwargs(netG.device)['like_glm'], theta, device=netG.device)
         else:
             logl = flow.loglike(target.like_id, theta, 1.0, device=netG.device, like_params=target.like_params)
         self.total_calls += N

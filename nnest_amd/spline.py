@@ -39,7 +39,8 @@ class HipSpline(_PaddedVectors, _HipFlow):
                    importance_check='nnest_spline_importance_check', mcmc_tempered='nnest_spline_mcmc_tempered_steps',
                    mcmc_mixed='nnest_spline_mcmc_mixed_steps', mcmc_mixed_check='nnest_spline_mcmc_mixed_check',
                    mcmc_adapt='nnest_spline_mcmc_adapt_steps', mcmc_adapt_check='nnest_spline_mcmc_adapt_check',
-                   mcmc_gdata='nnest_spline_mcmc_gdata_steps', mcmc_gdata_check='nnest_spline_mcmc_gdata_check')
+                   mcmc_gdata='nnest_spline_mcmc_gdata_steps', mcmc_gdata_check='nnest_spline_mcmc_gdata_check',
+                   mcmc_glm='nnest_spline_mcmc_glm_steps', mcmc_glm_check='nnest_spline_mcmc_glm_check')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (flow._PaddedVectors: zero-padded, exact)
         with torch.cuda.device(self.device):

@@ -1,0 +1,166 @@
+"""Developer diagnostic: the kernels of the regression likelihoods of user data (nnest_mcmc_glm_steps, nnest_spline_mcmc_glm_steps)
+1. against the kernels of the Gaussian likelihood from user data at the same x_dim, per x_dim, flow (NVP, spline) and family,
+   `walkers` chains x `steps` steps, on the same flow (at its initialisation: nothing is trained), T and start, with the histories
+   written, every step local (global_every = 0) and the adaptation off:
+     gdata   nnest_mcmc_gdata_steps / nnest_spline_mcmc_gdata_steps on tests/gdata_check.make_target's dense P -- units this tree does
+             not touch: the parent commit's kernels, D (D + 1) / 2 products per evaluation;
+     glm     the new entry on tests/glm_check.make_data with n rows: n D products and n float64 terms per evaluation.
+   The ratio glm / gdata is the price of n rows against D (D + 1) / 2 products.
+2. through the front end: MCMCSampler.run(route='fused') against route='host' with the same callable -- the only route this
+   likelihood had before --, the flow trained once beforehand (its training is outside the clock), `fe_chains` chains x `fe_steps`
+   steps.
+The sides alternate in one process: after a warm-up of each, `reps` rounds, each launch timed by a host clock around work that ends
+in a device synchronise.  Printed per side: the mean, the standard deviation and the standard error of the mean; per case the ratio
+of the means with its standard error (first order, from the two standard errors).  There is no pass/fail ratio: the figures are
+recorded.
+   python tools/time_mcmc_glm.py [--reps R] [--rows N] [--fe-reps R] [--out FILE] [x_dim walkers steps] ...
+   (default: --reps 20 --rows 1024 --fe-reps 20, 50 1000 250 and 20 1000 250; --fe-reps 0 skips part 2; --out appends the report to
+   FILE, e.g. profiles/mcmc_glm/summary.txt)"""
+import ctypes
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import nnest_amd  # noqa: E402
+from nnest_amd import _lib, flow, likelihoods  # noqa: E402
+from tests import gdata_check as gc  # noqa: E402
+from tests import glm_check as gk  # noqa: E402
+
+
+def timed(fn, seed):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn(seed)
+    torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t0), out
+
+
+def stats(t):
+    t = np.asarray(t)
+    sd = float(t.std(ddof=1)) if len(t) > 1 else 0.0
+    return float(t.mean()), sd, sd / np.sqrt(len(t))
+
+
+def entry(net, which, like, z0, S, step, t_std, t_mean, seed):
+    """the gdata or the glm entry itself at global_every = 0, adapt_steps = 0, no step_in; like: the struct the entry takes"""
+    dev = z0.device
+    C, D = z0.shape
+    f32, f64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.float64, device=dev)
+    out = dict(z=torch.empty(C, D, **f32), x=torch.empty(C, D, **f32), lp=torch.empty(C, **f64), logl=torch.empty(C, **f64),
+               hist_z=torch.empty(C, S, D, **f32), hist_x=torch.empty(C, S, D, **f32), hist_logl=torch.empty(C, S, **f64),
+               n_accept=torch.empty(C, dtype=torch.int32, device=dev), n_accept_global=torch.empty(C, dtype=torch.int32, device=dev),
+               step=torch.empty(C, **f64), hist_step=torch.empty(C, S, **f64))
+    with torch.cuda.device(dev):
+        _lib.check(net._sym[which](
+            net._h, ctypes.byref(like), _lib.ptr(t_std), _lib.ptr(t_mean), None, None, _lib.ptr(z0), None, None, _lib.ptr(out['z']),
+            _lib.ptr(out['x']), _lib.ptr(out['lp']), _lib.ptr(out['logl']), _lib.ptr(out['hist_z']), _lib.ptr(out['hist_x']),
+            _lib.ptr(out['hist_logl']), _lib.ptr(out['n_accept']), C, S, ctypes.c_float(step), 0, int(seed), 0, ctypes.c_double(1.0), 0,
+            _lib.ptr(out['n_accept_global']), None, _lib.ptr(out['step']), _lib.ptr(out['hist_step']), ctypes.c_uint32(0),
+            ctypes.c_double(1.0), ctypes.c_double(0.234), _lib.current_stream(dev)))
+    return out
+
+
+def alternate(sides, reps, say, fmt):
+    """warm each side up, then `reps` rounds in turn; returns the means and standard errors"""
+    ts = {n: [] for n in sides}
+    last = {}
+    for name, fn in sides.items():   # warm-up: code objects, allocator
+        timed(fn, 0)
+    for r in range(reps):
+        for name, fn in sides.items():
+            ms, last[name] = timed(fn, r + 1)
+            ts[name].append(ms)
+    m, e = {}, {}
+    for name in sides:
+        m[name], sd, e[name] = stats(ts[name])
+        say(fmt(name, m[name], len(ts[name]), sd, e[name], last[name]))
+    return m, e
+
+
+def main(argv):
+    reps, fe_reps, rows, out_path, nums = 20, 20, 1024, None, []
+    fe_chains, fe_steps = 1000, 250
+    it = iter(argv)
+    for a in it:
+        if a == '--reps':
+            reps = int(next(it))
+        elif a == '--fe-reps':
+            fe_reps = int(next(it))
+        elif a == '--rows':
+            rows = int(next(it))
+        elif a == '--out':
+            out_path = next(it)
+        else:
+            nums.append(int(a))
+    nums = nums or [50, 1000, 250, 20, 1000, 250]
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+
+    def say(s):   # (line by line: a run that is cut short keeps what it measured)
+        print(s, flush=True)
+        if out_path:
+            with open(out_path, 'a') as f:
+                f.write(s + '\n')
+
+    say('%s, torch %s' % (torch.cuda.get_device_name(0), torch.__version__))
+    tmp = tempfile.mkdtemp()
+    for D, C, S in zip(*[iter(nums)] * 3):
+        step = 2.0 / np.sqrt(D)
+        x0 = np.random.RandomState(0).normal(size=(C, D)).astype(np.float32) * 0.5
+        mu, P = gc.make_target(D, D)
+        gdata = likelihoods.GaussianData(mu, precision=P).hip_like_data
+        likes = dict((fam, gk.make_like(D, rows, fam, D)) for fam in gk.FAMILIES)
+        for flow_name in ('nvp', 'spline'):
+            s = nnest_amd.MCMCSampler(D, likelihoods.Gaussian(D, 0.5), log_dir=tmp, log_level=30, flow=flow_name)
+            net = s.trainer.netG
+            z0, _ = net.forward(x0)   # (the spline: sets the ActNorm layers from the start points)
+            z0 = z0.contiguous()
+            t_std = torch.full((D,), 0.5, dtype=torch.float32, device=z0.device)
+            t_mean = torch.zeros(D, dtype=torch.float32, device=z0.device)
+            gspec, keep = flow.gdata_spec(gdata, z0.device)
+            specs = dict((fam, flow.glm_spec(like.hip_like_glm, z0.device)) for fam, like in likes.items())
+            say('x_dim %d, n %d, %s flow, %d chains x %d steps, step %.3f' % (D, rows, flow_name, C, S, step))
+            sides = {'gdata': lambda seed: entry(net, 'mcmc_gdata', gspec, z0, S, step, t_std, t_mean, seed)}
+            for fam in gk.FAMILIES:
+                sides[fam] = lambda seed, fam=fam: entry(net, 'mcmc_glm', specs[fam][0], z0, S, step, t_std, t_mean, seed)
+            m, e = alternate(sides, reps, say, lambda name, mean, k, sd, se, out:
+                             '  kernel %-8s %9.3f ms per launch (mean of %d; sd %.3f, se %.3f), %8.2f us per step, acceptance %.3f'
+                             % (name, mean, k, sd, se, 1e3 * mean / S, float(out['n_accept'].sum()) / (C * S)))
+            for fam in gk.FAMILIES:
+                ratio = m[fam] / m['gdata']
+                say('  %s / gdata: %.3fx +- %.3f (%d x %d products and %d float64 terms against %d products per evaluation)'
+                    % (fam, ratio, ratio * np.hypot(e[fam] / m[fam], e['gdata'] / m['gdata']), rows, D, rows, D * (D + 1) // 2))
+    if fe_reps > 0:
+        for D in sorted(set(nums[0::3])):
+            for fam in gk.FAMILIES:
+                like = gk.make_like(D, rows, fam, D)
+                th, _ = gk.posterior_mode(like, -5.0, 5.0, iters=30)
+                rng = np.random.RandomState(1)
+                train = th + 0.1 * rng.normal(size=(2000, D))
+                for flow_name in ('nvp', 'spline'):
+                    np.random.seed(0)
+                    torch.manual_seed(0)
+                    s = nnest_amd.MCMCSampler(D, like, log_dir=tmp, log_level=30, flow=flow_name)
+                    init = ((train[:fe_chains] - train.mean(0)) / train.std(0))
+                    try:
+                        s.run(2, fe_chains, train, init_samples=init, route='fused', seed=0)   # (trains the flow; kept for every run below)
+                    except ValueError as err:   # (the probe's tolerances are absolute beyond |logL| of 1e1: a refusal is reported)
+                        say('front end: x_dim %d, n %d, %s, %s flow: %s' % (D, rows, fam, flow_name, err))
+                        continue
+                    s.trainer.train = lambda samples, **kw: None
+                    say('front end: x_dim %d, n %d, %s, %s flow, %d chains x %d steps' % (D, rows, fam, flow_name, fe_chains, fe_steps))
+                    sides = dict((route, lambda seed, route=route: s.run(fe_steps, fe_chains, train, init_samples=init, route=route, seed=seed))
+                                 for route in ('host', 'fused'))
+                    m, e = alternate(sides, fe_reps, say, lambda name, mean, k, sd, se, out:
+                                     '  route %-6s %10.2f ms per run (mean of %d; sd %.2f, se %.2f)' % (name, mean, k, sd, se))
+                    ratio = m['host'] / m['fused']
+                    say('  host / fused: %.2fx +- %.2f' % (ratio, ratio * np.hypot(e['host'] / m['host'], e['fused'] / m['fused'])))
+
+
+if __name__ == '__main__':
+    main(sys.argv[1:])
