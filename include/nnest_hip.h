@@ -717,6 +717,54 @@ int nnest_spline_mcmc_glm_steps(struct nnest_spline *spl, const nnest_glm_t *glm
                                 float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta, int global_every,
                                 int *n_accept_global_dev, const double *step_in_dev, double *step_out_dev, double *hist_step_dev,
                                 uint32_t adapt_steps, double adapt_rate, double target_accept, void *stream);
+/* INDEPENDENT NORMAL PRIORS beside the regression likelihoods above, in kernels of their own (nnest_mcmc_glm_prior.hip,
+ * nnest_spline_mcmc_glm_prior.hip, gauss_prior.h).  BUILD-DEFINED.  (All added within ABI 15.)
+ *   log pi(theta) = logc - 1/2 sum_c ((theta_c - m_c) / sigma_c)^2,   logc = -sum_c log sigma_c - (D / 2) log 2 pi.
+ * nnest_gauss_prior_t: m_dev [D] float32 the means, r_dev [D] float32 = float32(1 / sigma_c), logc as above (any finite constant is
+ *   taken: the walk does not depend on it), 1 <= D <= 128.  r = 0 is an infinitely wide prior in that coordinate.
+ * The arithmetic, with t = T(x) the float32 row the likelihood sees (or a row of t_dev):
+ *     u_c    = (t_c - m_c) * r_c                 float32, each operation rounded (no fused multiply-add)
+ *     ss     = sum_c (double)u_c * (double)u_c   float64, in the kernel's own fixed order (the order of the walk's sum of z^2)
+ *     log pi = logc - 0.5 * ss                   float64; -inf where ss is not finite: a non-finite coordinate is refused, never NaN
+ *     lp_beta = ((beta * logL) + log|det|) + log pi   each operation rounded: the tempered target with log pi in place of its 0.0
+ *   A row outside the box lo_dev / hi_dev has lp = -inf, as in every sibling.  The same row gives the same bits of log pi at any
+ *   position of any launch of one entry.  (The two walks order the sum differently: their values agree to rounding.)
+ * nnest_logprior_gauss: log pi alone on N rows t_dev [N, D] float32 that are already T(x); logp_dev [N] float64.  D must be the
+ *   descriptor's.  N = 0 launches nothing.
+ * nnest_mcmc_glm_prior_steps, nnest_spline_mcmc_glm_prior_steps: the arguments of nnest_mcmc_glm_steps / nnest_spline_mcmc_glm_steps
+ *   with `const nnest_gauss_prior_t *prior` after `glm`.  The run is theirs in every respect -- draws, mixed schedule, the global
+ *   step's weight (on this lp), accept rule, step rule, beta, lp_in_dev / logl_in_dev, histories, counters, steps = 0, the cut into
+ *   launches, a shard by walker_offset --; only the target's prior term differs.  With r = 0 and logc = 0.0 every lp of a row whose
+ *   coordinates are finite is nnest_mcmc_glm_steps's to the bit.
+ * NNEST_E_ARG before any launch, the outputs untouched: prior NULL, a NULL m_dev or r_dev, D outside 1 .. 128 or not the flow's
+ *   x_dim, logc not finite, and every argument error of the glm entries.  NNEST_E_UNSUPPORTED before any launch: what the _check
+ *   entry refuses.
+ * nnest_mcmc_glm_prior_check, nnest_spline_mcmc_glm_prior_check: the verdict of nnest_mcmc_glm_check / nnest_spline_mcmc_glm_check
+ *   (the same shapes and base) for these entries; nothing is launched. */
+typedef struct nnest_gauss_prior {
+    const float *m_dev;
+    const float *r_dev;
+    double logc;
+    int D;
+} nnest_gauss_prior_t;
+int nnest_logprior_gauss(const nnest_gauss_prior_t *prior, const float *t_dev, double *logp_dev, int N, int D, void *stream);
+int nnest_mcmc_glm_prior_check(nnest_nvp_t *nvp, int D);
+int nnest_spline_mcmc_glm_prior_check(struct nnest_spline *spl, int D);
+int nnest_mcmc_glm_prior_steps(nnest_nvp_t *nvp, const nnest_glm_t *glm, const nnest_gauss_prior_t *prior, const float *t_std_dev,
+                               const float *t_mean_dev, const float *lo_dev, const float *hi_dev, const float *z_in_dev,
+                               const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev, float *x_out_dev, double *lp_out_dev,
+                               double *logl_out_dev, float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C,
+                               int steps, float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta,
+                               int global_every, int *n_accept_global_dev, const double *step_in_dev, double *step_out_dev,
+                               double *hist_step_dev, uint32_t adapt_steps, double adapt_rate, double target_accept, void *stream);
+int nnest_spline_mcmc_glm_prior_steps(struct nnest_spline *spl, const nnest_glm_t *glm, const nnest_gauss_prior_t *prior,
+                                      const float *t_std_dev, const float *t_mean_dev, const float *lo_dev, const float *hi_dev,
+                                      const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev,
+                                      float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev, float *hist_x_dev,
+                                      double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size, uint64_t step0,
+                                      uint64_t seed, uint64_t walker_offset, double beta, int global_every, int *n_accept_global_dev,
+                                      const double *step_in_dev, double *step_out_dev, double *hist_step_dev, uint32_t adapt_steps,
+                                      double adapt_rate, double target_accept, void *stream);
 /* IMPORTANCE-SAMPLED EVIDENCE with the trained flow as the proposal: Z = E_q[L(T(x)) pi(T(x)) / q(x)], drawn, evaluated and reduced
  * inside one kernel.  BUILD-DEFINED: the reference has no such estimator.  Sample m is a global 64-bit index; row k of a launch of M
  * samples is m = sample_offset + k:

@@ -115,6 +115,11 @@ class GlmSpec(ctypes.Structure):
                 ('n', ctypes.c_int), ('ld', ctypes.c_int), ('D', ctypes.c_int), ('family', ctypes.c_int)]
 
 
+class GaussPriorSpec(ctypes.Structure):
+    """nnest_gauss_prior_t (include/nnest_hip.h): independent normal priors -- device pointers of m [D] and r = 1 / sigma [D], logc, D"""
+    _fields_ = [('m_dev', ctypes.c_void_p), ('r_dev', ctypes.c_void_p), ('logc', ctypes.c_double), ('D', ctypes.c_int)]
+
+
 GLM_FAMILIES = {'logistic': 0, 'poisson': 1}   # NNEST_GLM_LOGISTIC, NNEST_GLM_POISSON
 
 
@@ -275,6 +280,15 @@ SIGNATURES = {
     'nnest_loglike_glm': [_vp, _vp, _vp, _i, _i, _vp],
     'nnest_mcmc_glm_check': [_vp, _i],
     'nnest_spline_mcmc_glm_check': [_vp, _i],
+    # normal priors beside them: the glm entries' arguments with `const nnest_gauss_prior_t *prior` after `glm`;
+    # (prior, t_dev, logp_dev, N, D, stream); (handle, D)
+    'nnest_mcmc_glm_prior_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64,
+                                   _u64, _u64, _d, _i, _vp, _vp, _vp, _vp, _u32, _d, _d, _vp],
+    'nnest_spline_mcmc_glm_prior_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f,
+                                          _u64, _u64, _u64, _d, _i, _vp, _vp, _vp, _vp, _u32, _d, _d, _vp],
+    'nnest_logprior_gauss': [_vp, _vp, _vp, _i, _i, _vp],
+    'nnest_mcmc_glm_prior_check': [_vp, _i],
+    'nnest_spline_mcmc_glm_prior_check': [_vp, _i],
     # (logl_dev, N, beta, ess_fraction, out_dev [4], m_dev [N] int64, stream)
     'nnest_smc_reweight': [_vp, _i, _d, _d, _vp, _vp, _vp],
     # (m_dev, N, D, seed, stage, theta_in_dev, logl_in_dev, anc_out_dev, theta_out_dev, logl_out_dev, stream)

@@ -14,6 +14,7 @@
 #include "mcmc_adapt.h"
 #include "mcmc_gdata.h"
 #include "glm_data.h"
+#include "gauss_prior.h"
 
 using namespace nnest;
 
@@ -473,6 +474,16 @@ int nnest::glm_ok(const nnest_glm_t *g, int D, GlmSpec *out) {
     out->n = g->n; out->ld = g->ld; out->D = g->D; out->family = g->family;
     return NNEST_OK;
 }
+// D: what the descriptor's dimension must be (the flow's x_dim, or the D argument of nnest_logprior_gauss)
+int nnest::gauss_prior_ok(const nnest_gauss_prior_t *g, int D, GaussPriorSpec *out, const char *what) {
+    if (!g) return fail(NNEST_E_ARG, "prior is NULL");
+    if (!g->m_dev || !g->r_dev) return fail(NNEST_E_ARG, "prior: NULL m_dev or r_dev");
+    if (g->D < 1 || g->D > 128) return fail(NNEST_E_ARG, "prior: D=%d (1 .. 128)", g->D);
+    if (g->D != D) return fail(NNEST_E_ARG, "the prior's D=%d is not %s=%d", g->D, what, D);
+    if (!isfinite(g->logc)) return fail(NNEST_E_ARG, "prior: logc=%g (finite)", g->logc);
+    out->m = g->m_dev; out->r = g->r_dev; out->logc = g->logc; out->D = g->D;
+    return NNEST_OK;
+}
 int nnest::importance_args(ImpArgs *a, const float *t_std, const float *t_mean, const float *lo, const float *hi, float *z_out, float *x_out,
                            double *logl_out, double *logw_out, double *partials, double *sums, int M, uint64_t seed, uint64_t sample_offset) {
     if (M < 0 || M > (1 << 30)) return fail(NNEST_E_ARG, "importance: M=%d (0 .. 2^30 samples a launch)", M);
@@ -805,6 +816,58 @@ int nnest_mcmc_glm_steps(nnest_nvp_t *h, const nnest_glm_t *glm, const float *t_
     hipError_t e = launch_mcmc_glm(h->s, h->w, a, (hipStream_t)stream);
     if (e == hipErrorInvalidConfiguration) return fail(NNEST_E_UNSUPPORTED, "mcmc glm: x_dim=%d not instantiated", h->s.D);
     if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_mcmc_glm: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+// the normal priors beside the regression likelihoods (nnest_mcmc_glm_prior.hip, gauss_prior.h): the prior alone
+int nnest_logprior_gauss(const nnest_gauss_prior_t *prior, const float *t_dev, double *logp_dev, int N, int D, void *stream) {
+    GaussPriorSpec p;
+    int rc;
+    if ((rc = gauss_prior_ok(prior, D, &p, "D"))) return rc;
+    if (N < 0) return fail(NNEST_E_ARG, "logprior gauss: N=%d (>= 0)", N);
+    if (N > 0 && (!t_dev || !logp_dev)) return fail(NNEST_E_ARG, "NULL device buffer");
+    hipError_t e = launch_logprior_gauss(p, t_dev, logp_dev, N, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_logprior_gauss: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+// what nnest_mcmc_glm_prior_steps takes, asked before a launch (and by the entry itself): nnest_mcmc_glm_check's verdict -- the
+// kernel is that kernel's with a prior term, so the same shapes and base
+int nnest_mcmc_glm_prior_check(nnest_nvp_t *h, int D) { return nnest_mcmc_glm_check(h, D); }
+
+// (as nnest_mcmc_glm_steps: the checks that need no handle come first)
+int nnest_mcmc_glm_prior_steps(nnest_nvp_t *h, const nnest_glm_t *glm, const nnest_gauss_prior_t *prior, const float *t_std_dev,
+                               const float *t_mean_dev, const float *lo_dev, const float *hi_dev, const float *z_in_dev,
+                               const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev, float *x_out_dev, double *lp_out_dev,
+                               double *logl_out_dev, float *hist_z_dev, float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int C,
+                               int steps, float step_size, uint64_t step0, uint64_t seed, uint64_t walker_offset, double beta,
+                               int global_every, int *n_accept_global_dev, const double *step_in_dev, double *step_out_dev,
+                               double *hist_step_dev, uint32_t adapt_steps, double adapt_rate, double target_accept, void *stream) {
+    McmcGlmPriorArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc;
+    if ((rc = glm_ok(glm, glm ? glm->D : 0, &a.gl))) return rc;
+    if ((rc = gauss_prior_ok(prior, h ? h->s.D : prior ? prior->D : 0, &a.pr))) return rc;   // (no handle: refused below)
+    if ((rc = mcmc_beta_ok(beta))) return rc;
+    if ((rc = mcmc_mixed_every_ok(global_every))) return rc;
+    if ((rc = mcmc_adapt_rule_ok(adapt_rate, target_accept))) return rc;
+    a.beta = beta;
+    a.global_every = global_every;
+    a.n_accept_global = n_accept_global_dev;
+    a.step_in = step_in_dev;
+    a.step_out = step_out_dev;
+    a.hist_step = hist_step_dev;
+    a.adapt_steps = adapt_steps;
+    a.adapt_rate = adapt_rate;
+    a.target_accept = target_accept;
+    rc = mcmc_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev, lp_out_dev,
+                   logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0, seed, walker_offset);
+    if (rc) return rc;
+    if ((rc = nnest_mcmc_glm_prior_check(h, a.gl.D))) return rc;
+    a.like.scale = 1.0f;
+    hipError_t e = launch_mcmc_glm_prior(h->s, h->w, a, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(NNEST_E_UNSUPPORTED, "mcmc glm prior: x_dim=%d not instantiated", h->s.D);
+    if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_mcmc_glm_prior: %s", hipGetErrorString(e));
     return NNEST_OK;
 }
 

@@ -21,6 +21,7 @@
 #include "mcmc_adapt.h"
 #include "mcmc_gdata.h"
 #include "glm_data.h"
+#include "gauss_prior.h"
 #include "nnest_internal.h"
 #include "mh_common.h"
 
@@ -669,6 +670,56 @@ int nnest_spline_mcmc_glm_steps(nnest_spline_t *h, const nnest_glm_t *glm, const
     a.like.scale = 1.0f;
     const hipError_t e = launch_spline_mcmc_glm(SplArgs{h->img, h->s}, a, (hipStream_t)stream);
     if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_mcmc_glm: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+// what nnest_spline_mcmc_glm_prior_steps takes, asked before a launch (and by the entry itself): nnest_spline_mcmc_glm_check's
+// verdict -- the kernel is that kernel's with a prior term, and the team tile's shapes are the same
+int nnest_spline_mcmc_glm_prior_check(nnest_spline_t *h, int D) {
+    int rc;
+    if ((rc = nnest_spline_mcmc_glm_check(h, D))) return rc;
+    McmcGlmPriorArgs probe;
+    memset(&probe, 0, sizeof(probe));   // (C = 0: the shape's verdict, nothing is launched)
+    if (launch_spline_mcmc_glm_prior(SplArgs{h->img, h->s}, probe, nullptr) == hipErrorInvalidConfiguration)
+        return spline_fail(NNEST_E_UNSUPPORTED, "spline mcmc glm prior: x_dim=%d hidden_dim=%d not instantiated (the team tile's shapes)",
+                           h->s.D, h->s.H);
+    return NNEST_OK;
+}
+
+// the same walk under the normal priors of gauss_prior.h (nnest_spline_mcmc_glm_prior.hip); the argument checks of
+// nnest_mcmc_glm_prior_steps
+int nnest_spline_mcmc_glm_prior_steps(nnest_spline_t *h, const nnest_glm_t *glm, const nnest_gauss_prior_t *prior,
+                                      const float *t_std_dev, const float *t_mean_dev, const float *lo_dev, const float *hi_dev,
+                                      const float *z_in_dev, const double *lp_in_dev, const double *logl_in_dev, float *z_out_dev,
+                                      float *x_out_dev, double *lp_out_dev, double *logl_out_dev, float *hist_z_dev, float *hist_x_dev,
+                                      double *hist_logl_dev, int *n_accept_dev, int C, int steps, float step_size, uint64_t step0,
+                                      uint64_t seed, uint64_t walker_offset, double beta, int global_every, int *n_accept_global_dev,
+                                      const double *step_in_dev, double *step_out_dev, double *hist_step_dev, uint32_t adapt_steps,
+                                      double adapt_rate, double target_accept, void *stream) {
+    McmcGlmPriorArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc;
+    if ((rc = glm_ok(glm, glm ? glm->D : 0, &a.gl))) return rc;
+    if ((rc = gauss_prior_ok(prior, h ? h->s.D : prior ? prior->D : 0, &a.pr))) return rc;   // (no handle: refused below)
+    if ((rc = mcmc_beta_ok(beta))) return rc;
+    if ((rc = mcmc_mixed_every_ok(global_every))) return rc;
+    if ((rc = mcmc_adapt_rule_ok(adapt_rate, target_accept))) return rc;
+    a.beta = beta;
+    a.global_every = global_every;
+    a.n_accept_global = n_accept_global_dev;
+    a.step_in = step_in_dev;
+    a.step_out = step_out_dev;
+    a.hist_step = hist_step_dev;
+    a.adapt_steps = adapt_steps;
+    a.adapt_rate = adapt_rate;
+    a.target_accept = target_accept;
+    rc = mcmc_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_in_dev, lp_in_dev, logl_in_dev, z_out_dev, x_out_dev, lp_out_dev,
+                   logl_out_dev, hist_z_dev, hist_x_dev, hist_logl_dev, n_accept_dev, C, steps, step_size, step0, seed, walker_offset);
+    if (rc) return rc;
+    if ((rc = nnest_spline_mcmc_glm_prior_check(h, a.gl.D))) return rc;
+    a.like.scale = 1.0f;
+    const hipError_t e = launch_spline_mcmc_glm_prior(SplArgs{h->img, h->s}, a, (hipStream_t)stream);
+    if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_mcmc_glm_prior: %s", hipGetErrorString(e));
     return NNEST_OK;
 }
 

@@ -408,7 +408,7 @@ class _HipFlow(object):
 
     def mcmc_steps(self, like_id, z, steps, step_size, t_std=None, t_mean=None, lo=None, hi=None, lp=None, logl=None, seed=0, step0=0,
                    walker_offset=0, like_params=None, history=True, beta=None, global_every=0, step_in=None, adapt_steps=0, adapt_rate=1.0,
-                   target_accept=0.234, like_data=None, like_glm=None):
+                   target_accept=0.234, like_data=None, like_glm=None, prior_gauss=None):
         """`steps` steps of random-walk Metropolis in latent space with the likelihood, the prior and the Jacobian in the ratio, in ONE
         launch (the family's `mcmc` entry point: nnest_mcmc_steps, nnest_spline_mcmc_steps; build-defined stream, the reference's move:
         include/nnest_hip.h has the definition).  z [C, D] float32 on the device: the walkers' start; lp, logl [C] float64: the
@@ -444,6 +444,10 @@ class _HipFlow(object):
         (likelihoods.GLMData.hip_like_glm: at [D, ld], y [ld], o [ld] float32, logl0, n, family) -- `like_id` and `like_data` must
         then be None, and the run goes through the family's `mcmc_glm` entry (nnest_mcmc_glm_steps, nnest_spline_mcmc_glm_steps)
         in the same way, with the same keys.
+        prior_gauss: None -- the entries above, as they were, bit for bit; the descriptor of independent normal priors on T(x)
+        (priors.GaussianPrior.hip_gauss_prior: m [D], r = 1 / sigma [D] float32, logc) -- only with a `like_glm` (ValueError naming
+        prior_gauss otherwise), and the run goes through the family's `mcmc_glm_prior` entry (nnest_mcmc_glm_prior_steps,
+        nnest_spline_mcmc_glm_prior_steps): lp = ((beta logL) + log|det|) + log pi, -inf outside lo / hi, with the same keys.
         NotImplementedError for a family without such a kernel (its handle must not reach another family's)."""
         global_every = int(global_every)
         if global_every < 0:
@@ -456,15 +460,18 @@ class _HipFlow(object):
         glm = like_glm is not None
         if glm and (like_id is not None or like_data is not None):
             raise ValueError('mcmc_steps: like_glm goes with like_id=None and like_data=None')
+        gprior = prior_gauss is not None
+        if gprior and not glm:
+            raise ValueError('mcmc_steps: prior_gauss goes only with a like_glm (a GaussianPrior beside a regression likelihood of user data)')
         gdata = like_data is not None or glm   # (either descriptor: the adaptive entry's arguments, whatever the options)
         if gdata and like_id is not None:
             raise ValueError('mcmc_steps: like_data goes with like_id=None, got like_id=%r' % (like_id,))
-        fn = self._sym.get('mcmc_glm' if glm else 'mcmc_gdata' if gdata else 'mcmc_adapt' if adapt else 'mcmc_mixed' if mixed else 'mcmc' if beta is None
+        fn = self._sym.get('mcmc_glm_prior' if gprior else 'mcmc_glm' if glm else 'mcmc_gdata' if gdata else 'mcmc_adapt' if adapt else 'mcmc_mixed' if mixed else 'mcmc' if beta is None
                            else 'mcmc_tempered')
         if fn is None:
             raise NotImplementedError('no fused %srandom-walk Metropolis kernel for %s%s' % (
                 'adaptive ' if adapt else 'mixed ' if mixed else '' if beta is None else 'tempered ', type(self).__name__,
-                ' on a regression likelihood of user data' if glm else ' on a Gaussian likelihood from user data' if gdata else ''))
+                ' on a regression likelihood of user data under a normal prior' if gprior else ' on a regression likelihood of user data' if glm else ' on a Gaussian likelihood from user data' if gdata else ''))
         tempered = () if beta is None and not mixed and not adapt and not gdata else (ctypes.c_double(1.0 if beta is None else float(beta)),)
         dev = self.device
         z = _as_dev_f32(z, dev).contiguous()
@@ -509,12 +516,15 @@ class _HipFlow(object):
         with torch.cuda.device(dev):
             if glm:
                 lk, keep = glm_spec(like_glm, dev)   # (`keep`, as below)
+                if gprior:
+                    pspec, pkeep = gauss_prior_spec(prior_gauss, dev)
             elif gdata:
                 lk, keep = gdata_spec(like_data, dev)   # (`keep`: the staged arrays, alive until the call has been enqueued)
             else:
                 lk = _lib.like_spec(like_id, 1.0, like_params)
             _lib.check(fn(
-                self._h, ctypes.byref(lk), _lib.ptr(t_std), _lib.ptr(t_mean), _lib.ptr(lo_t), _lib.ptr(hi_t), _lib.ptr(z), _lib.ptr(lp),
+                self._h, ctypes.byref(lk), *((ctypes.byref(pspec),) if gprior else ()), _lib.ptr(t_std), _lib.ptr(t_mean), _lib.ptr(lo_t),
+                _lib.ptr(hi_t), _lib.ptr(z), _lib.ptr(lp),
                 _lib.ptr(logl), _lib.ptr(out['z']) if steps > 0 else None, _lib.ptr(out['x']), _lib.ptr(out['lp']), _lib.ptr(out['logl']),
                 _lib.ptr(out['hist_z']), _lib.ptr(out['hist_x']), _lib.ptr(out['hist_logl']), _lib.ptr(out['n_accept']), C, steps,
                 ctypes.c_float(float(step_size)), int(step0) & 0xFFFFFFFFFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF,
@@ -556,6 +566,21 @@ class _HipFlow(object):
         fn = self._sym.get('mcmc_glm_check')
         if fn is None or 'mcmc_glm' not in self._sym:
             raise NotImplementedError('no fused random-walk Metropolis kernel for %s on a regression likelihood of user data' % type(self).__name__)
+        with torch.cuda.device(self.device):
+            rc = fn(self._h, self.D if D is None else int(D))
+        if rc == _lib.NNEST_OK:
+            return None
+        msg = self._lib.nnest_hip_last_error()
+        return msg.decode() if msg else 'error %d' % rc
+
+    def mcmc_glm_prior_refusal(self, D=None):
+        """why `mcmc_steps` with a like_glm of dimension D (None: the flow's own) and a prior_gauss would refuse this flow (its shape,
+        its base) -- the library's own words (the family's `mcmc_glm_prior_check` entry; nothing is launched) --, or None where it is
+        taken.  NotImplementedError for a family without such a kernel"""
+        fn = self._sym.get('mcmc_glm_prior_check')
+        if fn is None or 'mcmc_glm_prior' not in self._sym:
+            raise NotImplementedError('no fused random-walk Metropolis kernel for %s on a regression likelihood of user data under a normal '
+                                      'prior' % type(self).__name__)
         with torch.cuda.device(self.device):
             rc = fn(self._h, self.D if D is None else int(D))
         if rc == _lib.NNEST_OK:
@@ -870,7 +895,8 @@ class HipNVP(_PaddedVectors, _HipFlow):
                    mcmc_mixed_check='nnest_mcmc_mixed_check', mcmc_adapt='nnest_mcmc_adapt_steps',
                    mcmc_adapt_check='nnest_mcmc_adapt_check', mcmc_gdata='nnest_mcmc_gdata_steps',
                    mcmc_gdata_check='nnest_mcmc_gdata_check', mcmc_glm='nnest_mcmc_glm_steps',
-                   mcmc_glm_check='nnest_mcmc_glm_check')
+                   mcmc_glm_check='nnest_mcmc_glm_check', mcmc_glm_prior='nnest_mcmc_glm_prior_steps',
+                   mcmc_glm_prior_check='nnest_mcmc_glm_prior_check')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (_PaddedVectors)
         with torch.cuda.device(self.device):
@@ -1173,6 +1199,34 @@ def loglike_glm(data, t, device=None):
     with torch.cuda.device(dev):
         spec, keep = glm_spec(data, dev)
         _lib.check(_lib.load().nnest_loglike_glm(ctypes.byref(spec), _lib.ptr(t), _lib.ptr(out), N, D, _lib.current_stream(dev)))
+    return out
+
+
+def gauss_prior_spec(data, device):
+    """the nnest_gauss_prior_t of independent normal priors on `device`: data = the mapping priors.GaussianPrior.hip_gauss_prior holds
+    (m [D] and r = 1 / sigma [D] float32, arrays or tensors; logc).  Arrays already on the device are used as they are.  Returns
+    (spec, keep): `keep` holds the staged tensors the spec points into.  ValueError for misshapen arrays; the ranges are the
+    library's to refuse"""
+    m = _as_dev_f32(data['m'], device).reshape(-1).contiguous()   # (a [D] array comes back as [1, D])
+    r = _as_dev_f32(data['r'], device).reshape(-1).contiguous()
+    if m.shape[0] < 1 or r.shape != m.shape:
+        raise ValueError('prior_gauss: m and r must both be shaped [D], got %s and %s' % (tuple(m.shape), tuple(r.shape)))
+    return _lib.GaussPriorSpec(m.data_ptr(), r.data_ptr(), float(data['logc']), m.shape[0]), (m, r)
+
+
+def logprior_gauss(data, t, device=None):
+    """independent normal priors alone (nnest_logprior_gauss; include/nnest_hip.h has the arithmetic): data as `gauss_prior_spec`
+    takes it, t [N, D] rows that are already T(x) (float32 on the device, or anything convertible).  Returns log pi [N] float64 on
+    the device (-inf on a row with a non-finite coordinate).  Asynchronous on the current stream."""
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    t = _as_dev_f32(t, dev).contiguous()
+    if t.dim() != 2:
+        raise ValueError('logprior_gauss: t must be shaped [N, D], got %s' % (tuple(t.shape),))
+    N, D = t.shape
+    out = torch.empty(N, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        spec, keep = gauss_prior_spec(data, dev)
+        _lib.check(_lib.load().nnest_logprior_gauss(ctypes.byref(spec), _lib.ptr(t), _lib.ptr(out), N, D, _lib.current_stream(dev)))
     return out
 
 

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from .device_target import DeviceTarget
-from .priors import UniformPrior
+from .priors import GaussianPrior, UniformPrior
 from .utils import create_logger, get_or_create_run_dir, write_rows_e5
 
 
@@ -259,6 +259,19 @@ class Sampler(object):
         ok = bool(np.allclose(dev, host, rtol=1e-5, atol=1e-4))
         if not ok:
             self.logger.warning('%sthe likelihood\'s hip_like_glm disagrees with the host callable; using the host protocol' % warn)
+        return ok
+
+    def _probe_agrees_gauss_prior(self, data, affine, warn=''):
+        """`_probe_agrees_glm` for the prior: the kernels' evaluation of the descriptor `data` (flow.logprior_gauss) against the prior's
+        host callable, on the same 32 points under the same tolerances.  Warns where it does not"""
+        from . import flow
+        x = np.random.RandomState(4321).uniform(-1, 1, size=(32, self.x_dim)).astype(np.float32)
+        x = x * np.asarray(affine[0], np.float32) + np.asarray(affine[1], np.float32)
+        dev = flow.logprior_gauss(data, x, device=self.trainer.netG.device).cpu().numpy()
+        host = np.array([self._user_prior(r) for r in x.astype(np.float64)], dtype=np.float64)
+        ok = bool(np.allclose(dev, host, rtol=1e-5, atol=1e-4))
+        if not ok:
+            self.logger.warning('%sthe prior\'s hip_gauss_prior disagrees with the host callable; using the host protocol' % warn)
         return ok
 
     def _next_seed(self):
@@ -792,7 +805,10 @@ class Sampler(object):
         entries (GDATA_ENTRIES) where the flow's `mcmc_gdata` entry is bound and takes the flow (`mcmc_gdata_refusal`) and the
         descriptor agrees with the host callable (`_probe_agrees_gdata`): the target then has like_id None and the data.  Likewise
         a likelihood with a `hip_like_glm` (likelihoods.GLMData): the flow's `mcmc_glm` entry, `mcmc_glm_refusal`,
-        `_probe_agrees_glm`"""
+        `_probe_agrees_glm`.  Beside such a likelihood, and only there, a priors.GaussianPrior on T(x) whose `__call__` is its own
+        is taken where the flow binds `mcmc_glm_prior` and takes the shape (`mcmc_glm_prior_refusal`) and the prior's
+        `hip_gauss_prior` agrees with its callable (`_probe_agrees_gauss_prior`): the target then carries `prior_gauss` and no box.
+        With any other likelihood, entry or flow a GaussianPrior stays a Python prior: refused here, the host route's"""
         affine = self._ensemble_affine() if affine is None else affine
         netG = self.trainer.netG
         if self.num_derived != 0:
@@ -812,8 +828,13 @@ class Sampler(object):
             like_glm = None
         if like_id is None and like_data is None and like_glm is None:
             return None, 'a likelihood the kernels do not know (a Python callable)'
+        prior = self._user_prior
+        prior_gauss = None   # (normal priors: beside a regression likelihood of user data only)
+        if (like_glm is not None and self._transform_prior and isinstance(prior, GaussianPrior)
+                and type(prior).__call__ is GaussianPrior.__call__ and 'mcmc_glm_prior' in getattr(netG, '_sym', ())):
+            prior_gauss = prior.hip_gauss_prior
         if like_glm is not None:   # (as below for like_data: one kernel per flow and family serves the four entries)
-            why = netG.mcmc_glm_refusal(np.shape(like_glm['at'])[0])
+            why = (netG.mcmc_glm_refusal if prior_gauss is None else netG.mcmc_glm_prior_refusal)(np.shape(like_glm['at'])[0])
             if why is not None:
                 return None, 'the flow %s: %s' % (type(netG).__name__, why)
             entry = None
@@ -836,11 +857,13 @@ class Sampler(object):
                 return None, 'the flow %s: %s' % (type(netG).__name__, why)
         refused ='this transform, likelihood or prior (an affine transform, a likelihood that agrees with the kernel\'s, and no prior%s)' % (
             ', a UniformPrior on T(x) or the unit box on x' if unit_box_on_x else ' or a UniformPrior on T(x)')
-        prior = self._user_prior
+        refused = refused[:-1] + ', or a GaussianPrior with a GLMData)'
         box = (None, None)
         if unit_box_on_x and self._unit_box_on_x() and self._linear_scale is not None:
             s = np.full(self.x_dim, abs(float(self._linear_scale)), np.float32)
             box = (-s, s)
+        elif prior_gauss is not None:   # (no box beside it)
+            pass
         elif prior is not None:   # (a UniformPrior on T(x) whose rule is its own, or refused)
             ok = self._transform_prior and isinstance(prior, UniformPrior) and type(prior).__call__ is UniformPrior.__call__
             box = (prior.minimum, prior.maximum) if ok else None
@@ -848,7 +871,9 @@ class Sampler(object):
         if like_glm is not None:
             if affine is None or box is None or not self._probe_agrees_glm(like_glm, affine, warn='mcmc: '):
                 return None, refused
-            return DeviceTarget(None, (), affine[0], affine[1], *box, like_glm=like_glm), None
+            if prior_gauss is not None and (box != (None, None) or not self._probe_agrees_gauss_prior(prior_gauss, affine, warn='mcmc: ')):
+                return None, refused
+            return DeviceTarget(None, (), affine[0], affine[1], *box, like_glm=like_glm, prior_gauss=prior_gauss), None
         if like_data is not None:
             if affine is None or box is None or not self._probe_agrees_gdata(like_data, affine, warn='mcmc: '):
                 return None, refused

@@ -15,7 +15,9 @@ derived parameters are not carried by either route.
 CONVENTION of `logz`: log of the integral of L(theta) pi(theta) d theta with the NORMALISED prior the particles were drawn from
 (Z at beta = 0 is 1), as NestedSampler's `logz`.  For a UniformPrior on [lo, hi] this differs from `Sampler.importance_evidence`'s
 convention -- the prior as its callable returns it, the unnormalised indicator -- by sum log(hi - lo):
-logz_smc = logz_importance - sum log(hi - lo)."""
+logz_smc = logz_importance - sum log(hi - lo).  A priors.GaussianPrior's callable is the normalised density itself, and its
+particles are drawn with `prior.sample`: `logz` under it carries no such term on either route (with a likelihoods.GLMData the fused
+route takes it: DESIGN.md 3.17)."""
 import functools
 import logging
 import math
