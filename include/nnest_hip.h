@@ -765,6 +765,41 @@ int nnest_spline_mcmc_glm_prior_steps(struct nnest_spline *spl, const nnest_glm_
                                       uint64_t seed, uint64_t walker_offset, double beta, int global_every, int *n_accept_global_dev,
                                       const double *step_in_dev, double *step_out_dev, double *hist_step_dev, uint32_t adapt_steps,
                                       double adapt_rate, double target_accept, void *stream);
+/* POINTWISE PREDICTIVE STATISTICS of the regression likelihoods above over a set of posterior draws: per data row, what lppd, WAIC
+ * and importance-sampled leave-one-out are made of, and per new design row the posterior predictive mean (nnest_glm_pointwise.hip,
+ * glm_pointwise.h).  BUILD-DEFINED: the reference has no such estimator.  (All added within ABI 15.)
+ * The [S draws x n rows] matrix of terms is never stored: the product runs on the matrix cores, the float64 term behind it, and a
+ * running reduction over the draws per data row.  t_dev [S, D] float32: rows that are already theta = T(x).  For nnest_glm_t:
+ *     eta_is = o_i + sum_c A[i, c] * t_sc     float32, exactly nnest_loglike_glm's definition: fused multiply-adds, in the kernel's
+ *                                             own order
+ *     l_is   = the family's term              float64 from (double)eta_is, as written above (NaN where eta_is is not finite).
+ *                                             logl0 plays no part: a constant belongs to no row
+ *   A pair (i, s) is LIVE when l_is is finite; NaN and +-inf are dead and are not counted.  A draw with a non-finite coordinate is
+ *   dead for every row.
+ * nnest_glm_pointwise writes eight doubles per data row i < n, stats_dev[i][0 .. 7], all sums over the live s:
+ *     0, 1      a_i = max_s l_is,          P_i = sum_s exp(l_is - a_i)
+ *     2, 3, 4   b_i = max_s (-l_is),       Q_i = sum_s exp(-l_is - b_i),   Q2_i = sum_s exp(2 (-l_is - b_i))
+ *     5         cnt_i, the live draws
+ *     6, 7      mean_i = the mean of l_is, M2_i = sum_s (l_is - mean_i)^2; carried as (count, mean, M2), merged by Chan's rule
+ *   A row with no live draw gives {-inf, 0, -inf, 0, 0, 0, 0, 0}.  (lppd_i = a + log P - log cnt; the WAIC penalty is
+ *   M2 / (cnt - 1); the importance-sampled leave-one-out density is -(b + log Q - log cnt), its effective sample size Q^2 / Q2.)
+ * nnest_glm_predict is the same stream over NEW design rows: the descriptor holds A_new and offset_new (y_dev is ignored but must
+ *   not be NULL), and row j < n gets three doubles stats_dev[j][0 .. 2] = {cnt_j, mean_j, M2_j} of the inverse link
+ *     NNEST_GLM_LOGISTIC: mu_js = 1 / (1 + exp(-eta_js));   NNEST_GLM_POISSON: mu_js = exp(eta_js)
+ *   in float64 from the float32 eta_js.  A pair is live when eta_js and mu_js are finite.
+ * The reduction is deterministic and uses no floating-point atomics: the draws are dealt in tiles of 16 to G = nnest_glm_pointwise_groups
+ *   (S, n) draw groups, each workgroup writes its rows' partial statistics into partials_dev ([G, n, 8] doubles; [G, n, 3] for
+ *   nnest_glm_predict), and a second kernel merges the G partials of a row in index order.  The same call made twice returns the
+ *   same bits.  G depends on (S, n) alone, not on the device.  S = 0 is valid (G = 0) and writes the empty statistics.  The
+ *   statistics of a run cut into launches and merged on the host (a = max a_k, P = sum P_k e^(a_k - a), ...; Chan's rule for slots
+ *   5 - 7: _lib.merge_glm_pointwise) are the single launch's up to reordered float64 addition.  Rows n .. ld - 1 of the descriptor's
+ *   arrays are masked, whatever they hold.  The calls are asynchronous on `stream`.
+ * nnest_glm_pointwise_groups: G for S draws and n rows (0 for S = 0); -1 for S outside 0 .. 2^30 or n outside 1 .. 65536.
+ * NNEST_E_ARG before any launch, the outputs untouched: a NULL glm, t_dev, stats_dev or partials_dev, a D that is not the
+ *   descriptor's, every descriptor nnest_loglike_glm refuses, S outside 0 .. 2^30. */
+int nnest_glm_pointwise_groups(int S, int n);
+int nnest_glm_pointwise(const nnest_glm_t *glm, const float *t_dev, double *stats_dev, double *partials_dev, int S, int D, void *stream);
+int nnest_glm_predict(const nnest_glm_t *glm, const float *t_dev, double *stats_dev, double *partials_dev, int S, int D, void *stream);
 /* IMPORTANCE-SAMPLED EVIDENCE with the trained flow as the proposal: Z = E_q[L(T(x)) pi(T(x)) / q(x)], drawn, evaluated and reduced
  * inside one kernel.  BUILD-DEFINED: the reference has no such estimator.  Sample m is a global 64-bit index; row k of a launch of M
  * samples is m = sample_offset + k:

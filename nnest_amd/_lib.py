@@ -10,6 +10,7 @@ import os
 import ctypes
 import math
 
+import numpy as np
 import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -280,6 +281,10 @@ SIGNATURES = {
     'nnest_loglike_glm': [_vp, _vp, _vp, _i, _i, _vp],
     'nnest_mcmc_glm_check': [_vp, _i],
     'nnest_spline_mcmc_glm_check': [_vp, _i],
+    # their pointwise predictive statistics: (S, n); (glm, t_dev, stats_dev, partials_dev, S, D, stream)
+    'nnest_glm_pointwise_groups': [_i, _i],
+    'nnest_glm_pointwise': [_vp, _vp, _vp, _vp, _i, _i, _vp],
+    'nnest_glm_predict': [_vp, _vp, _vp, _vp, _i, _i, _vp],
     # normal priors beside them: the glm entries' arguments with `const nnest_gauss_prior_t *prior` after `glm`;
     # (prior, t_dev, logp_dev, N, D, stream); (handle, D)
     'nnest_mcmc_glm_prior_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64,
@@ -344,6 +349,51 @@ def importance_result(a, S1, S2, n_live, M):
     ess = S1 * S1 / S2
     err = math.sqrt(max(M / ess - 1.0, 0.0) / (M - 1)) if M > 1 else math.inf
     return dict(logz_x=a + math.log(S1) - math.log(M), ess=ess, logzerr=err, max_weight_share=1.0 / S1, n_live=int(n_live), n_samples=M)
+
+
+def _merge_shifted(m1, s1, m2, s2, powers=(1,)):
+    """max-shifted sums of two sets: m = max(m1, m2), each s[k] = s1[k] e^(powers[k] (m1 - m)) + s2[k] e^(powers[k] (m2 - m));
+    -inf beside -inf has the factor 1, on sums of 0"""
+    m = np.maximum(m1, m2)
+    with np.errstate(invalid='ignore'):
+        e1 = np.where(m1 == m, 1.0, np.exp(m1 - m))
+        e2 = np.where(m2 == m, 1.0, np.exp(m2 - m))
+    return m, [a * e1 ** p + b * e2 ** p for a, b, p in zip(s1, s2, powers)]
+
+
+def _merge_moments(n1, mean1, M21, n2, mean2, M22):
+    """Chan, Golub & LeVeque's rule for (count, mean, M2) of the union of two sets; an empty side leaves the other as it is"""
+    n = n1 + n2
+    safe = np.where(n > 0, n, 1.0)
+    d = mean2 - mean1
+    mean = np.where(n1 == 0, mean2, np.where(n2 == 0, mean1, (n1 * mean1 + n2 * mean2) / safe))
+    M2 = np.where(n1 == 0, M22, np.where(n2 == 0, M21, (M21 + M22) + d * d * (n1 * n2 / safe)))
+    return n, np.where(n > 0, mean, 0.0), np.where(n > 0, M2, 0.0)
+
+
+def empty_glm_pointwise(n, slots=8):
+    """the statistics of no draws at all: [n, 8] rows {-inf, 0, -inf, 0, 0, 0, 0, 0}, or [n, 3] zeros (nnest_glm_predict)"""
+    out = np.zeros((int(n), int(slots)), np.float64)
+    if slots == 8:
+        out[:, 0] = out[:, 2] = -np.inf
+    return out
+
+
+def merge_glm_pointwise(p, q):
+    """the per-row statistics of the union of two sets of draws from the statistics of each (include/nnest_hip.h
+    nnest_glm_pointwise: [n, 8] = {a, P, b, Q, Q2, cnt, mean, M2}; nnest_glm_predict: [n, 3] = {cnt, mean, M2}): the max-shifted
+    sums rescaled to the common maximum, Chan's rule for (cnt, mean, M2).  float64 numpy; the result of a run cut into launches is
+    the single launch's up to reordered float64 addition"""
+    p, q = np.asarray(p, np.float64), np.asarray(q, np.float64)
+    if p.shape != q.shape or p.ndim != 2 or p.shape[1] not in (3, 8):
+        raise ValueError('merge_glm_pointwise: two arrays shaped [n, 8] or [n, 3], got %s and %s' % (p.shape, q.shape))
+    out = np.empty_like(p)
+    k = p.shape[1] - 3
+    if k:
+        out[:, 0], (out[:, 1],) = _merge_shifted(p[:, 0], [p[:, 1]], q[:, 0], [q[:, 1]])
+        out[:, 2], (out[:, 3], out[:, 4]) = _merge_shifted(p[:, 2], [p[:, 3], p[:, 4]], q[:, 2], [q[:, 3], q[:, 4]], powers=(1, 2))
+    out[:, k], out[:, k + 1], out[:, k + 2] = _merge_moments(p[:, k], p[:, k + 1], p[:, k + 2], q[:, k], q[:, k + 1], q[:, k + 2])
+    return out
 
 
 class HostState(ctypes.Structure):   # nnest_host_state_t

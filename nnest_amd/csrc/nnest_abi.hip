@@ -14,6 +14,7 @@
 #include "mcmc_adapt.h"
 #include "mcmc_gdata.h"
 #include "glm_data.h"
+#include "glm_pointwise.h"
 #include "gauss_prior.h"
 
 using namespace nnest;
@@ -768,6 +769,33 @@ int nnest_loglike_glm(const nnest_glm_t *glm, const float *t_dev, double *logl_d
     hipError_t e = launch_loglike_glm(gl, t_dev, logl_dev, N, (hipStream_t)stream);
     if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_loglike_glm: %s", hipGetErrorString(e));
     return NNEST_OK;
+}
+
+// the pointwise predictive statistics of these likelihoods over a set of draws (nnest_glm_pointwise.hip, glm_pointwise.h)
+int nnest_glm_pointwise_groups(int S, int n) {
+    if (S < 0 || S > GLMPW_MAX_DRAWS || n < 1 || n > GLM_MAX_ROWS) return -1;
+    return glm_pointwise_groups(S, n);
+}
+
+static int glm_pointwise_entry(const char *what, int predict, const nnest_glm_t *glm, const float *t_dev, double *stats_dev,
+                               double *partials_dev, int S, int D, void *stream) {
+    GlmSpec gl;
+    int rc;
+    if ((rc = glm_ok(glm, D, &gl))) return rc;
+    if (S < 0 || S > GLMPW_MAX_DRAWS) return fail(NNEST_E_ARG, "%s: S=%d (0 .. %d draws)", what, S, GLMPW_MAX_DRAWS);
+    if (!t_dev || !stats_dev || !partials_dev)
+        return fail(NNEST_E_ARG, "%s: NULL t_dev=%p, stats_dev=%p or partials_dev=%p", what, (const void *)t_dev, (void *)stats_dev, (void *)partials_dev);
+    hipError_t e = launch_glm_pointwise(gl, t_dev, stats_dev, partials_dev, S, predict, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_glm_pointwise: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+int nnest_glm_pointwise(const nnest_glm_t *glm, const float *t_dev, double *stats_dev, double *partials_dev, int S, int D, void *stream) {
+    return glm_pointwise_entry("glm pointwise", 0, glm, t_dev, stats_dev, partials_dev, S, D, stream);
+}
+
+int nnest_glm_predict(const nnest_glm_t *glm, const float *t_dev, double *stats_dev, double *partials_dev, int S, int D, void *stream) {
+    return glm_pointwise_entry("glm predict", 1, glm, t_dev, stats_dev, partials_dev, S, D, stream);
 }
 
 // what nnest_mcmc_glm_steps takes, asked before a launch (and by the entry itself): the shapes and the base of

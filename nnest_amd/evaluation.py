@@ -5,6 +5,8 @@ through their chain and step strides when float32 with a unit dimension stride).
 (the autocorrelation divided by the standard deviation; the ESS sum stopped globally over the dimensions), are in the header.
 There is no CPU path: without a GPU these raise NnestHipError."""
 
+import logging
+
 import numpy as np
 import torch
 
@@ -199,3 +201,30 @@ def gelman_rubin_diagnostic(x, mu=None):
     if x.shape[0] < 2:
         raise ZeroDivisionError('gelman_rubin_diagnostic: one chain (B divides by C - 1)')
     return chain_stats(x, mean=mu, ess=False, rhat_at_mean=mu is not None)['rhat']
+
+
+def predictive_criteria(like, samples, route=None):
+    """The predictive model-comparison criteria of a regression posterior (build-defined: the reference has none) -- the other half
+    of model comparison beside the evidence.  like: a likelihoods.GLMData; samples: [S, x_dim] or [N, steps, x_dim] posterior draws
+    theta (unweighted); route: None, 'host' or 'fused', as GLMData.pointwise takes it (the 'host' route needs no GPU).
+    Returns a dict: the totals over the n data rows elpd_waic, p_waic, lppd, elpd_isloo; their standard errors elpd_waic_se,
+    p_waic_se, lppd_se, elpd_isloo_se = sqrt(n var_i) of the pointwise values (n - 1 in the divisor; NaN for one row);
+    min_isloo_ess, the smallest per-row effective sample size of the leave-one-out weights; pointwise, GLMData.pointwise's dict;
+    n_samples; route.  elpd_isloo is PLAIN importance-sampled leave-one-out, without Pareto smoothing: where min_isloo_ess is small
+    (a handful of draws) it is unreliable and too optimistic -- prefer elpd_waic there, or more draws.  Logs one line."""
+    pw = like.pointwise(samples, route=route)
+    n = len(pw['lppd'])
+    out = {}
+    with np.errstate(invalid='ignore'):
+        for k in ('elpd_waic', 'p_waic', 'lppd', 'elpd_isloo'):
+            out[k] = float(np.sum(pw[k]))
+            out[k + '_se'] = float(np.sqrt(n * np.var(pw[k], ddof=1))) if n > 1 else float('nan')
+    out['min_isloo_ess'] = float(np.min(pw['isloo_ess']))
+    out['pointwise'] = pw
+    out['n_samples'] = int(np.prod(np.shape(samples)[:-1]))
+    out['route'] = like.pointwise_route
+    logging.getLogger(__name__).info('predictive: elpd_waic [%5.4f +- %5.4f] p_waic [%5.4f] lppd [%5.4f] elpd_isloo [%5.4f +- %5.4f] '
+                                     'min IS-LOO ESS [%.1f] rows [%d] route [%s]' % (
+                                         out['elpd_waic'], out['elpd_waic_se'], out['p_waic'], out['lppd'], out['elpd_isloo'],
+                                         out['elpd_isloo_se'], out['min_isloo_ess'], n, out['route']))
+    return out

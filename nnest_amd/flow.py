@@ -1202,6 +1202,41 @@ def loglike_glm(data, t, device=None):
     return out
 
 
+def _glm_pointwise(entry, slots, data, t, device):
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    t = _as_dev_f32(t, dev).contiguous()
+    if t.dim() != 2:
+        raise ValueError('%s: t must be shaped [S, D], got %s' % (entry, tuple(t.shape),))
+    S, D = t.shape
+    with torch.cuda.device(dev):
+        spec, keep = glm_spec(data, dev)
+        if S == 0:
+            t = torch.zeros(1, D, dtype=torch.float32, device=dev)   # (an empty tensor has no pointer; the entry reads nothing of it)
+        n = max(int(spec.n), 1)
+        G = max(_lib.load().nnest_glm_pointwise_groups(S, n), 1)   # (-1: a shape the entry refuses before it touches the partials)
+        out = torch.empty(n, slots, dtype=torch.float64, device=dev)
+        partials = torch.empty(G * n * slots, dtype=torch.float64, device=dev)
+        _lib.check(getattr(_lib.load(), entry)(ctypes.byref(spec), _lib.ptr(t), _lib.ptr(out), _lib.ptr(partials), S, D,
+                                               _lib.current_stream(dev)))
+    return out
+
+
+def glm_pointwise(data, t, device=None):
+    """the pointwise predictive statistics of a regression likelihood of user data over the draws t (nnest_glm_pointwise;
+    include/nnest_hip.h has the definition): data as `glm_spec` takes it, t [S, D] rows that are already T(x) (float32 on the device,
+    or anything convertible; S = 0 is valid).  Returns [n, 8] float64 on the device: per data row {a, P, b, Q, Q2, cnt, mean, M2}
+    over the live draws.  Deterministic: the same call twice returns the same bits.  Asynchronous on the current stream."""
+    return _glm_pointwise('nnest_glm_pointwise', 8, data, t, device)
+
+
+def glm_predict(data, t, device=None):
+    """the posterior predictive mean at new design rows (nnest_glm_predict): data as `glm_spec` takes it with A_new and offset_new in
+    the places of A and the offset (y is ignored), t [S, D] as in `glm_pointwise`.  Returns [n_new, 3] float64 on the device: per new
+    row {cnt, mean, M2} of the inverse link -- 1 / (1 + exp(-eta)) or exp(eta) -- over the live draws.  Asynchronous on the current
+    stream."""
+    return _glm_pointwise('nnest_glm_predict', 3, data, t, device)
+
+
 def gauss_prior_spec(data, device):
     """the nnest_gauss_prior_t of independent normal priors on `device`: data = the mapping priors.GaussianPrior.hip_gauss_prior holds
     (m [D] and r = 1 / sigma [D] float32, arrays or tensors; logc).  Arrays already on the device are used as they are.  Returns

@@ -6,6 +6,7 @@ HIP kernels (include/nnest_hip.h NNEST_LIKE_*), which is where the MCMC evaluati
 import numpy as np
 import scipy.special
 
+from . import _lib
 from ._lib import LIKE_IDS
 
 
@@ -345,3 +346,158 @@ class GLMData(Likelihood):
                 terms = self.y * eta - np.exp(eta)
             logl = self.logl0 + np.sum(terms, axis=1)
         return np.where(np.isfinite(logl), logl, -1e100)
+
+    # ---- pointwise predictive statistics (build-defined: the reference has none; include/nnest_hip.h nnest_glm_pointwise) ----
+    POINTWISE_CHUNK = 1 << 20        # draws per launch of the fused route
+    POINTWISE_HOST_BYTES = 1 << 26   # the host route's [chunk, n] float64 block
+
+    def _draws(self, samples, what):
+        x = np.asarray(samples)
+        if x.ndim == 3:
+            x = x.reshape(-1, x.shape[-1])
+        if x.ndim != 2 or x.shape[1] != self.x_dim:
+            raise ValueError('%s: samples must be shaped [S, %d] or [N, steps, %d], got %s' % (what, self.x_dim, self.x_dim, np.shape(samples)))
+        return x
+
+    @staticmethod
+    def _route(route, what):
+        if route not in (None, 'host', 'fused'):
+            raise ValueError("%s: route=%r: None, 'host' or 'fused'" % (what, route))
+        if route is None:
+            import torch
+            route = 'fused' if torch.cuda.is_available() else 'host'
+        return route
+
+    @staticmethod
+    def _moments(v, live):
+        """(cnt, mean, M2) [n] of the live entries of v [S, n], float64, two passes"""
+        cnt = live.sum(axis=0).astype(np.float64)
+        safe = np.where(cnt > 0, cnt, 1.0)
+        mean = np.where(live, v, 0.0).sum(axis=0) / safe
+        M2 = np.where(live, (np.where(live, v, 0.0) - mean) ** 2, 0.0).sum(axis=0)
+        return cnt, np.where(cnt > 0, mean, 0.0), np.where(cnt > 0, M2, 0.0)
+
+    @classmethod
+    def _pointwise_block(cls, l):
+        """the eight statistics of nnest_glm_pointwise [n, 8] of a block of terms l [S, n]"""
+        live = np.isfinite(l)
+        out = _lib.empty_glm_pointwise(l.shape[1])
+        with np.errstate(invalid='ignore', over='ignore'):
+            for k, v in ((0, l), (2, -l)):
+                m = np.max(np.where(live, v, -np.inf), axis=0, initial=-np.inf)
+                e = np.where(live, np.exp(np.where(live, v, 0.0) - np.where(np.isfinite(m), m, 0.0)), 0.0)
+                out[:, k], out[:, k + 1] = m, e.sum(axis=0)
+                if k == 2:
+                    out[:, 4] = (e * e).sum(axis=0)
+        out[:, 5], out[:, 6], out[:, 7] = cls._moments(l, live)
+        return out
+
+    def _row_terms(self, x):
+        """l [S, n] float64 from the float64 data, without the Poisson lgamma (NaN where eta is not finite: the kernels' rule)"""
+        with np.errstate(over='ignore', invalid='ignore'):
+            eta = self.offset + np.asarray(x, dtype=np.float64) @ self.A.T
+            if self.family == 'logistic':
+                s = (1.0 - 2.0 * self.y) * eta
+                l = -(np.maximum(s, 0.0) + np.log1p(np.exp(-np.abs(s))))
+            else:
+                l = self.y * eta - np.exp(eta)
+        return np.where(np.isfinite(eta), l, np.nan)
+
+    def pointwise_stats(self, samples, route=None, chunk=None):
+        """the per-row statistics [n, 8] float64 (include/nnest_hip.h nnest_glm_pointwise: {a, P, b, Q, Q2, cnt, mean, M2}) of the
+        draws `samples`, and the route taken; `pointwise` has the arguments"""
+        x = self._draws(samples, 'GLMData.pointwise')
+        route = self._route(route, 'GLMData.pointwise')
+        n, S = self.A.shape[0], x.shape[0]
+        stats = _lib.empty_glm_pointwise(n)
+        if route == 'fused':
+            import torch
+            from . import flow
+            chunk = max(1, min(int(self.POINTWISE_CHUNK if chunk is None else chunk), 1 << 30))
+            dev = torch.device('cuda', torch.cuda.current_device())
+            spec = {k: (torch.as_tensor(v).to(dev) if k in ('at', 'y', 'o') else v) for k, v in self.hip_like_glm.items()}
+            for first in range(0, S, chunk):
+                part = flow.glm_pointwise(spec, np.ascontiguousarray(x[first:first + chunk], dtype=np.float32), device=dev)
+                stats = _lib.merge_glm_pointwise(stats, part.cpu().numpy())
+        else:
+            chunk = max(1, int(self.POINTWISE_HOST_BYTES // (8 * n) if chunk is None else chunk))
+            for first in range(0, S, chunk):
+                stats = _lib.merge_glm_pointwise(stats, self._pointwise_block(self._row_terms(x[first:first + chunk])))
+        return stats, route
+
+    def pointwise(self, samples, route=None, chunk=None):
+        """How well the model predicts each observation, from posterior draws (build-defined: the reference has none).  samples:
+        [S, x_dim] or [N, steps, x_dim] (flattened) rows theta, as `sampler.samples` holds them, unweighted.  With l_is = log p(y_i |
+        theta_s) and the sums over the LIVE draws of a row (l_is finite; a draw with a non-finite coordinate is dead for every row),
+        returns a dict of float64 arrays of length n:
+            lppd        log mean_s exp(l_is)                      the log pointwise predictive density
+            p_waic      var_s l_is (n - 1 in the divisor)         WAIC's effective number of parameters; NaN below 2 live draws
+            elpd_waic   lppd - p_waic
+            elpd_isloo  -log mean_s exp(-l_is)                    leave-one-out by plain importance sampling (weights 1 / p(y_i | theta_s))
+            isloo_ess   (sum_s w_is)^2 / sum_s w_is^2             the effective sample size of those weights
+            mean_logl   mean_s l_is
+            n_live      the live draws
+        The Poisson -lgamma(y_i + 1) is added on the host to lppd, elpd_isloo and mean_logl: these are log p(y_i | .), normalised.
+        PLAIN importance-sampled leave-one-out is UNRELIABLE for a row whose isloo_ess is small: its weights have a heavy tail there
+        and elpd_isloo is then too high; Pareto smoothing (PSIS) is not built.  Read isloo_ess before elpd_isloo.
+        route: 'fused' -- the product on the matrix cores, the float64 term and the reduction over the draws inside one kernel
+        (include/nnest_hip.h nnest_glm_pointwise), float32 data and draws, in launches of `chunk` draws merged by
+        _lib.merge_glm_pointwise; 'host' -- the same statistics in chunked float64 numpy from the float64 data, no GPU needed; None
+        -- 'fused' where a device is available.  The route taken is left in `pointwise_route`."""
+        stats, route = self.pointwise_stats(samples, route, chunk)
+        self.pointwise_route = route
+        return self.pointwise_from_stats(stats)
+
+    def pointwise_from_stats(self, stats):
+        """`pointwise`'s dict from the statistics [n, 8]"""
+        a, P, b, Q, Q2, cnt, mean, M2 = np.asarray(stats, np.float64).T
+        norm = -scipy.special.gammaln(self.y + 1.0) if self.family == 'poisson' else np.zeros_like(self.y)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            lppd = np.where(cnt > 0, a + np.log(P) - np.log(cnt) + norm, np.nan)   # (no live draw: nothing to average)
+            p_waic = np.where(cnt >= 2, M2 / np.where(cnt >= 2, cnt - 1.0, 1.0), np.nan)
+            isloo = np.where(cnt > 0, -(b + np.log(Q) - np.log(cnt)) + norm, np.nan)
+            ess = np.where(Q2 > 0, Q * Q / np.where(Q2 > 0, Q2, 1.0), 0.0)
+        return dict(lppd=lppd, p_waic=p_waic, elpd_waic=lppd - p_waic, elpd_isloo=isloo, isloo_ess=ess,
+                    mean_logl=np.where(cnt > 0, mean + norm, np.nan), n_live=cnt)
+
+    def predict(self, samples, A_new, offset_new=None, route=None):
+        """The posterior predictive mean at new design rows: A_new [n_new, x_dim], offset_new [n_new] or None; samples and route as
+        `pointwise` takes them.  Returns a dict of float64 arrays of length n_new: mean and sd (n - 1 in the divisor; NaN below 2
+        live draws) over the live draws of mu = 1 / (1 + exp(-eta)) (logistic) or exp(eta) (poisson), eta = offset_new + A_new theta,
+        and n_live (eta and mu finite).  ValueError for shapes the constructor would refuse."""
+        x = self._draws(samples, 'GLMData.predict')
+        route = self._route(route, 'GLMData.predict')
+        A = np.array(A_new, dtype=np.float64)
+        if A.ndim != 2 or A.shape[1] != self.x_dim or not 1 <= A.shape[0] <= self.MAX_ROWS:
+            raise ValueError('GLMData.predict: A_new must be shaped [n_new, %d] with n_new in 1 .. %d, got %s' % (self.x_dim, self.MAX_ROWS, A.shape))
+        n = A.shape[0]
+        o = np.zeros(n) if offset_new is None else np.array(offset_new, dtype=np.float64)
+        if o.shape != (n,):
+            raise ValueError('GLMData.predict: offset_new must be shaped [%d], got %s' % (n, o.shape))
+        if not (np.all(np.isfinite(A)) and np.all(np.isfinite(o))):
+            raise ValueError('GLMData.predict: A_new and offset_new must be finite')
+        stats = _lib.empty_glm_pointwise(n, 3)
+        if route == 'fused':
+            import torch
+            from . import flow
+            dev = torch.device('cuda', torch.cuda.current_device())
+            at, yy, oo = self.layout(A, np.zeros(n), o)
+            spec = dict(at=torch.as_tensor(at).to(dev), y=torch.as_tensor(yy).to(dev), o=torch.as_tensor(oo).to(dev), logl0=0.0, n=n,
+                        family=self.family)
+            for first in range(0, x.shape[0], self.POINTWISE_CHUNK):
+                part = flow.glm_predict(spec, np.ascontiguousarray(x[first:first + self.POINTWISE_CHUNK], dtype=np.float32), device=dev)
+                stats = _lib.merge_glm_pointwise(stats, part.cpu().numpy())
+        else:
+            chunk = max(1, self.POINTWISE_HOST_BYTES // (8 * n))
+            for first in range(0, x.shape[0], chunk):
+                with np.errstate(over='ignore', invalid='ignore'):
+                    eta = o + np.asarray(x[first:first + chunk], dtype=np.float64) @ A.T
+                    mu = 1.0 / (1.0 + np.exp(-eta)) if self.family == 'logistic' else np.exp(eta)
+                block = np.stack(self._moments(mu, np.isfinite(eta) & np.isfinite(mu)), axis=1)
+                stats = _lib.merge_glm_pointwise(stats, block)
+        cnt, mean, M2 = stats.T
+        with np.errstate(invalid='ignore'):
+            sd = np.where(cnt >= 2, np.sqrt(M2 / np.where(cnt >= 2, cnt - 1.0, 1.0)), np.nan)
+        self.predict_route = route
+        return dict(mean=np.where(cnt > 0, mean, np.nan), sd=sd, n_live=cnt)
+
