@@ -6,7 +6,15 @@ runs and, under each with global steps, has among the walkers that start inside 
 whose walker's decisions up to there all lie further than ten times the tolerance in force from their thresholds
 (tile_like_check.seed_is_fair).  Prints the two tables tile_like_check.WALK_SEEDS and DATA_SEEDS hold.
 
-Usage: python tools/walk_like_cases.py [walk|data]"""
+`prior` chooses the prior width and the seed of every case of tests/test_gpu_prior_tile.py the same way (tests/prior_tile_check.py
+pick): widths 1, 2, 0.5, 0.25, each moved to the first base (1 + j / 4096) under which the float32 restatement of the prior term
+leaves half of B_pi unused on the case's start, and sixty seeds from 9000 + x_dim on, four hundred where those hold no fair pair; the
+first pair under which the restatement with the normal prior in the target, at tile_like_check.DATA_CONFIG, moves some but not all
+local steps, accepts and refuses a global proposal, starts with more than C / 4 finite rows and has NO acceptance margin within ten
+times the tolerance in force -- the flow's, plus B, plus B_pi.  It prints the tables prior_tile_check.PRIOR_SEEDS and
+BORDER_EXCEPTIONS hold; a case without such a pair is printed with the fair pair that has the fewest borderline decisions.
+
+Usage: python tools/walk_like_cases.py [walk|data|prior]"""
 import os
 import sys
 
@@ -40,9 +48,30 @@ def choose_data():
     print('}')
 
 
+def _pick_prior(case):
+    from tests import prior_tile_check as pt
+    return (case,) + pt.pick(case)
+
+
+def choose_prior():
+    import multiprocessing
+    from tests import prior_tile_check as pt
+    exceptions = {}
+    print('PRIOR_SEEDS = {')
+    with multiprocessing.Pool(12) as pool:
+        for case, width, seed, st, exact in pool.imap(_pick_prior, pt.CASES):
+            print('    %r: (%r, %d),   # %s' % (case, width, seed, st), flush=True)
+            if not exact:
+                exceptions[case] = st['border']
+    print('}')
+    print('BORDER_EXCEPTIONS = %r' % (exceptions,))
+
+
 if __name__ == '__main__':
     what = sys.argv[1] if len(sys.argv) > 1 else 'both'
     if what in ('walk', 'both'):
         choose_walk()
     if what in ('data', 'both'):
         choose_data()
+    if what == 'prior':
+        choose_prior()
