@@ -800,6 +800,53 @@ int nnest_spline_mcmc_glm_prior_steps(struct nnest_spline *spl, const nnest_glm_
 int nnest_glm_pointwise_groups(int S, int n);
 int nnest_glm_pointwise(const nnest_glm_t *glm, const float *t_dev, double *stats_dev, double *partials_dev, int S, int D, void *stream);
 int nnest_glm_predict(const nnest_glm_t *glm, const float *t_dev, double *stats_dev, double *partials_dev, int S, int D, void *stream);
+/* PARETO-SMOOTHED LEAVE-ONE-OUT (PSIS-LOO) of the same likelihoods over the same draws, and the matrix of their terms
+ * (nnest_glm_psis.hip, glm_psis.h).  BUILD-DEFINED, to the operation: the reference has no such estimator.  (All
+ * added within ABI 15.)  eta_is and l_is are nnest_glm_pointwise's, to the bit: the kernels stream the draws in its layout.
+ * nnest_glm_terms writes the matrix itself: out_dev [S, n] float64, out[s][i] = l_is, NaN for a dead pair.  S = 0 writes nothing.
+ *   NNEST_E_ARG before any launch: what nnest_glm_pointwise refuses, a NULL out_dev, S n above 2^30.
+ * nnest_glm_psis: per data row i, over its live draws, with b_i and cnt_i the slots 2 and 5 of stats_dev [n, 8] = what
+ *   nnest_glm_pointwise wrote FOR THE SAME t_dev AND S (read only),
+ *     d_s   = b_i - (-l_is) >= 0                       float64
+ *     M*    = min(cnt / 5, ceil(3 sqrt(cnt)))          integers; ceil(3 sqrt(cnt)) the smallest m with m^2 >= 9 cnt
+ *     c_i   = the largest double whose low 40 bits are zero with #{s : d_s < c_i} <= M*  (a bin edge of key(d) = the top 24 bits of
+ *             the pattern of d, so that tied draws go in or out together); 0 for a row with no live draw
+ *     tail  = {s : d_s < c_i}, M_i its size (0 when the bin of d = 0 alone holds more than M* draws)
+ *     body  = the others: N_body their number, B = sum e^(-d), B2 = sum (e^(-d))^2
+ *   and, where M_i >= 5, Zhang & Stephens' (2009) fit of a generalised Pareto distribution to the tail's exceedances, with the
+ *   prior of loo::gpdfit: u = e^(-c_i); x_(1) <= .. <= x_(M) the sorted e^(-d) - u; m = 30 + floor(sqrt(M));
+ *   x* = x_(floor(M / 4 + 0.5)); theta_j = 1 / x_(M) + (1 - sqrt(m / (j - 1/2))) / (3 x*), j = 1 .. m; k_j = mean log1p(-theta_j x);
+ *   L_j = M (log(-theta_j / k_j) - k_j - 1); w_j = 1 / sum_i exp(L_i - L_j) (an overflow to +inf: 0); theta^ = sum theta_j w_j;
+ *   k = mean log1p(-theta^ x); sigma = -k / theta^; k^ = (k M + 5) / (M + 10).  The smoothed tail: p_j = (j - 1/2) / M,
+ *   q_j = min(1, u + sigma expm1(-k^ log1p(-p_j)) / k^) (for |k^| < 2^-40: u - sigma log1p(-p_j)), beside d_(j), the d of x_(j).
+ *     log numerator   = log(N_body + sum_j q_j e^(d_(j)))
+ *     log denominator = log(B + sum_j q_j)
+ *     elpd_psis       = (-b_i + log numerator) - log denominator
+ *     psis_ess        = (B + sum q)^2 / (B2 + sum q^2)
+ *   Where M_i < 5 there is no fit: k^ = +inf, sigma = NaN, and q_j = e^(-d_(j)), the raw weights, with the numerator N_body + M_i:
+ *   the plain importance-sampling estimate.  A k that is not finite: k^ = NaN, sigma = NaN, and the plain estimate likewise.
+ *   out_dev [n, 16] float64, row i: {0 c_i, 1 M_i, 2 N_body, 3 B, 4 B2, 5 sigma, 6 k^, 7 log numerator, 8 log denominator,
+ *   9 elpd_psis (NaN for a row with no live draw), 10 psis_ess (0 then), 11 flag, 12 M*, 13 theta^ (NaN without a fit), 14, 15 zero}.
+ *   flag: 1 = a tail value found no slot and was dropped (never with a stats_dev of these draws), 2 = no fit (M_i < 5), 4 = k not
+ *   finite.  (The Poisson -lgamma(y_i + 1) is the caller's to add to elpd_psis.)
+ *   work_dev: nnest_glm_psis_work_bytes(S, n) bytes.  Its first n Mcap doubles, Mcap = nnest_glm_psis_tail_cap(S) = ceil(3 sqrt(S))
+ *   (1 for S = 0), are the tail buffer [n, Mcap]: behind the call, row i holds its M_i tail values d sorted ascending in its first
+ *   M_i slots; the other slots are not written.  The rest -- the draw groups' body sums, the digit counts, the prefixes and the slot
+ *   counters -- is scratch.  Nothing is written past the stated sizes nor to rows i >= n; rows n .. ld - 1 of the descriptor are masked.
+ *   The cutoff comes from three streaming passes that count one 8-bit digit of the key each (integer atomics), a fourth pass
+ *   collects the tail and the body sums, a fit kernel sorts the tail and does the rest in a fixed order: no floating-point atomics,
+ *   the same call twice returns the same bits.  All S draws are resident in one call: S <= 2^20 (thin a longer run), and the work
+ *   buffer at most 2^30 bytes.  S = 0 is valid and writes the empty result {0, 0, 0, 0, 0, NaN, +inf, -inf, -inf, NaN, 0, 2, 0, NaN,
+ *   0, 0}.  Asynchronous on `stream`.
+ * nnest_glm_psis_work_bytes: the bytes of work_dev; -1 for S outside 0 .. 2^20, n outside 1 .. 65536 or more than 2^30 bytes.
+ * nnest_glm_psis_tail_cap: Mcap; -1 for S outside 0 .. 2^20.
+ * NNEST_E_ARG before any launch, the outputs untouched: everything nnest_glm_pointwise refuses, a NULL stats_dev, out_dev or
+ *   work_dev, S above 2^20, a work size above 2^30 bytes. */
+int nnest_glm_terms(const nnest_glm_t *glm, const float *t_dev, double *out_dev, int S, int D, void *stream);
+int nnest_glm_psis_tail_cap(int S);
+long long nnest_glm_psis_work_bytes(int S, int n);
+int nnest_glm_psis(const nnest_glm_t *glm, const float *t_dev, const double *stats_dev, double *out_dev, void *work_dev, int S, int D,
+                   void *stream);
 /* IMPORTANCE-SAMPLED EVIDENCE with the trained flow as the proposal: Z = E_q[L(T(x)) pi(T(x)) / q(x)], drawn, evaluated and reduced
  * inside one kernel.  BUILD-DEFINED: the reference has no such estimator.  Sample m is a global 64-bit index; row k of a launch of M
  * samples is m = sample_offset + k:

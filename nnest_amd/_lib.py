@@ -285,6 +285,12 @@ SIGNATURES = {
     'nnest_glm_pointwise_groups': [_i, _i],
     'nnest_glm_pointwise': [_vp, _vp, _vp, _vp, _i, _i, _vp],
     'nnest_glm_predict': [_vp, _vp, _vp, _vp, _i, _i, _vp],
+    # the matrix of terms (glm, t_dev, out_dev, S, D, stream); Pareto-smoothed leave-one-out: (S); (S, n);
+    # (glm, t_dev, stats_dev, out_dev, work_dev, S, D, stream)
+    'nnest_glm_terms': [_vp, _vp, _vp, _i, _i, _vp],
+    'nnest_glm_psis_tail_cap': [_i],
+    'nnest_glm_psis_work_bytes': [_i, _i],
+    'nnest_glm_psis': [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     # normal priors beside them: the glm entries' arguments with `const nnest_gauss_prior_t *prior` after `glm`;
     # (prior, t_dev, logp_dev, N, D, stream); (handle, D)
     'nnest_mcmc_glm_prior_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64,
@@ -423,7 +429,8 @@ def load():
             fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
             fn.argtypes = argtypes
             fn.restype = (ctypes.c_char_p if name == 'nnest_hip_last_error' else ctypes.c_long if name in ('nnest_format_rows_e5', 'nnest_format_scalar_rows')
-                          else ctypes.c_double if name == 'nnest_host_h_update' else ctypes.c_int)
+                          else ctypes.c_double if name == 'nnest_host_h_update'
+                          else ctypes.c_longlong if name == 'nnest_glm_psis_work_bytes' else ctypes.c_int)
         _lib = lib
     return _lib
 

@@ -102,6 +102,36 @@ template <> struct PwSlots<PwMoments> {
     __device__ static __forceinline__ PwMoments empty() { return pw_moments_empty(); }
 };
 
+// ---- the wave's operands, shared by every kernel that streams the draws in this layout (nnest_glm_pointwise.hip, nnest_glm_psis.hip):
+// lane = 16 g + m.  The same loads and the same MFMA order give the same bits of eta in each of them. ----
+// the tile's operand: of draw min(s, S - 1), the columns 32 tau + 8 g + j
+template <int NT>
+__device__ __forceinline__ void pw_load_tile(const float *__restrict__ t, long s, int S, int D, int g, float (&b)[NT][8]) {
+    const float *row = t + (size_t)(s < S ? s : S - 1) * D;
+#pragma unroll
+    for (int tau = 0; tau < NT; ++tau)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = 32 * tau + 8 * g + j;
+            const float v = row[min(c, D - 1)];
+            b[tau][j] = c < D ? v : 0.f;
+        }
+}
+// the invariant operand: A[16 rb + m, 32 tau + 8 g + j], read once from at
+template <int NT>
+__device__ __forceinline__ void pw_load_a(const GlmSpec &gl, int rb, int m, int g, float (&a)[NT][8]) {
+    const int D = gl.D;
+    const size_t ld = (size_t)gl.ld;
+#pragma unroll
+    for (int tau = 0; tau < NT; ++tau)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = 32 * tau + 8 * g + j;
+            const float v = gl.at[(size_t)min(c, D - 1) * ld + 16 * rb + m];   // (no read past [D, ld])
+            a[tau][j] = c < D ? v : 0.f;
+        }
+}
+
 // nnest_glm_pointwise.hip.  G, the draw groups of S draws over n rows (the partials are [G, n, slots]): enough for
 // GLMPW_TARGET_GROUPS workgroups at ceil(n / 64) row groups, at least GLMPW_MIN_TILES tiles of draws each, G n bounded.  A function
 // of (S, n) alone -- not of the device: the same call gives the same bits on any part

@@ -15,6 +15,7 @@
 #include "mcmc_gdata.h"
 #include "glm_data.h"
 #include "glm_pointwise.h"
+#include "glm_psis.h"
 #include "gauss_prior.h"
 
 using namespace nnest;
@@ -796,6 +797,46 @@ int nnest_glm_pointwise(const nnest_glm_t *glm, const float *t_dev, double *stat
 
 int nnest_glm_predict(const nnest_glm_t *glm, const float *t_dev, double *stats_dev, double *partials_dev, int S, int D, void *stream) {
     return glm_pointwise_entry("glm predict", 1, glm, t_dev, stats_dev, partials_dev, S, D, stream);
+}
+
+// their matrix of terms and Pareto-smoothed leave-one-out (nnest_glm_psis.hip, glm_psis.h)
+int nnest_glm_terms(const nnest_glm_t *glm, const float *t_dev, double *out_dev, int S, int D, void *stream) {
+    GlmSpec gl;
+    int rc;
+    if ((rc = glm_ok(glm, D, &gl))) return rc;
+    if (S < 0 || S > GLMPW_MAX_DRAWS || (long long)S * gl.n > GLMPSIS_MAX_TERMS)
+        return fail(NNEST_E_ARG, "glm terms: S=%d, n=%d (S >= 0, S n <= %lld)", S, gl.n, GLMPSIS_MAX_TERMS);
+    if (!t_dev || !out_dev) return fail(NNEST_E_ARG, "glm terms: NULL t_dev=%p or out_dev=%p", (const void *)t_dev, (void *)out_dev);
+    hipError_t e = launch_glm_terms(gl, t_dev, out_dev, S, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_glm_terms: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+int nnest_glm_psis_tail_cap(int S) {
+    if (S < 0 || S > GLMPSIS_MAX_DRAWS) return -1;
+    return glm_psis_tail_cap(S);
+}
+
+long long nnest_glm_psis_work_bytes(int S, int n) {
+    if (S < 0 || S > GLMPSIS_MAX_DRAWS || n < 1 || n > GLM_MAX_ROWS) return -1;
+    const long long bytes = glm_psis_work(S, n).bytes;
+    return bytes > GLMPSIS_MAX_WORK ? -1 : bytes;
+}
+
+int nnest_glm_psis(const nnest_glm_t *glm, const float *t_dev, const double *stats_dev, double *out_dev, void *work_dev, int S, int D,
+                   void *stream) {
+    GlmSpec gl;
+    int rc;
+    if ((rc = glm_ok(glm, D, &gl))) return rc;
+    if (S < 0 || S > GLMPSIS_MAX_DRAWS) return fail(NNEST_E_ARG, "glm psis: S=%d (0 .. %d draws in one call: thin a longer run)", S, GLMPSIS_MAX_DRAWS);
+    if (nnest_glm_psis_work_bytes(S, gl.n) < 0)
+        return fail(NNEST_E_ARG, "glm psis: S=%d, n=%d need more than %lld bytes of work (thin the draws)", S, gl.n, GLMPSIS_MAX_WORK);
+    if (!t_dev || !stats_dev || !out_dev || !work_dev)
+        return fail(NNEST_E_ARG, "glm psis: NULL t_dev=%p, stats_dev=%p, out_dev=%p or work_dev=%p", (const void *)t_dev, (const void *)stats_dev,
+                    (void *)out_dev, work_dev);
+    hipError_t e = launch_glm_psis(gl, t_dev, stats_dev, out_dev, work_dev, S, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_glm_psis: %s", hipGetErrorString(e));
+    return NNEST_OK;
 }
 
 // what nnest_mcmc_glm_steps takes, asked before a launch (and by the entry itself): the shapes and the base of

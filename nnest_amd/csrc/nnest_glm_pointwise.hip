@@ -46,39 +46,17 @@ __device__ __forceinline__ PwStats pw_xor(const PwStats &r, int k) {
     return PwStats{pw_xor(r.p, k), pw_xor(r.q, k), __shfl_xor(r.n, k), __shfl_xor(r.mean, k), __shfl_xor(r.m2, k)};
 }
 
-// the tile's operand: of draw min(s, S - 1), the columns 32 tau + 8 g + j
-template <int NT>
-__device__ __forceinline__ void pw_load_tile(const float *__restrict__ t, long s, int S, int D, int g, float (&b)[NT][8]) {
-    const float *row = t + (size_t)(s < S ? s : S - 1) * D;
-#pragma unroll
-    for (int tau = 0; tau < NT; ++tau)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int c = 32 * tau + 8 * g + j;
-            const float v = row[min(c, D - 1)];
-            b[tau][j] = c < D ? v : 0.f;
-        }
-}
-
 template <int NT, int FAM, int PRED>
 __global__ void __launch_bounds__(256) glm_pointwise_kernel(GlmSpec gl, const float *__restrict__ t, double *__restrict__ partials, int S, int G) {
     using T = typename std::conditional<PRED != 0, PwMoments, PwStats>::type;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = lane & 15, g = lane >> 4;
     const int D = gl.D, n = gl.n;
-    const size_t ld = (size_t)gl.ld;
     const int rb = 4 * blockIdx.x + wave, chunk = blockIdx.y;
     if (16 * rb >= n) return;   // (uniform in the wave; no barrier follows)
     const int i0 = 16 * rb + 4 * g;
     float a[NT][8];
-#pragma unroll
-    for (int tau = 0; tau < NT; ++tau)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int c = 32 * tau + 8 * g + j;
-            const float v = gl.at[(size_t)min(c, D - 1) * ld + 16 * rb + m];   // (no read past [D, ld])
-            a[tau][j] = c < D ? v : 0.f;
-        }
+    pw_load_a<NT>(gl, rb, m, g, a);
     const f32x4 off = *reinterpret_cast<const f32x4 *>(gl.o + i0);
     f32x4 yv = f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (!PRED) yv = *reinterpret_cast<const f32x4 *>(gl.y + i0);

@@ -203,7 +203,7 @@ def gelman_rubin_diagnostic(x, mu=None):
     return chain_stats(x, mean=mu, ess=False, rhat_at_mean=mu is not None)['rhat']
 
 
-def predictive_criteria(like, samples, route=None):
+def predictive_criteria(like, samples, route=None, psis=False):
     """The predictive model-comparison criteria of a regression posterior (build-defined: the reference has none) -- the other half
     of model comparison beside the evidence.  like: a likelihoods.GLMData; samples: [S, x_dim] or [N, steps, x_dim] posterior draws
     theta (unweighted); route: None, 'host' or 'fused', as GLMData.pointwise takes it (the 'host' route needs no GPU).
@@ -211,8 +211,11 @@ def predictive_criteria(like, samples, route=None):
     p_waic_se, lppd_se, elpd_isloo_se = sqrt(n var_i) of the pointwise values (n - 1 in the divisor; NaN for one row);
     min_isloo_ess, the smallest per-row effective sample size of the leave-one-out weights; pointwise, GLMData.pointwise's dict;
     n_samples; route.  elpd_isloo is PLAIN importance-sampled leave-one-out, without Pareto smoothing: where min_isloo_ess is small
-    (a handful of draws) it is unreliable and too optimistic -- prefer elpd_waic there, or more draws.  Logs one line."""
-    pw = like.pointwise(samples, route=route)
+    (a handful of draws) it is unreliable and too optimistic -- prefer elpd_waic there, or more draws.  psis=True adds Pareto-smoothed
+    leave-one-out (GLMData.pointwise has it): the totals elpd_psis, elpd_psis_se and p_loo; max_pareto_k, the largest fitted shape
+    (NaN and +inf -- no fit -- aside); n_pareto_k_bad, the rows whose khat is above loo's threshold min(1 - 1 / log10(S), 0.7) and
+    whose elpd_psis is therefore unreliable; pareto_k_threshold.  Logs one line."""
+    pw = like.pointwise(samples, route=route, psis=True) if psis else like.pointwise(samples, route=route)
     n = len(pw['lppd'])
     out = {}
     with np.errstate(invalid='ignore'):
@@ -223,8 +226,22 @@ def predictive_criteria(like, samples, route=None):
     out['pointwise'] = pw
     out['n_samples'] = int(np.prod(np.shape(samples)[:-1]))
     out['route'] = like.pointwise_route
+    extra = ''
+    if psis:
+        from .psis import pareto_k_threshold
+        with np.errstate(invalid='ignore'):
+            out['elpd_psis'] = float(np.sum(pw['elpd_psis']))
+            out['elpd_psis_se'] = float(np.sqrt(n * np.var(pw['elpd_psis'], ddof=1))) if n > 1 else float('nan')
+            out['p_loo'] = float(np.sum(pw['p_loo']))
+            k = pw['pareto_k']
+            fitted = k[np.isfinite(k)]
+            out['max_pareto_k'] = float(np.max(fitted)) if len(fitted) else float('nan')
+            out['pareto_k_threshold'] = pareto_k_threshold(out['n_samples'])
+            out['n_pareto_k_bad'] = int(np.sum(fitted > out['pareto_k_threshold']))
+        extra = ' elpd_psis [%5.4f +- %5.4f] p_loo [%5.4f] max Pareto k [%.3f] rows above %.2f [%d]' % (
+            out['elpd_psis'], out['elpd_psis_se'], out['p_loo'], out['max_pareto_k'], out['pareto_k_threshold'], out['n_pareto_k_bad'])
     logging.getLogger(__name__).info('predictive: elpd_waic [%5.4f +- %5.4f] p_waic [%5.4f] lppd [%5.4f] elpd_isloo [%5.4f +- %5.4f] '
-                                     'min IS-LOO ESS [%.1f] rows [%d] route [%s]' % (
+                                     'min IS-LOO ESS [%.1f] rows [%d] route [%s]%s' % (
                                          out['elpd_waic'], out['elpd_waic_se'], out['p_waic'], out['lppd'], out['elpd_isloo'],
-                                         out['elpd_isloo_se'], out['min_isloo_ess'], n, out['route']))
+                                         out['elpd_isloo_se'], out['min_isloo_ess'], n, out['route'], extra))
     return out

@@ -1237,6 +1237,49 @@ def glm_predict(data, t, device=None):
     return _glm_pointwise('nnest_glm_predict', 3, data, t, device)
 
 
+def glm_terms(data, t, device=None):
+    """the matrix of terms l_is = log p(y_i | theta_s) of a regression likelihood of user data over the draws t (nnest_glm_terms):
+    data and t as `glm_pointwise` takes them.  Returns [S, n] float64 on the device, NaN for a dead pair, with the bits
+    `glm_pointwise` reduced.  Asynchronous on the current stream."""
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    t = _as_dev_f32(t, dev).contiguous()
+    if t.dim() != 2:
+        raise ValueError('glm_terms: t must be shaped [S, D], got %s' % (tuple(t.shape),))
+    S, D = t.shape
+    with torch.cuda.device(dev):
+        spec, keep = glm_spec(data, dev)
+        n = max(int(spec.n), 1)
+        out = torch.empty(S, n, dtype=torch.float64, device=dev)
+        if S == 0:
+            return out
+        _lib.check(_lib.load().nnest_glm_terms(ctypes.byref(spec), _lib.ptr(t), _lib.ptr(out), S, D, _lib.current_stream(dev)))
+    return out
+
+
+def glm_psis(data, t, device=None, with_work=False):
+    """Pareto-smoothed leave-one-out of a regression likelihood of user data over the draws t (nnest_glm_psis; include/nnest_hip.h
+    has the definition): data and t as `glm_pointwise` takes them, at most 2^20 draws.  Runs nnest_glm_pointwise first for the row
+    statistics.  Returns (stats [n, 8], out [n, 16]) float64 on the device -- with_work: and the work buffer (uint8), whose first
+    n Mcap doubles are the rows' sorted tails.  Deterministic.  Asynchronous on the current stream."""
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    t = _as_dev_f32(t, dev).contiguous()
+    if t.dim() != 2:
+        raise ValueError('glm_psis: t must be shaped [S, D], got %s' % (tuple(t.shape),))
+    S, D = t.shape
+    stats = glm_pointwise(data, t, dev)
+    with torch.cuda.device(dev):
+        spec, keep = glm_spec(data, dev)
+        if S == 0:
+            t = torch.zeros(1, D, dtype=torch.float32, device=dev)   # (an empty tensor has no pointer; the entry reads nothing of it)
+        n = max(int(spec.n), 1)
+        nbytes = int(_lib.load().nnest_glm_psis_work_bytes(S, n))
+        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)   # (-1: a shape the entry refuses before it touches the buffer)
+        out = torch.empty(n, 16, dtype=torch.float64, device=dev)
+        _lib.check(_lib.load().nnest_glm_psis(ctypes.byref(spec), _lib.ptr(t), _lib.ptr(stats), _lib.ptr(out), _lib.ptr(work), S, D,
+                                              _lib.current_stream(dev)))
+    return (stats, out, work) if with_work else (stats, out)
+
+
 def gauss_prior_spec(data, device):
     """the nnest_gauss_prior_t of independent normal priors on `device`: data = the mapping priors.GaussianPrior.hip_gauss_prior holds
     (m [D] and r = 1 / sigma [D] float32, arrays or tensors; logc).  Arrays already on the device are used as they are.  Returns

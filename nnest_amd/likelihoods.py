@@ -392,15 +392,17 @@ class GLMData(Likelihood):
         out[:, 5], out[:, 6], out[:, 7] = cls._moments(l, live)
         return out
 
-    def _row_terms(self, x):
-        """l [S, n] float64 from the float64 data, without the Poisson lgamma (NaN where eta is not finite: the kernels' rule)"""
+    def _row_terms(self, x, rows=slice(None)):
+        """l [S, n] float64 from the float64 data (of the data rows `rows`), without the Poisson lgamma (NaN where eta is not
+        finite: the kernels' rule)"""
+        y = self.y[rows]
         with np.errstate(over='ignore', invalid='ignore'):
-            eta = self.offset + np.asarray(x, dtype=np.float64) @ self.A.T
+            eta = self.offset[rows] + np.asarray(x, dtype=np.float64) @ self.A[rows].T
             if self.family == 'logistic':
-                s = (1.0 - 2.0 * self.y) * eta
+                s = (1.0 - 2.0 * y) * eta
                 l = -(np.maximum(s, 0.0) + np.log1p(np.exp(-np.abs(s))))
             else:
-                l = self.y * eta - np.exp(eta)
+                l = y * eta - np.exp(eta)
         return np.where(np.isfinite(eta), l, np.nan)
 
     def pointwise_stats(self, samples, route=None, chunk=None):
@@ -425,7 +427,7 @@ class GLMData(Likelihood):
                 stats = _lib.merge_glm_pointwise(stats, self._pointwise_block(self._row_terms(x[first:first + chunk])))
         return stats, route
 
-    def pointwise(self, samples, route=None, chunk=None):
+    def pointwise(self, samples, route=None, chunk=None, psis=False):
         """How well the model predicts each observation, from posterior draws (build-defined: the reference has none).  samples:
         [S, x_dim] or [N, steps, x_dim] (flattened) rows theta, as `sampler.samples` holds them, unweighted.  With l_is = log p(y_i |
         theta_s) and the sums over the LIVE draws of a row (l_is finite; a draw with a non-finite coordinate is dead for every row),
@@ -439,14 +441,78 @@ class GLMData(Likelihood):
             n_live      the live draws
         The Poisson -lgamma(y_i + 1) is added on the host to lppd, elpd_isloo and mean_logl: these are log p(y_i | .), normalised.
         PLAIN importance-sampled leave-one-out is UNRELIABLE for a row whose isloo_ess is small: its weights have a heavy tail there
-        and elpd_isloo is then too high; Pareto smoothing (PSIS) is not built.  Read isloo_ess before elpd_isloo.
+        and elpd_isloo is then too high.  psis=True adds PARETO-SMOOTHED leave-one-out (PSIS-LOO; include/nnest_hip.h nnest_glm_psis
+        and nnest_amd/psis.py have the definition, to the operation):
+            elpd_psis   the leave-one-out density with the row's M largest weights replaced by the quantiles of a generalised
+                        Pareto distribution fitted to them (Zhang & Stephens' fit, as loo::gpdfit), truncated at the largest raw one
+            pareto_k    the fitted shape khat, the diagnostic: above min(1 - 1 / log10(S), 0.7) the row's estimate is unreliable
+                        whatever the number of draws; +inf where the tail was too small for a fit (fewer than 5 values: elpd_psis is
+                        then elpd_isloo), NaN where the fit failed
+            psis_ess    the effective sample size of the smoothed weights
+            psis_tail   M, the weights that were smoothed
+            p_loo       lppd - elpd_psis
+        All draws are resident at once there: at most 2^20 draws, and a bounded work buffer -- a ValueError above either: thin the run.
+        With psis=False the dict is the one above, key for key.
         route: 'fused' -- the product on the matrix cores, the float64 term and the reduction over the draws inside one kernel
         (include/nnest_hip.h nnest_glm_pointwise), float32 data and draws, in launches of `chunk` draws merged by
         _lib.merge_glm_pointwise; 'host' -- the same statistics in chunked float64 numpy from the float64 data, no GPU needed; None
         -- 'fused' where a device is available.  The route taken is left in `pointwise_route`."""
-        stats, route = self.pointwise_stats(samples, route, chunk)
+        if not psis:
+            stats, route = self.pointwise_stats(samples, route, chunk)
+            self.pointwise_route = route
+            return self.pointwise_from_stats(stats)
+        from . import psis as _psis
+        x = self._draws(samples, 'GLMData.pointwise')
+        route = self._route(route, 'GLMData.pointwise')
+        n, S = self.A.shape[0], x.shape[0]
+        if S > _psis.MAX_DRAWS:
+            raise ValueError('GLMData.pointwise: psis=True takes at most %d draws at once, got %d: thin the run' % (_psis.MAX_DRAWS, S))
+        if route == 'fused':
+            import torch
+            from . import flow
+            if _lib.load().nnest_glm_psis_work_bytes(S, n) < 0:
+                raise ValueError('GLMData.pointwise: psis=True with %d draws of %d rows needs too large a work buffer: thin the run' % (S, n))
+            dev = torch.device('cuda', torch.cuda.current_device())
+            spec = {k: (torch.as_tensor(v).to(dev) if k in ('at', 'y', 'o') else v) for k, v in self.hip_like_glm.items()}
+            stats, rows = flow.glm_psis(spec, np.ascontiguousarray(x, dtype=np.float32), device=dev)
+            stats, rows = stats.cpu().numpy(), rows.cpu().numpy()
+        else:
+            stats, _ = self.pointwise_stats(x, 'host', chunk)
+            rows = np.empty((n, _psis.SLOTS))
+            step = max(1, int(self.POINTWISE_HOST_BYTES // (8 * max(S, 1))))
+            for first in range(0, n, step):   # (blocks of data rows: the [S, rows] block of terms is what is held)
+                rows[first:first + step] = _psis.psis_rows(self._row_terms(x, slice(first, first + step)))
         self.pointwise_route = route
-        return self.pointwise_from_stats(stats)
+        out = self.pointwise_from_stats(stats)
+        norm = -scipy.special.gammaln(self.y + 1.0) if self.family == 'poisson' else np.zeros_like(self.y)
+        out['elpd_psis'] = rows[:, _psis.ELPD] + norm
+        out['pareto_k'] = rows[:, _psis.KHAT].copy()
+        out['psis_ess'] = rows[:, _psis.ESS].copy()
+        out['psis_tail'] = rows[:, _psis.M].copy()
+        out['p_loo'] = out['lppd'] - out['elpd_psis']
+        return out
+
+    def log_lik(self, samples, route=None):
+        """The pointwise log-likelihood matrix [S, n] float64, l_is = log p(y_i | theta_s), normalised (the Poisson -lgamma(y_i + 1)
+        is added on the host), NaN for a dead pair: what other tools take for their own leave-one-out.  samples and route as
+        `pointwise` takes them; 'fused' is nnest_glm_terms (float32 data and draws, the terms `pointwise` reduces, at most 2^30
+        entries), 'host' float64 numpy.  The route taken is left in `log_lik_route`."""
+        x = self._draws(samples, 'GLMData.log_lik')
+        route = self._route(route, 'GLMData.log_lik')
+        if route == 'fused':
+            import torch
+            from . import flow
+            if x.shape[0] * self.A.shape[0] > 1 << 30:
+                raise ValueError('GLMData.log_lik: %d draws of %d rows are more than 2^30 entries: thin the run' % (x.shape[0], self.A.shape[0]))
+            dev = torch.device('cuda', torch.cuda.current_device())
+            spec = {k: (torch.as_tensor(v).to(dev) if k in ('at', 'y', 'o') else v) for k, v in self.hip_like_glm.items()}
+            l = flow.glm_terms(spec, np.ascontiguousarray(x, dtype=np.float32), device=dev).cpu().numpy()
+        else:
+            l = self._row_terms(x)
+        self.log_lik_route = route
+        if self.family == 'poisson':
+            l = l - scipy.special.gammaln(self.y + 1.0)
+        return l
 
     def pointwise_from_stats(self, stats):
         """`pointwise`'s dict from the statistics [n, 8]"""
