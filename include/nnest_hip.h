@@ -891,6 +891,41 @@ int nnest_spline_importance_evidence(struct nnest_spline *spl, const nnest_like_
                                      double *logw_out_dev, double *partials_dev, double *sums_dev, int M, uint64_t seed,
                                      uint64_t sample_offset, void *stream);
 int nnest_importance_fill_noise(float *z_dev, int M, int D, uint64_t seed, uint64_t sample_offset, void *stream);
+/* IMPORTANCE-SAMPLED EVIDENCE OF A REGRESSION: nnest_importance_evidence's estimate with the likelihood of a nnest_glm_t (logistic,
+ * Poisson) in place of the analytic ones and, optionally, the normal priors of a nnest_gauss_prior_t in place of the box
+ * (nnest_importance_glm.hip, nnest_spline_importance_glm.hip).  BUILD-DEFINED.  A sample is the importance sample above in every
+ * respect but the target: the draws (stream 7, m = sample_offset + k: z_out_dev is bit-equal to nnest_importance_fill_noise), the
+ * flow's inverse and T, the base, the weight logw = lp - logb, the sums, the partials (3 * nnest_importance_groups(M, tile) doubles,
+ * tile 4 / 16), the two-stage reduction without floating-point atomics and the determinism are those stated there.
+ *   logL:    the likelihood of nnest_mcmc_glm_steps on T(x), float64 terms from the float32 linear predictor in the layout's fixed
+ *            order, rows >= n masked, -1e100 where the sum is not finite;
+ *   prior:   prior NULL: 0 inside the box lo_dev / hi_dev on T(x) (NaN inside), -inf outside, or no box; prior given: log pi(T(x)) =
+ *            logc - 1/2 ss of nnest_mcmc_glm_prior_steps, float64 in the layout's fixed order, -inf where ss is not finite; no box;
+ *   lp:      (logL + ld) + prior, each operation rounded (nnest_mcmc_glm_prior_steps's target at beta = 1).
+ * (Without a box and without a prior the sums are those of the likelihood's integral over R^D, which is no evidence and is infinite
+ * for separable classes: a front end asks for a proper prior.)  Asynchronous on `stream`.  (All added within ABI 15.)
+ * nnest_importance_glm_evidence: the shapes of nnest_importance_evidence; one sample per wave, the wave's 64 lanes take 64 data rows
+ *   a pass; the prior's m and r in registers, loaded once a launch.
+ * nnest_spline_importance_glm_evidence: the same through the neural-spline flow on the team tile: the four waves share the row
+ *   blocks of the matrix-core product, rows >= M of the last tile evaluate their point and are neither counted nor written; the
+ *   prior's m and r are staged once per workgroup in LDS; one wave publishes.
+ * NNEST_E_ARG before any launch, the outputs untouched: everything nnest_importance_evidence refuses (M outside 0 .. 2^30; the
+ *   per-sample outputs not all four or all NULL; NULL partials_dev or sums_dev; t_std_dev / t_mean_dev or lo_dev / hi_dev not both or
+ *   neither), everything nnest_mcmc_glm_steps refuses of the descriptor, everything nnest_mcmc_glm_prior_steps refuses of the prior, a
+ *   prior together with a box.  M = 0 is valid: the sums are {-inf, 0, 0, 0}.  NNEST_E_UNSUPPORTED: what the _check says.
+ * nnest_importance_glm_check, nnest_spline_importance_glm_check: the verdict of nnest_importance_check /
+ *   nnest_spline_importance_check on the handle's shape and base, and D == x_dim (NNEST_E_ARG otherwise); nothing is launched. */
+int nnest_importance_glm_check(nnest_nvp_t *nvp, int D);
+int nnest_spline_importance_glm_check(struct nnest_spline *spl, int D);
+int nnest_importance_glm_evidence(nnest_nvp_t *nvp, const nnest_glm_t *glm, const nnest_gauss_prior_t *prior /* NULL: none */,
+                                  const float *t_std_dev, const float *t_mean_dev, const float *lo_dev, const float *hi_dev,
+                                  float *z_out_dev, float *x_out_dev, double *logl_out_dev, double *logw_out_dev, double *partials_dev,
+                                  double *sums_dev, int M, uint64_t seed, uint64_t sample_offset, void *stream);
+int nnest_spline_importance_glm_evidence(struct nnest_spline *spl, const nnest_glm_t *glm, const nnest_gauss_prior_t *prior /* NULL: none */,
+                                         const float *t_std_dev, const float *t_mean_dev, const float *lo_dev, const float *hi_dev,
+                                         float *z_out_dev, float *x_out_dev, double *logl_out_dev, double *logw_out_dev,
+                                         double *partials_dev, double *sums_dev, int M, uint64_t seed, uint64_t sample_offset,
+                                         void *stream);
 /* size of sync_dev in 8-byte words for a launch of `steps` steps */
 int nnest_mh_sync_words(int steps);
 /* number of adaptation groups nnest_mh_constrained_steps uses for C walkers (size of scale_out_dev) */

@@ -309,6 +309,10 @@ SIGNATURES = {
     'nnest_spline_importance_check': [_vp, _i],
     'nnest_importance_evidence': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u64, _u64, _vp],
     'nnest_spline_importance_evidence': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u64, _u64, _vp],
+    'nnest_importance_glm_check': [_vp, _i],
+    'nnest_spline_importance_glm_check': [_vp, _i],
+    'nnest_importance_glm_evidence': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u64, _u64, _vp],
+    'nnest_spline_importance_glm_evidence': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u64, _u64, _vp],
     'nnest_importance_fill_noise': [_vp, _i, _i, _u64, _u64, _vp],
     'nnest_host_prior_consume': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  ctypes.c_longlong, _d, ctypes.c_longlong, ctypes.c_longlong, _d, _d, _i],

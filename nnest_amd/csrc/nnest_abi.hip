@@ -17,6 +17,7 @@
 #include "glm_pointwise.h"
 #include "glm_psis.h"
 #include "gauss_prior.h"
+#include "importance_glm.h"
 
 using namespace nnest;
 
@@ -970,6 +971,41 @@ int nnest_importance_evidence(nnest_nvp_t *h, const nnest_like_t *like, const fl
     const hipStream_t st = (hipStream_t)stream;
     HIP_TRY(launch_importance_begin(sums_dev, st));
     HIP_TRY(launch_importance(h->s, h->w, a, st));
+    HIP_TRY(launch_importance_combine(partials_dev, sums_dev, a.groups, st));
+    return NNEST_OK;
+}
+
+// what nnest_importance_glm_evidence takes, asked before a launch (and by the entry itself): nnest_importance_check's verdict on the
+// shape and the base -- the kernel is that kernel's on another target --, and a descriptor of the flow's x_dim
+int nnest_importance_glm_check(nnest_nvp_t *h, int D) {
+    int rc;
+    if ((rc = nnest_importance_check(h, NNEST_LIKE_GAUSSIAN))) return rc;
+    if (D != h->s.D) return fail(NNEST_E_ARG, "importance glm: the likelihood's D=%d is not the flow's x_dim=%d", D, h->s.D);
+    return NNEST_OK;
+}
+
+// (as nnest_importance_evidence: the checks that need no handle come first)
+int nnest_importance_glm_evidence(nnest_nvp_t *h, const nnest_glm_t *glm, const nnest_gauss_prior_t *prior, const float *t_std_dev,
+                                  const float *t_mean_dev, const float *lo_dev, const float *hi_dev, float *z_out_dev, float *x_out_dev,
+                                  double *logl_out_dev, double *logw_out_dev, double *partials_dev, double *sums_dev, int M, uint64_t seed,
+                                  uint64_t sample_offset, void *stream) {
+    ImpGlmArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc = importance_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_out_dev, x_out_dev, logl_out_dev, logw_out_dev, partials_dev,
+                             sums_dev, M, seed, sample_offset);
+    if (rc) return rc;
+    if ((rc = glm_ok(glm, glm ? glm->D : 0, &a.gl))) return rc;
+    if (prior) {
+        if ((rc = gauss_prior_ok(prior, h ? h->s.D : prior->D, &a.pr))) return rc;   // (no handle: refused below)
+        if (lo_dev) return fail(NNEST_E_ARG, "importance glm: a prior together with the box lo_dev / hi_dev (one or the other)");
+        a.prior = 1;
+    }
+    if ((rc = nnest_importance_glm_check(h, a.gl.D))) return rc;
+    a.like.scale = 1.0f;
+    a.groups = importance_groups(M, IMP_NVP_TILE, h->num_cu);
+    const hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(launch_importance_begin(sums_dev, st));
+    HIP_TRY(launch_importance_glm(h->s, h->w, a, st));
     HIP_TRY(launch_importance_combine(partials_dev, sums_dev, a.groups, st));
     return NNEST_OK;
 }

@@ -22,6 +22,7 @@
 #include "mcmc_gdata.h"
 #include "glm_data.h"
 #include "gauss_prior.h"
+#include "importance_glm.h"
 #include "nnest_internal.h"
 #include "mh_common.h"
 
@@ -758,6 +759,50 @@ int nnest_spline_importance_evidence(nnest_spline_t *h, const nnest_like_t *like
     SHIP_TRY(launch_importance_begin(sums_dev, st));
     hipError_t e = launch_spline_importance(SplArgs{h->img, h->s}, a, st);
     if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_importance: %s", hipGetErrorString(e));
+    SHIP_TRY(launch_importance_combine(partials_dev, sums_dev, a.groups, st));
+    return NNEST_OK;
+}
+
+// what nnest_spline_importance_glm_evidence takes, asked before a launch (and by the entry itself): nnest_spline_importance_check's
+// verdict on the base and the team tile's shapes -- the kernel is that kernel's on another target --, and a descriptor of the
+// flow's x_dim
+int nnest_spline_importance_glm_check(nnest_spline_t *h, int D) {
+    int rc;
+    if ((rc = nnest_spline_importance_check(h, NNEST_LIKE_GAUSSIAN))) return rc;
+    ImpGlmArgs probe;
+    memset(&probe, 0, sizeof(probe));   // (M = 0: the shape's verdict, nothing is launched)
+    if (launch_spline_importance_glm(SplArgs{h->img, h->s}, probe, nullptr) == hipErrorInvalidConfiguration)
+        return spline_fail(NNEST_E_UNSUPPORTED, "spline importance glm: x_dim=%d hidden_dim=%d not instantiated (the team tile's shapes)",
+                           h->s.D, h->s.H);
+    if (D != h->s.D) return spline_fail(NNEST_E_ARG, "importance glm: the likelihood's D=%d is not the flow's x_dim=%d", D, h->s.D);
+    return NNEST_OK;
+}
+
+// the importance-sampled evidence of a regression through the spline flow (nnest_spline_importance_glm.hip); the argument checks of
+// nnest_importance_glm_evidence
+int nnest_spline_importance_glm_evidence(nnest_spline_t *h, const nnest_glm_t *glm, const nnest_gauss_prior_t *prior,
+                                         const float *t_std_dev, const float *t_mean_dev, const float *lo_dev, const float *hi_dev,
+                                         float *z_out_dev, float *x_out_dev, double *logl_out_dev, double *logw_out_dev,
+                                         double *partials_dev, double *sums_dev, int M, uint64_t seed, uint64_t sample_offset,
+                                         void *stream) {
+    ImpGlmArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc = importance_args(&a, t_std_dev, t_mean_dev, lo_dev, hi_dev, z_out_dev, x_out_dev, logl_out_dev, logw_out_dev, partials_dev,
+                             sums_dev, M, seed, sample_offset);
+    if (rc) return rc;
+    if ((rc = glm_ok(glm, glm ? glm->D : 0, &a.gl))) return rc;
+    if (prior) {
+        if ((rc = gauss_prior_ok(prior, h ? h->s.D : prior->D, &a.pr))) return rc;   // (no handle: refused below)
+        if (lo_dev) return spline_fail(NNEST_E_ARG, "importance glm: a prior together with the box lo_dev / hi_dev (one or the other)");
+        a.prior = 1;
+    }
+    if ((rc = nnest_spline_importance_glm_check(h, a.gl.D))) return rc;
+    a.like.scale = 1.0f;
+    a.groups = importance_groups(M, IMP_SPLINE_TILE, h->num_cu);
+    const hipStream_t st = (hipStream_t)stream;
+    SHIP_TRY(launch_importance_begin(sums_dev, st));
+    hipError_t e = launch_spline_importance_glm(SplArgs{h->img, h->s}, a, st);
+    if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_importance_glm: %s", hipGetErrorString(e));
     SHIP_TRY(launch_importance_combine(partials_dev, sums_dev, a.groups, st));
     return NNEST_OK;
 }

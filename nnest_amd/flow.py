@@ -616,19 +616,48 @@ class _HipFlow(object):
         msg = self._lib.nnest_hip_last_error()
         return msg.decode() if msg else 'error %d' % rc
 
+    def importance_glm_refusal(self, D=None):
+        """why `importance_evidence` with a like_glm of dimension D (None: the flow's own) would refuse this flow (its shape, its
+        base) -- the library's own words (the family's `importance_glm_check` entry; nothing is launched) --, or None where it is
+        taken.  NotImplementedError for a family without such a kernel"""
+        fn = self._sym.get('importance_glm_check')
+        if fn is None or 'importance_glm' not in self._sym:
+            raise NotImplementedError('no fused importance-sampling kernel for %s on a regression likelihood of user data' % type(self).__name__)
+        with torch.cuda.device(self.device):
+            rc = fn(self._h, self.D if D is None else int(D))
+        if rc == _lib.NNEST_OK:
+            return None
+        msg = self._lib.nnest_hip_last_error()
+        return msg.decode() if msg else 'error %d' % rc
+
     def importance_evidence(self, like_id, M, t_std=None, t_mean=None, lo=None, hi=None, seed=0, sample_offset=0, like_params=None,
-                            want_samples=False):
+                            want_samples=False, like_glm=None, prior_gauss=None):
         """the sums of the importance-sampled evidence with this flow as the proposal, M samples drawn, evaluated and reduced in ONE
         launch (the family's `importance` entry point: nnest_importance_evidence, nnest_spline_importance_evidence; build-defined:
         include/nnest_hip.h has the definition).  The likelihood `like_id` sees T(x) = x * t_std + t_mean (per dimension; None:
         identity); lo / hi [D]: the prior box on T(x) (None: no prior); sample_offset: the global index of sample 0 -- a sample
         depends on (seed, global index) only, so a run cut into launches is the same run.  Returns a dict: sums [4] float64 on the
         device ({a, S1, S2, n_live}: _lib.merge_importance / importance_result read them) and, with want_samples, z, x [M, D]
-        float32 (x before T), logl, logw [M] float64.  Asynchronous on the current stream.  NotImplementedError for a family
-        without such a kernel (its handle must not reach another family's)."""
-        fn = self._sym.get('importance')
+        float32 (x before T), logl, logw [M] float64.  Asynchronous on the current stream.
+        like_glm: None -- the entry above, as it was; the descriptor of a regression likelihood of user data
+        (likelihoods.GLMData.hip_like_glm, as `mcmc_steps` takes it) -- `like_id` must then be None, and the launch goes through the
+        family's `importance_glm` entry (nnest_importance_glm_evidence, nnest_spline_importance_glm_evidence), with the same keys.
+        prior_gauss: None, or the descriptor of independent normal priors on T(x) (priors.GaussianPrior.hip_gauss_prior) -- only
+        with a like_glm and without lo / hi (ValueError otherwise): lp = (logL + log|det|) + log pi.
+        NotImplementedError for a family without such a kernel (its handle must not reach another family's)."""
+        glm = like_glm is not None
+        gprior = prior_gauss is not None
+        if glm and like_id is not None:
+            raise ValueError('importance_evidence: like_glm goes with like_id=None, got like_id=%r' % (like_id,))
+        if gprior and not glm:
+            raise ValueError('importance_evidence: prior_gauss goes only with a like_glm (a GaussianPrior beside a regression likelihood of '
+                             'user data)')
+        if gprior and (lo is not None or hi is not None):
+            raise ValueError('importance_evidence: prior_gauss goes without lo / hi (the prior is the normal one or the box, not both)')
+        fn = self._sym.get('importance_glm' if glm else 'importance')
         if fn is None:
-            raise NotImplementedError('no fused importance-sampling kernel for %s' % type(self).__name__)
+            raise NotImplementedError('no fused importance-sampling kernel for %s%s' % (
+                type(self).__name__, ' on a regression likelihood of user data' if glm else ''))
         dev = self.device
         M, D = int(M), self.D
         if M < 0:
@@ -644,9 +673,14 @@ class _HipFlow(object):
             if groups < 0:
                 raise _lib.NnestHipError('nnest_importance_groups(%d, %d) failed' % (M, self._IMPORTANCE_TILE))
             partials = torch.empty(3 * max(groups, 1), **f64)
-            lk = _lib.like_spec(like_id, 1.0, like_params)
+            if glm:
+                lk, keep = glm_spec(like_glm, dev)   # (`keep`: the staged arrays, alive until the call has been enqueued)
+                pspec, pkeep = gauss_prior_spec(prior_gauss, dev) if gprior else (None, None)
+            else:
+                lk = _lib.like_spec(like_id, 1.0, like_params)
             _lib.check(fn(
-                self._h, ctypes.byref(lk), _lib.ptr(t_std), _lib.ptr(t_mean), _lib.ptr(lo_t), _lib.ptr(hi_t), _lib.ptr(out.get('z')),
+                self._h, ctypes.byref(lk), *(((ctypes.byref(pspec) if gprior else None),) if glm else ()), _lib.ptr(t_std),
+                _lib.ptr(t_mean), _lib.ptr(lo_t), _lib.ptr(hi_t), _lib.ptr(out.get('z')),
                 _lib.ptr(out.get('x')), _lib.ptr(out.get('logl')), _lib.ptr(out.get('logw')), _lib.ptr(partials), _lib.ptr(out['sums']), M,
                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset) & 0xFFFFFFFFFFFFFFFF, _lib.current_stream(dev)))
         out['groups'] = groups
@@ -896,7 +930,8 @@ class HipNVP(_PaddedVectors, _HipFlow):
                    mcmc_adapt_check='nnest_mcmc_adapt_check', mcmc_gdata='nnest_mcmc_gdata_steps',
                    mcmc_gdata_check='nnest_mcmc_gdata_check', mcmc_glm='nnest_mcmc_glm_steps',
                    mcmc_glm_check='nnest_mcmc_glm_check', mcmc_glm_prior='nnest_mcmc_glm_prior_steps',
-                   mcmc_glm_prior_check='nnest_mcmc_glm_prior_check')
+                   mcmc_glm_prior_check='nnest_mcmc_glm_prior_check', importance_glm='nnest_importance_glm_evidence',
+                   importance_glm_check='nnest_importance_glm_check')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (_PaddedVectors)
         with torch.cuda.device(self.device):

@@ -808,7 +808,12 @@ class Sampler(object):
         `_probe_agrees_glm`.  Beside such a likelihood, and only there, a priors.GaussianPrior on T(x) whose `__call__` is its own
         is taken where the flow binds `mcmc_glm_prior` and takes the shape (`mcmc_glm_prior_refusal`) and the prior's
         `hip_gauss_prior` agrees with its callable (`_probe_agrees_gauss_prior`): the target then carries `prior_gauss` and no box.
-        With any other likelihood, entry or flow a GaussianPrior stays a Python prior: refused here, the host route's"""
+        With any other likelihood, entry or flow a GaussianPrior stays a Python prior: refused here, the host route's.
+        For entry 'importance' a `hip_like_glm` is taken where the flow binds `importance_glm` and takes the shape and base
+        (`importance_glm_refusal`), the descriptor agrees with the host callable and there is a PROPER prior: a UniformPrior on T(x)
+        whose rule is its own or the unit box on x (the box), or a GaussianPrior on T(x) whose `__call__` is its own (`prior_gauss`
+        through the same entry, no box).  A GLMData with NO prior is not taken, in the words a Python callable gets: the integral of
+        a regression likelihood over R^D is not an evidence, and is infinite for separable classes"""
         affine = self._ensemble_affine() if affine is None else affine
         netG = self.trainer.netG
         if self.num_derived != 0:
@@ -824,17 +829,23 @@ class Sampler(object):
         if like_data is not None and not (entry in self.GDATA_ENTRIES and 'mcmc_gdata' in getattr(netG, '_sym', ())):
             like_data = None
         like_glm = getattr(like, 'hip_like_glm', None) if like_id is None and like_data is None else None
-        if like_glm is not None and not (entry in self.GDATA_ENTRIES and 'mcmc_glm' in getattr(netG, '_sym', ())):
+        prior = self._user_prior
+        gauss_own = self._transform_prior and isinstance(prior, GaussianPrior) and type(prior).__call__ is GaussianPrior.__call__
+        glm_evidence = False   # (the evidence of a regression: the flow's `importance_glm` entry, and a PROPER prior)
+        if like_glm is not None and entry == 'importance':
+            proper = (gauss_own or (unit_box_on_x and self._unit_box_on_x() and self._linear_scale is not None)
+                      or (self._transform_prior and isinstance(prior, UniformPrior) and type(prior).__call__ is UniformPrior.__call__))
+            glm_evidence = proper and 'importance_glm' in getattr(netG, '_sym', ())
+        if like_glm is not None and not glm_evidence and not (entry in self.GDATA_ENTRIES and 'mcmc_glm' in getattr(netG, '_sym', ())):
             like_glm = None
         if like_id is None and like_data is None and like_glm is None:
             return None, 'a likelihood the kernels do not know (a Python callable)'
-        prior = self._user_prior
         prior_gauss = None   # (normal priors: beside a regression likelihood of user data only)
-        if (like_glm is not None and self._transform_prior and isinstance(prior, GaussianPrior)
-                and type(prior).__call__ is GaussianPrior.__call__ and 'mcmc_glm_prior' in getattr(netG, '_sym', ())):
+        if like_glm is not None and gauss_own and (glm_evidence or 'mcmc_glm_prior' in getattr(netG, '_sym', ())):
             prior_gauss = prior.hip_gauss_prior
         if like_glm is not None:   # (as below for like_data: one kernel per flow and family serves the four entries)
-            why = (netG.mcmc_glm_refusal if prior_gauss is None else netG.mcmc_glm_prior_refusal)(np.shape(like_glm['at'])[0])
+            ask = netG.importance_glm_refusal if glm_evidence else netG.mcmc_glm_refusal if prior_gauss is None else netG.mcmc_glm_prior_refusal
+            why = ask(np.shape(like_glm['at'])[0])
             if why is not None:
                 return None, 'the flow %s: %s' % (type(netG).__name__, why)
             entry = None
@@ -920,7 +931,10 @@ class Sampler(object):
         Z = E_q[L(T(x)) pi(T(x)) / q(x)] over `num_samples` exact draws of the flow -- an estimate that does not depend on how well
         any chain has mixed, with an error bar and an effective sample size.  For every front end, once a flow has been trained.
         route: 'fused' -- drawn, evaluated and reduced inside the kernel (include/nnest_hip.h nnest_importance_evidence,
-        nnest_spline_importance_evidence), in launches of `chunk` samples addressed by their global index (the cut does not change
+        nnest_spline_importance_evidence; for a likelihoods.GLMData under a proper prior -- a UniformPrior, the unit box or a
+        priors.GaussianPrior -- nnest_importance_glm_evidence, nnest_spline_importance_glm_evidence; a GLMData with no prior is
+        not taken: the integral of a regression likelihood over R^D is not an evidence, and is infinite for separable classes),
+        in launches of `chunk` samples addressed by their global index (the cut does not change
         a sample; chunk defaults to 2^22, or by ENSEMBLE_HISTORY_BYTES when samples come back); taken where `_device_target`
         gives a target (a likelihood the kernels know, no derived or slow parameters, an affine transform, no prior or a
         UniformPrior on T(x), HipNVP in the default shape or HipSpline) or the prior is the NestedSampler's unit box on x, and the

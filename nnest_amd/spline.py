@@ -41,7 +41,8 @@ class HipSpline(_PaddedVectors, _HipFlow):
                    mcmc_adapt='nnest_spline_mcmc_adapt_steps', mcmc_adapt_check='nnest_spline_mcmc_adapt_check',
                    mcmc_gdata='nnest_spline_mcmc_gdata_steps', mcmc_gdata_check='nnest_spline_mcmc_gdata_check',
                    mcmc_glm='nnest_spline_mcmc_glm_steps', mcmc_glm_check='nnest_spline_mcmc_glm_check',
-                   mcmc_glm_prior='nnest_spline_mcmc_glm_prior_steps', mcmc_glm_prior_check='nnest_spline_mcmc_glm_prior_check')
+                   mcmc_glm_prior='nnest_spline_mcmc_glm_prior_steps', mcmc_glm_prior_check='nnest_spline_mcmc_glm_prior_check',
+                   importance_glm='nnest_spline_importance_glm_evidence', importance_glm_check='nnest_spline_importance_glm_check')
         self._h = ctypes.c_void_p()
         self._Hn = native_hidden(self.H)     # the native handle's hidden width (flow._PaddedVectors: zero-padded, exact)
         with torch.cuda.device(self.device):
