@@ -847,6 +847,44 @@ int nnest_glm_psis_tail_cap(int S);
 long long nnest_glm_psis_work_bytes(int S, int n);
 int nnest_glm_psis(const nnest_glm_t *glm, const float *t_dev, const double *stats_dev, double *out_dev, void *work_dev, int S, int D,
                    void *stream);
+/* GRADIENT, CURVATURE AND NEWTON STEP of the same likelihoods at ONE theta: what a posterior mode, the Laplace approximation and the
+ * Laplace evidence are made of (nnest_glm_newton.hip, glm_newton.h).  BUILD-DEFINED: the reference has none.  (All
+ * added within ABI 15.)  Everything is float64; the float32 descriptor is read as it is and converted exactly.
+ * nnest_glm_curv, at theta_dev [D] float64, writes out_dev [1 + D + D D] float64:
+ *     eta_i = o_i + sum_c A[i, c] * theta_c    float64; fused multiply-adds, in the kernel's own fixed order
+ *     l_i                                      the family's term as written above, from the double eta_i (NaN where it is not finite)
+ *     NNEST_GLM_LOGISTIC: mu_i = 1 / (1 + exp(-eta_i)), w_i = mu_i (1 - mu_i), both from exp(-|eta_i|): no overflow at either end
+ *     NNEST_GLM_POISSON:  mu_i = w_i = exp(eta_i)
+ *     out[0]               = logl0 + sum_{i < n} l_i              -1e100 where that is not finite
+ *     out[1 + c]           = sum_i (y_i - mu_i) A[i, c]           the gradient of log L
+ *     out[1 + D + c D + d] = sum_i w_i A[i, c] A[i, d]            the NEGATIVE Hessian of log L: a full matrix, the lower triangle a
+ *                                                                 bit copy of the upper
+ *   A non-finite theta_c or a non-finite sum leaves out[0] = -1e100; the gradient and the matrix then hold whatever they hold: read
+ *   out[0] first.  Rows n .. ld - 1 of the descriptor's arrays are masked, whatever they hold.  The rows are dealt in blocks of 64 to
+ *   G = nnest_glm_curv_groups(n, D) workgroups, which write their sums into partials_dev ([G][1 + D + D (D + 1) / 2] doubles), and a
+ *   second kernel adds the G partials of each entry in index order: no floating-point atomics, the same call twice returns the same
+ *   bits, and G depends on (n, D) alone, not on the device.  The matrix is accumulated on the float64 matrix cores.
+ * nnest_glm_curv_groups: G for n rows and D columns; -1 for n outside 1 .. 65536 or D outside 1 .. 128.
+ * nnest_glm_newton_solve, in one workgroup, from curv_dev (nnest_glm_curv's out) and theta_dev [D]: with the prior's m, r =
+ *   float32(1 / sigma) and logc converted to double (prior NULL: no prior, log pi = 0),
+ *     g_c = out[1 + c] - (theta_c - m_c) r_c^2,   H = the matrix + diag(r_c^2),   log pi = logc - 1/2 sum_c ((theta_c - m_c) r_c)^2
+ *     H = L L^T (float64 Cholesky, a fixed order),   H delta = g by the two triangular solves
+ *   step_dev [D] = delta; chol_dev [D D] = L, row-major, the part above the diagonal zero; info_dev [4] =
+ *     {log L + log pi,  the Newton decrement lambda^2 = g^T delta,  log det H = 2 sum_c log L_cc,  status}
+ *   status 0: ok; 1: a pivot was <= 0 or not finite (H is not positive definite: the data do not determine theta) -- pivot j counts
+ *   as <= 0 when it is not above (j + 2) 2^-52 H_jj, the bound on its own rounding error, so that an exactly singular H is refused
+ *   whichever way its last pivots round --; 2: curv_dev[0]
+ *   was the safe value -1e100, or log pi is not finite.  For a status other than 0 step_dev and chol_dev are zeros (never NaN) and
+ *   info[1] = info[2] = 0.
+ * Both are asynchronous on `stream`.  NNEST_E_ARG before any launch, the outputs untouched: everything nnest_loglike_glm refuses, a
+ *   D that is not the descriptor's (the solve: D outside 1 .. 128), a NULL pointer (but prior), a prior descriptor that
+ *   nnest_logprior_gauss refuses. */
+int nnest_glm_curv_groups(int n, int D);
+int nnest_glm_curv(const nnest_glm_t *glm, const double *theta_dev /*[D]*/, double *out_dev /*[1 + D + D*D]*/,
+                   double *partials_dev /*[G][1 + D + D(D+1)/2]*/, int D, void *stream);
+int nnest_glm_newton_solve(const double *curv_dev /* nnest_glm_curv's out */, const nnest_gauss_prior_t *prior /* NULL: none */,
+                           const double *theta_dev, double *step_dev /*[D]*/, double *chol_dev /*[D*D]*/, double *info_dev /*[4]*/, int D,
+                           void *stream);
 /* IMPORTANCE-SAMPLED EVIDENCE with the trained flow as the proposal: Z = E_q[L(T(x)) pi(T(x)) / q(x)], drawn, evaluated and reduced
  * inside one kernel.  BUILD-DEFINED: the reference has no such estimator.  Sample m is a global 64-bit index; row k of a launch of M
  * samples is m = sample_offset + k:

@@ -16,4 +16,7 @@ def __getattr__(name):   # the reference's package-level names (nnest/__init__.p
     if name == 'SMCSampler':   # (build-defined: the reference has none)
         from .smc import SMCSampler
         return SMCSampler
+    if name == 'LaplaceFit':   # (build-defined: what likelihoods.GLMData.laplace returns)
+        from .laplace import LaplaceFit
+        return LaplaceFit
     raise AttributeError(name)

@@ -291,6 +291,11 @@ SIGNATURES = {
     'nnest_glm_psis_tail_cap': [_i],
     'nnest_glm_psis_work_bytes': [_i, _i],
     'nnest_glm_psis': [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    # gradient and curvature at one theta: (n, D); (glm, theta_dev, out_dev, partials_dev, D, stream); the Newton step:
+    # (curv_dev, prior or NULL, theta_dev, step_dev, chol_dev, info_dev, D, stream)
+    'nnest_glm_curv_groups': [_i, _i],
+    'nnest_glm_curv': [_vp, _vp, _vp, _vp, _i, _vp],
+    'nnest_glm_newton_solve': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     # normal priors beside them: the glm entries' arguments with `const nnest_gauss_prior_t *prior` after `glm`;
     # (prior, t_dev, logp_dev, N, D, stream); (handle, D)
     'nnest_mcmc_glm_prior_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64,

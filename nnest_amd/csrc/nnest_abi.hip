@@ -18,6 +18,7 @@
 #include "glm_psis.h"
 #include "gauss_prior.h"
 #include "importance_glm.h"
+#include "glm_newton.h"
 
 using namespace nnest;
 
@@ -898,6 +899,39 @@ int nnest_logprior_gauss(const nnest_gauss_prior_t *prior, const float *t_dev, d
     if (N > 0 && (!t_dev || !logp_dev)) return fail(NNEST_E_ARG, "NULL device buffer");
     hipError_t e = launch_logprior_gauss(p, t_dev, logp_dev, N, (hipStream_t)stream);
     if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_logprior_gauss: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+// the gradient and curvature of the regression likelihoods at one theta, and the Newton step under the normal priors
+// (nnest_glm_newton.hip, glm_newton.h)
+int nnest_glm_curv_groups(int n, int D) {
+    if (n < 1 || n > GLM_MAX_ROWS || D < 1 || D > 128) return -1;
+    return glm_curv_groups(n, D);
+}
+
+int nnest_glm_curv(const nnest_glm_t *glm, const double *theta_dev, double *out_dev, double *partials_dev, int D, void *stream) {
+    GlmSpec gl;
+    int rc;
+    if ((rc = glm_ok(glm, D, &gl))) return rc;
+    if (!theta_dev || !out_dev || !partials_dev)
+        return fail(NNEST_E_ARG, "glm curv: NULL theta_dev=%p, out_dev=%p or partials_dev=%p", (const void *)theta_dev, (void *)out_dev,
+                    (void *)partials_dev);
+    hipError_t e = launch_glm_curv(gl, theta_dev, out_dev, partials_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_glm_curv: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+int nnest_glm_newton_solve(const double *curv_dev, const nnest_gauss_prior_t *prior, const double *theta_dev, double *step_dev,
+                           double *chol_dev, double *info_dev, int D, void *stream) {
+    if (D < 1 || D > 128) return fail(NNEST_E_ARG, "glm newton solve: D=%d (1 .. 128)", D);
+    GaussPriorSpec p;
+    int rc;
+    if (prior && (rc = gauss_prior_ok(prior, D, &p, "D"))) return rc;
+    if (!curv_dev || !theta_dev || !step_dev || !chol_dev || !info_dev)
+        return fail(NNEST_E_ARG, "glm newton solve: NULL curv_dev=%p, theta_dev=%p, step_dev=%p, chol_dev=%p or info_dev=%p", (const void *)curv_dev,
+                    (const void *)theta_dev, (void *)step_dev, (void *)chol_dev, (void *)info_dev);
+    hipError_t e = launch_glm_newton_solve(curv_dev, prior ? &p : nullptr, theta_dev, step_dev, chol_dev, info_dev, D, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_glm_newton_solve: %s", hipGetErrorString(e));
     return NNEST_OK;
 }
 

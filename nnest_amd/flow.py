@@ -1343,6 +1343,54 @@ def logprior_gauss(data, t, device=None):
     return out
 
 
+def _as_dev_f64(x, device):
+    """a flat contiguous float64 tensor on `device` (a float64 tensor already there is used as it is)"""
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64)))
+    return x.to(device=device, dtype=torch.float64).reshape(-1).contiguous()
+
+
+def glm_curvature(data, theta, device=None):
+    """the log-likelihood, its gradient and its negative Hessian at ONE theta for a regression likelihood of user data
+    (nnest_glm_curv; include/nnest_hip.h has the arithmetic): data as `glm_spec` takes it, theta [D] (float64 on the device, or
+    anything convertible).  Returns [1 + D + D D] float64 on the device: {logL (-1e100 where not finite), the gradient [D], the
+    negative Hessian [D, D] row-major, bit-symmetric}.  Deterministic: the same call twice returns the same bits.  Asynchronous on
+    the current stream."""
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    theta = _as_dev_f64(theta, dev)
+    D = int(theta.shape[0])
+    with torch.cuda.device(dev):
+        spec, keep = glm_spec(data, dev)
+        G = max(_lib.load().nnest_glm_curv_groups(max(int(spec.n), 1), max(D, 1)), 1)   # (-1: a shape the entry refuses first)
+        out = torch.empty(1 + D + D * D, dtype=torch.float64, device=dev)
+        partials = torch.empty(G * (1 + D + D * (D + 1) // 2), dtype=torch.float64, device=dev)
+        _lib.check(_lib.load().nnest_glm_curv(ctypes.byref(spec), _lib.ptr(theta), _lib.ptr(out), _lib.ptr(partials), D,
+                                              _lib.current_stream(dev)))
+    return out
+
+
+def glm_newton_solve(curv, theta, prior=None, device=None):
+    """the Newton step of a regression posterior from `glm_curvature`'s result at theta (nnest_glm_newton_solve; include/nnest_hip.h
+    has the arithmetic): prior None or as `gauss_prior_spec` takes it (the mapping priors.GaussianPrior.hip_gauss_prior holds).
+    Returns (step [D], chol [D, D] the lower Cholesky factor of the negative Hessian of the log posterior, info [4] = {log L + log
+    pi, the Newton decrement g^T step, log det, status}) float64 on the device; status 1: not positive definite, 2: a non-finite
+    log L or log pi -- step and chol are zeros then.  Asynchronous on the current stream."""
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    theta = _as_dev_f64(theta, dev)
+    curv = _as_dev_f64(curv, dev)
+    D = int(theta.shape[0])
+    if curv.shape[0] != 1 + D + D * D:
+        raise ValueError('glm_newton_solve: curv must hold 1 + D + D D = %d values for theta [%d], got %d' % (1 + D + D * D, D, curv.shape[0]))
+    with torch.cuda.device(dev):
+        pspec, keep = gauss_prior_spec(prior, dev) if prior is not None else (None, None)
+        step = torch.empty(D, dtype=torch.float64, device=dev)
+        chol = torch.empty(D, D, dtype=torch.float64, device=dev)
+        info = torch.empty(4, dtype=torch.float64, device=dev)
+        _lib.check(_lib.load().nnest_glm_newton_solve(_lib.ptr(curv), ctypes.byref(pspec) if pspec is not None else None, _lib.ptr(theta),
+                                                      _lib.ptr(step), _lib.ptr(chol), _lib.ptr(info), D, _lib.current_stream(dev)))
+    return step, chol, info
+
+
 SMC_MAX_PARTICLES = 1 << 20   # the population nnest_smc_reweight and nnest_smc_resample take (one workgroup each)
 
 

@@ -567,3 +567,28 @@ class GLMData(Likelihood):
         self.predict_route = route
         return dict(mean=np.where(cnt > 0, mean, np.nan), sd=sd, n_live=cnt)
 
+    # ---- the posterior mode and the Laplace approximation (build-defined: the reference has none; include/nnest_hip.h nnest_glm_curv) ----
+    def laplace(self, prior=None, theta0=None, tol=1e-12, max_iter=100, route=None):
+        """The posterior mode, the curvature there and the Laplace approximation built on them, by damped Newton (build-defined:
+        the reference has none).  prior: None or a priors.GaussianPrior (ValueError for anything else: a box has no curvature, and
+        truncation is not modelled).  Returns a laplace.LaplaceFit: mode, precision (the negative Hessian H of the log posterior at
+        the mode), cov, chol, logl, logprior, logdet, logz (the Laplace evidence logl + logprior + (D / 2) log 2 pi - logdet / 2;
+        None without a prior), decrement, iterations, halvings, converged, route, and `sample` / `as_gaussian` -- what
+        MCMCSampler.run takes as training_samples= and init_samples=, and the approximation as a GaussianData.
+        The iteration: start at theta0, else at the prior's mean, else at 0; evaluate log L, its gradient g and H at theta (with
+        the prior's terms) and the Newton step delta = H^-1 g; stop with converged=True when the Newton decrement lambda^2 = g^T
+        delta AT THE CURRENT theta is <= tol, returning that theta; otherwise try alpha = 1, 1/2, 1/4, ... (at most 40 halvings) and
+        accept the first alpha whose log posterior is finite and >= log post(theta) + 1e-4 alpha lambda^2.  After max_iter
+        iterations, or a failed line search, the result has converged=False and a warning is issued.
+        ValueError where H is not positive definite at an evaluated point: the data do not determine theta (n < x_dim, collinear
+        columns), and a GaussianPrior is the remedy.
+        FOR SEPARABLE CLASSES WITHOUT A PRIOR NO MODE EXISTS (logistic family: some direction splits the y = 1 rows from the y = 0
+        rows): the likelihood keeps rising along that direction, the iterates walk off to infinity, and the decrement falls slowly
+        below any tol on the way -- this cannot be told from convergence, so the result then says converged=True at a theta that
+        means nothing.  A proper prior is the cure.
+        route: 'fused' -- every evaluation is one nnest_glm_curv (the reduction over the data rows on the float64 matrix cores)
+        and one nnest_glm_newton_solve on the device, float64 from the float32 data, the host reading four doubles per trial;
+        'host' -- the same definition in float64 numpy from the same float32 data, no GPU needed; None -- 'fused' where a device is
+        available.  The two routes differ by rounding only."""
+        from . import laplace as _laplace
+        return _laplace.fit(self, prior=prior, theta0=theta0, tol=tol, max_iter=max_iter, route=route)
