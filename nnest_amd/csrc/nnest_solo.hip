@@ -52,6 +52,42 @@ namespace nnest {
 #define PSTAMP(v) do { } while (0)
 #define PSTAMP_DRAINED(v) do { } while (0)
 #endif
+// NNEST_STAMP + NNEST_STAMP_VOTE (VOTE=1 tools/build_stamp.sh, tools/stamp_solo_vote.py): the chain of an exact step's vote, segment
+// by segment, on tile 0's relay wave and its first net wave
+#if defined(NNEST_STAMP) && defined(NNEST_STAMP_VOTE)
+#define VSTAMP(v) do { __builtin_amdgcn_sched_barrier(0); v = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
+#undef NNEST_STAMP_VOTE
+#define VSTAMP(v) do { } while (0)
+#endif
+#ifdef NNEST_STAMP_VOTE
+// mh_sync_total(sync, it, nwg, 0, err) with stamps around every read: when the first read went out, when the read that saw every
+// arrival went out and came back, how many reads it took and how many arrivals the first one saw
+struct SoloVoteStamps { unsigned long long t_first, t_issue, t_ret; int reads, first_seen; };
+static __device__ __forceinline__ int solo_vote_total_stamped(const unsigned long long *sync, int it, int nwg, int *err, SoloVoteStamps &vs) {
+    unsigned long long s = 0, t = 0;
+    bool first = true, done = false;
+    int polls = 0;
+    while (!done) {
+        if ((polls & 255) == 0 && mh_sync_failed(err)) break;
+        if (++polls > MH_SYNC_MAX_POLLS) {
+            mh_sync_fail(err);
+            break;
+        }
+        __builtin_amdgcn_s_sleep(2);
+        unsigned long long t0;
+        VSTAMP(t0);
+        s = mh_sync_read(sync, it);
+        asm volatile("" : "+v"(s));   // (the value has arrived)
+        VSTAMP(t);
+        vs.reads += 1;
+        if (first) { vs.t_first = t0; vs.first_seen += (int)(s >> 32); first = false; }
+        if ((int)(s >> 32) == nwg) { vs.t_issue = t0; vs.t_ret = t; done = true; }
+    }
+    if (!done) { vs.t_issue = vs.t_ret = t; }
+    return (int)(s & 0xffffffffull);
+}
+#endif
 
 static constexpr int SOLO_ETAB = 1024;   // steps + 2 <= SOLO_ETAB: exp(1 / (1 + k)) from a table
 // The table is a constant of the kernel: filled once per process and device -- ON the device, with the expression the relay wave
@@ -376,6 +412,10 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         }
         unsigned long long qa = 0, qb = 0;
         const int k0 = solo_relay_first_iteration(warm);
+#ifdef NNEST_STAMP_VOTE
+        unsigned long long v_a = 0, v_post = 0, v_p = 0, v_vote = 0, v_rule = 0, v_br = 0, v_b = 0, v_bprev = 0, va[10] = {0};
+        SoloVoteStamps vs = {0, 0, 0, 0, 0};
+#endif
         if (warm > 0) {
             // Warm-up: behind the net waves' step k (barrier A) post that step's accepts and wait for the batch's vote while the
             // net waves evaluate step k + 1 for BOTH scales it can lead to (fs_cand, written one vote ahead); at barrier B name
@@ -387,16 +427,33 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
                 if (acc < rej) sc /= E(rej);
                 return sc;
             };
+            auto next_scale_tab = [&](int acc, int rej, double sc) {   // ... where the table reaches (use_tab)
+                if (acc > rej) sc *= etab[acc];
+                if (acc < rej) sc /= etab[rej];
+                return sc;
+            };
+            // The vote's chain (round 11; profiles/r11/k4_vote_stamps.txt).  An exact step lasts as long as the batch's vote takes -- B_k,
+            // the net waves' accept flags, A, the post, the counters' round trip, B_{k+1}: longer than the two evaluations it hides
+            // behind -- so the rule's float64 arithmetic does not belong between the vote's arrival and B.  The two scales the pending
+            // vote can lead to are kept as doubles (sc_up / sc_dn: fs_cand holds their float casts).  While the vote travels this wave
+            // works out, for EACH of the two, the pair of scales the vote after it can lead to -- four etab reads with a float64
+            // multiply or divide each, in a wait that is longer than they are -- and the vote only SELECTS: the scale, and the next
+            // pair.  (Working the next pair out behind B instead leaves it on the chain: the net waves read fs_cand behind barrier A,
+            // so this wave reaches A, behind which it posts, only after the arithmetic.)  The same next_scale expressions on the same
+            // operands in the same order: the same bits.  Where the table does not reach (steps + 2 > SOLO_ETAB) the rule keeps its
+            // place behind the vote: four more inlined exp() in this kernel moved hipcc's schedule of the net waves' lagged loop.
+            double sc_up = next_scale(accept + 1, reject, scale), sc_dn = next_scale(accept, reject + 1, scale);
             if (lane == 0) {
                 fsbuf[0] = (float)scale;
-                fs_cand[0] = (float)next_scale(accept + 1, reject, scale);
-                fs_cand[1] = (float)next_scale(accept, reject + 1, scale);
+                fs_cand[0] = (float)sc_up;
+                fs_cand[1] = (float)sc_dn;
             }
             solo_barrier();                   // P0
             if (lane == 0) fsbuf[1] = (float)scale;
             solo_barrier();                   // P1
             for (int k = 1; k <= warm; ++k) {
                 solo_barrier();               // A_k: the net waves have decided step k
+                VSTAMP(v_a);
                 if (lane == 0) {
                     const int *ac = acc_lds[k & 1];
                     int acs = 0;
@@ -405,20 +462,51 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
                     mh_sync_post(a.sync, k, tile, acs);
                     fsbuf[(k + 1) & 1] = (float)scale;   // (buffer k + 1's scale is not used: step k + 2 takes fs_exact or a candidate)
                 }
+                VSTAMP(v_post);
                 solo_barrier();               // P_{k+1}
+                VSTAMP(v_p);
                 // (an exact step's vote is read from the tiles' counters themselves -- one memory-side hop less than the window word
                 // the publisher workgroup writes for the lagged steps: counters -> publisher -> window; NNEST_SOLO_VOTE=window keeps the latter)
+                double uu = 0.0, ud = 0.0, du = 0.0, dd = 0.0;   // the scale after this vote AND the next: up-up, up-down, down-up, down-down
+                if (use_tab) {
+                    uu = next_scale_tab(accept + 2, reject, sc_up);
+                    ud = next_scale_tab(accept + 1, reject + 1, sc_up);
+                    du = next_scale_tab(accept + 1, reject + 1, sc_dn);
+                    dd = next_scale_tab(accept, reject + 2, sc_dn);
+                }
+#ifdef NNEST_STAMP_VOTE
+                const bool up = direct_votes ? 2 * solo_vote_total_stamped(a.sync, k, ntiles, a.sync_err, vs) > C
+                                             : mh_window_vote(a.sync, S, k, tile, 0ull, a.sync_err);
+#else
                 const bool up = direct_votes ? 2 * mh_sync_total(a.sync, k, ntiles, 0ull, a.sync_err) > C
                                              : mh_window_vote(a.sync, S, k, tile, 0ull, a.sync_err);
+#endif
+                VSTAMP(v_vote);
                 if (up) accept += 1; else reject += 1;
-                scale = next_scale(accept, reject, scale);
+                scale = up ? sc_up : sc_dn;
+                if (use_tab) {
+                    sc_up = up ? uu : du;
+                    sc_dn = up ? ud : dd;
+                } else {
+                    sc_up = next_scale(accept + 1, reject, scale);
+                    sc_dn = next_scale(accept, reject + 1, scale);
+                }
+                VSTAMP(v_rule);
                 if (lane == 0) {
                     vote_sel = up ? 0 : 1;
                     fs_exact = (float)scale;
-                    fs_cand[0] = (float)next_scale(accept + 1, reject, scale);
-                    fs_cand[1] = (float)next_scale(accept, reject + 1, scale);
+                    fs_cand[0] = (float)sc_up;
+                    fs_cand[1] = (float)sc_dn;
                 }
+                VSTAMP(v_br);
                 solo_barrier();               // B_k
+                VSTAMP(v_b);
+#ifdef NNEST_STAMP_VOTE
+                if (k > 1) va[7] += v_a - v_bprev;
+                va[0] += v_post - v_a; va[1] += v_p - v_post; va[2] += vs.t_first - v_p; va[3] += vs.t_issue - vs.t_first;
+                va[4] += vs.t_ret - vs.t_issue; va[5] += v_rule - v_vote; va[6] += v_br - v_rule; va[8] += v_vote - vs.t_ret; va[9] += v_b - v_br;
+                v_bprev = v_b;
+#endif
             }
         }
         for (int k2 = k0; k2 <= S; k2 += 2) {
@@ -446,6 +534,14 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         if (a.scale_out && lane == 0) {
             const int g0 = (tile * WPG + 15) >> 4;
             if (16 * g0 < (tile + 1) * WPG && 16 * g0 < C) a.scale_out[g0] = (float)scale;
+        }
+#endif
+#ifdef NNEST_STAMP_VOTE
+        if (a.scale_out && lane == 0 && tile == 0 && (C + 15) / 16 >= 62) {   // sums over the exact steps (tools/stamp_solo_vote.py divides)
+            float *o = a.scale_out;
+#pragma unroll
+            for (int i = 0; i < 10; ++i) o[40 + i] = (float)va[i];
+            o[50] = (float)vs.reads; o[51] = (float)vs.first_seen; o[52] = (float)warm; o[53] = (float)ntiles;
         }
 #endif
         return;
@@ -540,6 +636,9 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
 
     unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, a_prop = 0, a_inv = 0, a_post = 0, a_tot = 0;
     (void)st0; (void)st1; (void)st2; (void)st3; (void)a_prop; (void)a_inv; (void)a_post; (void)a_tot;
+#ifdef NNEST_STAMP_VOTE
+    unsigned long long w_a = 0, w_a2 = 0, w_f = 0, w_b = 0, wa[4] = {0, 0, 0, 0};
+#endif
     // One Metropolis step in three parts, so that the warm-up below can evaluate a step for TWO candidate scales:
     //   propose   z' = z + randn * scale  (sampler.py:310, :316), float32 like torch -- from the noise held in registers;
     //   finish    x' = f^-1(z'), box prior, Jacobian ratio, likelihood, the decision (sampler.py:321-361 / :396-410);
@@ -635,11 +734,16 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         for (int it = 1; it <= warm; ++it) {
             STAMP(st0);
             apply(it, it & 1, cur);
+            VSTAMP(w_a);
+#ifdef NNEST_STAMP_VOTE
+            if (it > 1) wa[0] += w_a - w_b;    // B passed .. A reached
+#endif
             // Warm-up (round 4).  The scale of step it + 1 exists only after the whole batch's vote on step it -- a grid-wide
             // round trip (~2.5 us) that round 3 spent waiting.  There are only TWO scales it can be (the vote is up or down;
             // the relay wave works both out beforehand, in the rule's own float64 arithmetic), so step it + 1 is evaluated for
             // both while the vote travels, and the one the vote names is kept: the chain is, bit for bit, the one that waits.
-            solo_barrier();                    // A: the relay posts this step's accepts and starts waiting for the vote
+            solo_barrier();                   // A: the relay posts this step's accepts and starts waiting for the vote
+            VSTAMP(w_a2);
             const float f0 = fs_cand[0], f1 = fs_cand[1];
             Prop c1;
             float u;
@@ -648,12 +752,17 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
             fetch_noise((it + 1) & 1, cur.zp, c1.zp);   // P: the noise of step it + 2
             finish(cur, u);
             finish(c1, u);
+            VSTAMP(w_f);
             solo_barrier();                    // B: the vote is in
+            VSTAMP(w_b);
             if (vote_sel != 0) cur = c1;
             fs_next = fs_exact;                // (step warm + 2 runs at the scale the exact steps end with: no lagged vote is due yet)
             STAMP(st3);
 #ifdef NNEST_STAMP
             a_prop += st1 - st0; a_inv += st2 - st1; a_post += st3 - st2; a_tot += st3 - st0;
+#endif
+#ifdef NNEST_STAMP_VOTE
+            wa[1] += w_a2 - w_a; wa[2] += w_f - w_a2; wa[3] += w_b - w_f;
 #endif
         }
         apply(warm + 1, (warm + 1) & 1, cur);  // step warm + 1: the candidate chosen at B_warm
@@ -693,6 +802,12 @@ __global__ void __launch_bounds__(64 * (WPG + 2)) mh_kernel_solo(MhArgs a) {
         float *o = a.scale_out;
         if (j == 0) { o[0] = (float)a_tot; o[1] = (float)a_prop; o[2] = (float)a_inv; o[3] = (float)a_post; }
         if (j < 4) { o[8 + 2 * j] = (float)a_inv; o[9 + 2 * j] = (float)a_post; }   // the four net waves: which one shares its SIMD with the noise wave
+    }
+#endif
+#ifdef NNEST_STAMP_VOTE
+    if (a.scale_out && lane == 0 && tile == 0 && j == 0 && (C + 15) / 16 >= 62) {   // sums over the exact steps, like the relay's
+        float *o = a.scale_out;
+        o[54] = (float)wa[0]; o[55] = (float)wa[1]; o[56] = (float)wa[2]; o[57] = (float)wa[3];
     }
 #endif
     bool all_moved = n_acc > 0;   // (no x buffer: the accept count stands in)
