@@ -5,7 +5,7 @@
 // in the place of mcmc_target_tempered's 0.0.  Here are the descriptor, the prior term in both layouts, the arguments and the
 // launchers' declarations.  The arithmetic, with t = T(x) the float32 row the likelihood sees:
 //   u_c = (t_c - m_c) * r_c            float32, each operation rounded (contract off)
-//   ss = sum_c (double)u_c (double)u_c float64, in the layout's own fixed order: the order of glm_row_zz / glm_tile_row_zz
+//   ss = sum_c (double)u_c (double)u_c float64, in the layout's own fixed order: the order of solo_row_zz / tile_row_zz
 //   log pi = logc - 0.5 ss             float64; -inf where ss is not finite (a non-finite coordinate is refused, never NaN)
 //   lp_beta = ((beta logL) + log|det|) + log pi    each operation rounded; -inf outside the box lo / hi, as in every sibling
 // Padded dimensions carry m = 0, r = 0 under t = 0: u = 0.  glm_data.h is included, not edited.
@@ -42,7 +42,7 @@ __device__ __forceinline__ double mcmc_target_tempered_prior(double logl, float 
 #pragma clang fp contract(fast)
 
 // ---- the solo layout (solo_tile.h): lane = 16 g + p holds dims 2U p + 2u + c of the row, and of m and r (pm, pr: loaded once a
-// launch); the lane's 2U products in the order (u, c), then the four-step xor butterfly over the 16 positions: glm_row_zz's order ----
+// launch); the lane's 2U products in the order (u, c), then the four-step xor butterfly over the 16 positions: solo_row_zz's order ----
 template <int U>
 __device__ __forceinline__ double gauss_prior_solo(const float (&tx)[2][U], const float (&pm)[2][U], const float (&pr)[2][U], double logc) {
     double ss = 0.0;
@@ -75,7 +75,7 @@ __device__ __forceinline__ void gauss_prior_solo_load(const GaussPriorSpec &p, i
 
 // ---- the team tile (spline_latent.h): lane = 16 g + w holds, of walker w, the dims 32 tau + 8 g + j; ppar: [2][32 NT] floats in
 // LDS -- m, r, padded dims 0 --, read as tpar is.  Every wave sums its own copy of the tile in full (group_sum over the walker's four
-// lane groups), in glm_tile_row_zz's order: the four waves hold the same bits without an exchange ----
+// lane groups), in tile_row_zz's order: the four waves hold the same bits without an exchange ----
 // (class c of the lane's eight consecutive values: spline_latent.h's tile_class, restated -- this header serves the solo unit too)
 __device__ __forceinline__ f32x4 gauss_prior_class(const f32x4 &v0, const f32x4 &v1, int c) {
     return c ? (f32x4){v0.y, v0.w, v1.y, v1.w} : (f32x4){v0.x, v0.z, v1.x, v1.z};

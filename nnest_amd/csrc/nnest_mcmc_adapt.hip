@@ -21,22 +21,6 @@
 
 namespace nnest {
 
-// the float64 sum of squares of a row (padded dims hold 0), the same bits on every lane of the wave: importance_kernel's order
-// (nnest_mcmc_mixed.hip's solo_row_zz, restated: that unit stays what it is)
-template <int U>
-__device__ __forceinline__ double adapt_row_zz(const float (&v)[2][U]) {
-    double zz = 0.0;
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) zz += (double)v[c][u] * (double)v[c][u];   // (the product of two float32 is exact in float64)
-    zz += __shfl_xor(zz, 1);
-    zz += __shfl_xor(zz, 2);
-    zz += __shfl_xor(zz, 4);
-    zz += __shfl_xor(zz, 8);
-    return zz;
-}
-
 template <int U, int LK>
 __global__ void __launch_bounds__(256) mcmc_adapt_kernel(FlowShape s, const float *__restrict__ packed, McmcAdaptArgs a) {
     extern __shared__ __attribute__((aligned(16))) float wlds[];
@@ -110,8 +94,8 @@ __global__ void __launch_bounds__(256) mcmc_adapt_kernel(FlowShape s, const floa
         // the two sides of the accept rule: lp on a local step, the log importance weight on a global one
         double lnew = lpq, lold = lp;
         if (glob) {
-            lnew = mixed_logw(lpq, adapt_row_zz<U>(q), D);
-            lold = mixed_logw(lp, adapt_row_zz<U>(z), D);
+            lnew = mixed_logw(lpq, solo_row_zz<U>(q), D);
+            lold = mixed_logw(lp, solo_row_zz<U>(z), D);
         }
         const bool acc = !init && ens_accept_factor(lnew, lold, 0.0, uacc);
         if (acc || init) {

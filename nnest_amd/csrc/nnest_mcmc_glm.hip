@@ -6,7 +6,7 @@
 // global_every = 0 the random walk, beta the tempering --, so one kernel per family serves every fused Metropolis route.
 //
 // Layout: mcmc_gdata_kernel's, the solo layout, one walker per wave; the flow half is solo_latent.h's SoloFlow, T and the box are
-// SoloBox's fields, restated here in front of the likelihood of glm_data.h (data rows over the wave's 64 lanes).
+// SoloBox::map, in front of the likelihood of glm_data.h (data rows over the wave's 64 lanes).
 #include <stdio.h>
 #include <string.h>
 
@@ -16,21 +16,6 @@
 #include "solo_latent.h"
 
 namespace nnest {
-
-// the float64 sum of squares of a row (nnest_mcmc_adapt.hip's adapt_row_zz, restated: that unit stays what it is)
-template <int U>
-__device__ __forceinline__ double glm_row_zz(const float (&v)[2][U]) {
-    double zz = 0.0;
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) zz += (double)v[c][u] * (double)v[c][u];   // (the product of two float32 is exact in float64)
-    zz += __shfl_xor(zz, 1);
-    zz += __shfl_xor(zz, 2);
-    zz += __shfl_xor(zz, 4);
-    zz += __shfl_xor(zz, 8);
-    return zz;
-}
 
 template <int U, int FAM>
 __global__ void __launch_bounds__(256) mcmc_glm_kernel(FlowShape s, const float *__restrict__ packed, McmcGlmArgs a) {
@@ -50,15 +35,7 @@ __global__ void __launch_bounds__(256) mcmc_glm_kernel(FlowShape s, const float 
     auto target = [&](float (&xs)[2][U], double &logl) -> double {
         const float ld = solo_logdet_total(flow.inverse(xs));
         float tx[2][U];
-        int ok = 1;
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                tx[c][u] = ens_T(xs[c][u], box.sd[c][u], box.mu[c][u]);
-                ok &= !(tx[c][u] < box.blo[c][u] || tx[c][u] > box.bhi[c][u]);   // (NaN counts as inside: UniformPrior, priors.py)
-            }
-        const bool in_prior = __ballot(ok != 0) == ~0ull;
+        const bool in_prior = box.map(xs, tx);
         logl = glm_solo_loglike<U, FAM>(a.gl, lane, tx);
         return mcmc_target_tempered(logl, ld, in_prior, a.beta);
     };
@@ -114,8 +91,8 @@ __global__ void __launch_bounds__(256) mcmc_glm_kernel(FlowShape s, const float 
         // the two sides of the accept rule: lp on a local step, the log importance weight on a global one
         double lnew = lpq, lold = lp;
         if (glob) {
-            lnew = mixed_logw(lpq, glm_row_zz<U>(q), D);
-            lold = mixed_logw(lp, glm_row_zz<U>(z), D);
+            lnew = mixed_logw(lpq, solo_row_zz<U>(q), D);
+            lold = mixed_logw(lp, solo_row_zz<U>(z), D);
         }
         const bool acc = !init && ens_accept_factor(lnew, lold, 0.0, uacc);
         if (acc || init) {
@@ -174,13 +151,7 @@ static hipError_t mcmc_glm_launch_k(const FlowShape &s, const float *packed, con
 
 template <int FAM>
 static hipError_t mcmc_glm_launch_f(const FlowShape &s, const float *packed, const McmcGlmArgs &a, hipStream_t st) {
-    switch (s.NT) {
-        case 1: return mcmc_glm_launch_k<1, FAM>(s, packed, a, st);
-        case 2: return mcmc_glm_launch_k<2, FAM>(s, packed, a, st);
-        case 3: return mcmc_glm_launch_k<3, FAM>(s, packed, a, st);
-        case 4: return mcmc_glm_launch_k<4, FAM>(s, packed, a, st);
-    }
-    return hipErrorInvalidConfiguration;
+    return solo_for_U(s.NT, [&](auto sh) { return mcmc_glm_launch_k<decltype(sh)::U, FAM>(s, packed, a, st); });
 }
 
 hipError_t launch_mcmc_glm(const FlowShape &s, const float *packed, const McmcGlmArgs &a, hipStream_t st) {
@@ -200,13 +171,8 @@ static hipError_t loglike_glm_launch_k(const GlmSpec &gl, const float *t, double
 
 template <int FAM>
 static hipError_t loglike_glm_launch_f(const GlmSpec &gl, const float *t, double *logl, int N, hipStream_t st) {
-    switch ((gl.D + 31) / 32) {   // (U: the lane's 2U dims, 32 U >= D)
-        case 1: return loglike_glm_launch_k<1, FAM>(gl, t, logl, N, st);
-        case 2: return loglike_glm_launch_k<2, FAM>(gl, t, logl, N, st);
-        case 3: return loglike_glm_launch_k<3, FAM>(gl, t, logl, N, st);
-        case 4: return loglike_glm_launch_k<4, FAM>(gl, t, logl, N, st);
-    }
-    return hipErrorInvalidConfiguration;
+    // (U: the lane's 2U dims, 32 U >= D)
+    return solo_for_U((gl.D + 31) / 32, [&](auto sh) { return loglike_glm_launch_k<decltype(sh)::U, FAM>(gl, t, logl, N, st); });
 }
 
 hipError_t launch_loglike_glm(const GlmSpec &gl, const float *t, double *logl, int N, hipStream_t st) {

@@ -17,21 +17,6 @@
 
 namespace nnest {
 
-// the float64 sum of squares of a row (nnest_mcmc_glm.hip's glm_row_zz, restated: that unit stays what it is)
-template <int U>
-__device__ __forceinline__ double glmp_row_zz(const float (&v)[2][U]) {
-    double zz = 0.0;
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) zz += (double)v[c][u] * (double)v[c][u];   // (the product of two float32 is exact in float64)
-    zz += __shfl_xor(zz, 1);
-    zz += __shfl_xor(zz, 2);
-    zz += __shfl_xor(zz, 4);
-    zz += __shfl_xor(zz, 8);
-    return zz;
-}
-
 template <int U, int FAM>
 __global__ void __launch_bounds__(256) mcmc_glm_prior_kernel(FlowShape s, const float *__restrict__ packed, McmcGlmPriorArgs a) {
     extern __shared__ __attribute__((aligned(16))) float wlds[];
@@ -53,15 +38,7 @@ __global__ void __launch_bounds__(256) mcmc_glm_prior_kernel(FlowShape s, const 
     auto target = [&](float (&xs)[2][U], double &logl) -> double {
         const float ld = solo_logdet_total(flow.inverse(xs));
         float tx[2][U];
-        int ok = 1;
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                tx[c][u] = ens_T(xs[c][u], box.sd[c][u], box.mu[c][u]);
-                ok &= !(tx[c][u] < box.blo[c][u] || tx[c][u] > box.bhi[c][u]);   // (NaN counts as inside: UniformPrior, priors.py)
-            }
-        const bool in_box = __ballot(ok != 0) == ~0ull;
+        const bool in_box = box.map(xs, tx);
         const double logpi = gauss_prior_solo<U>(tx, pm, pr, logc);
         logl = glm_solo_loglike<U, FAM>(a.gl, lane, tx);
         return mcmc_target_tempered_prior(logl, ld, in_box, logpi, a.beta);
@@ -118,8 +95,8 @@ __global__ void __launch_bounds__(256) mcmc_glm_prior_kernel(FlowShape s, const 
         // the two sides of the accept rule: lp on a local step, the log importance weight on a global one
         double lnew = lpq, lold = lp;
         if (glob) {
-            lnew = mixed_logw(lpq, glmp_row_zz<U>(q), D);
-            lold = mixed_logw(lp, glmp_row_zz<U>(z), D);
+            lnew = mixed_logw(lpq, solo_row_zz<U>(q), D);
+            lold = mixed_logw(lp, solo_row_zz<U>(z), D);
         }
         const bool acc = !init && ens_accept_factor(lnew, lold, 0.0, uacc);
         if (acc || init) {
@@ -179,13 +156,7 @@ static hipError_t mcmc_glm_prior_launch_k(const FlowShape &s, const float *packe
 
 template <int FAM>
 static hipError_t mcmc_glm_prior_launch_f(const FlowShape &s, const float *packed, const McmcGlmPriorArgs &a, hipStream_t st) {
-    switch (s.NT) {
-        case 1: return mcmc_glm_prior_launch_k<1, FAM>(s, packed, a, st);
-        case 2: return mcmc_glm_prior_launch_k<2, FAM>(s, packed, a, st);
-        case 3: return mcmc_glm_prior_launch_k<3, FAM>(s, packed, a, st);
-        case 4: return mcmc_glm_prior_launch_k<4, FAM>(s, packed, a, st);
-    }
-    return hipErrorInvalidConfiguration;
+    return solo_for_U(s.NT, [&](auto sh) { return mcmc_glm_prior_launch_k<decltype(sh)::U, FAM>(s, packed, a, st); });
 }
 
 hipError_t launch_mcmc_glm_prior(const FlowShape &s, const float *packed, const McmcGlmPriorArgs &a, hipStream_t st) {
@@ -205,13 +176,8 @@ static hipError_t logprior_gauss_launch_k(const GaussPriorSpec &p, const float *
 
 hipError_t launch_logprior_gauss(const GaussPriorSpec &p, const float *t, double *logp, int N, hipStream_t st) {
     if (N <= 0) return hipSuccess;
-    switch ((p.D + 31) / 32) {   // (U: the lane's 2U dims, 32 U >= D)
-        case 1: return logprior_gauss_launch_k<1>(p, t, logp, N, st);
-        case 2: return logprior_gauss_launch_k<2>(p, t, logp, N, st);
-        case 3: return logprior_gauss_launch_k<3>(p, t, logp, N, st);
-        case 4: return logprior_gauss_launch_k<4>(p, t, logp, N, st);
-    }
-    return hipErrorInvalidConfiguration;
+    // (U: the lane's 2U dims, 32 U >= D)
+    return solo_for_U((p.D + 31) / 32, [&](auto sh) { return logprior_gauss_launch_k<decltype(sh)::U>(p, t, logp, N, st); });
 }
 
 }  // namespace nnest

@@ -24,21 +24,6 @@
 
 namespace nnest {
 
-// the float64 sum of squares of a row (padded dims hold 0), the same bits on every lane of the wave: importance_kernel's order
-template <int U>
-__device__ __forceinline__ double solo_row_zz(const float (&v)[2][U]) {
-    double zz = 0.0;
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) zz += (double)v[c][u] * (double)v[c][u];   // (the product of two float32 is exact in float64)
-    zz += __shfl_xor(zz, 1);
-    zz += __shfl_xor(zz, 2);
-    zz += __shfl_xor(zz, 4);
-    zz += __shfl_xor(zz, 8);
-    return zz;
-}
-
 template <int U, int LK>
 __global__ void __launch_bounds__(256) mcmc_mixed_kernel(FlowShape s, const float *__restrict__ packed, McmcMixedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float wlds[];

@@ -18,21 +18,6 @@
 
 namespace nnest {
 
-// the float64 sum of squares of a walker's row (padded dims hold 0), the same bits on its four lane groups
-// (nnest_spline_mcmc_mixed.hip's tile_row_zz, restated: that unit stays what it is)
-template <int NT>
-__device__ __forceinline__ double adapt_tile_row_zz(const f32x4 (&v)[2][NT]) {
-    double zz = 0.0;
-#pragma unroll
-    for (int tau = 0; tau < NT; ++tau)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const f32x4 zc = v[c][tau];
-            zz += (double)zc.x * (double)zc.x + (double)zc.y * (double)zc.y + (double)zc.z * (double)zc.z + (double)zc.w * (double)zc.w;
-        }
-    return group_sum(zz);
-}
-
 // The walk of one tile (16 walkers, this wave's copy) through the S steps of a launch.  tpar: [4][32 NT] in LDS -- std, mean, lo, hi
 // (padded dims: 0, 0, -inf, +inf).  `writer`: the wave that stores.
 template <int NT, class Inv>
@@ -102,8 +87,8 @@ __device__ __forceinline__ void mcmc_adapt_tile_walk(const McmcAdaptArgs &a, int
         // the two sides of the accept rule: lp on a local step, the log importance weight on a global one
         double lnew = lpq, lold = lp;
         if (glob) {
-            lnew = mixed_logw(lpq, adapt_tile_row_zz<NT>(q), D);
-            lold = mixed_logw(lp, adapt_tile_row_zz<NT>(z), D);
+            lnew = mixed_logw(lpq, tile_row_zz<NT>(q), D);
+            lold = mixed_logw(lp, tile_row_zz<NT>(z), D);
         }
         const bool acc = moving && ens_accept_factor(lnew, lold, 0.0, uacc);
         const bool take = acc || init;

@@ -16,46 +16,14 @@
 
 namespace nnest {
 
-// the float64 sum of squares of a walker's row (nnest_spline_mcmc_adapt.hip's adapt_tile_row_zz, restated: that unit stays what it is)
-template <int NT>
-__device__ __forceinline__ double gdata_tile_row_zz(const f32x4 (&v)[2][NT]) {
-    double zz = 0.0;
-#pragma unroll
-    for (int tau = 0; tau < NT; ++tau)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const f32x4 zc = v[c][tau];
-            zz += (double)zc.x * (double)zc.x + (double)zc.y * (double)zc.y + (double)zc.z * (double)zc.z + (double)zc.w * (double)zc.w;
-        }
-    return group_sum(zz);
-}
-
-// x <- f^-1(x) in place; returns combine(logL(T(x)), ld, in_prior): spl_tile_eval (spline_latent.h), restated with the likelihood
+// x <- f^-1(x) in place; returns combine(logL(T(x)), ld, in_prior): spl_tile_eval (spline_latent.h) on spl_tile_map, with the likelihood
 // of mcmc_gdata.h behind T and the box
 template <int NT, class Inv, class Combine>
 __device__ __forceinline__ double gdata_tile_eval(const Inv &inv, const float *tpar, const GdataSpec &gd, const float *gmu, int lane,
                                                   f32x4 (&xs)[2][NT], Combine &&combine) {
-    const int g = lane >> 4;
     const float ld = group_sum(inv(xs));
     f32x4 tx[2][NT];
-    int inside = 1;
-#pragma unroll
-    for (int tau = 0; tau < NT; ++tau) {
-        const f32x4 *p = reinterpret_cast<const f32x4 *>(tpar + 32 * tau + 8 * g);
-        constexpr int PW = 8 * NT;   // f32x4 per parameter
-        const f32x4 s0 = p[0], s1 = p[1], m0 = p[PW], m1 = p[PW + 1], l0 = p[2 * PW], l1 = p[2 * PW + 1], h0 = p[3 * PW], h1 = p[3 * PW + 1];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const f32x4 sd = tile_class(s0, s1, c), mu = tile_class(m0, m1, c), lo = tile_class(l0, l1, c), hi = tile_class(h0, h1, c);
-            f32x4 t;
-            t.x = ens_T(xs[c][tau].x, sd.x, mu.x); t.y = ens_T(xs[c][tau].y, sd.y, mu.y);
-            t.z = ens_T(xs[c][tau].z, sd.z, mu.z); t.w = ens_T(xs[c][tau].w, sd.w, mu.w);
-            // (NaN counts as inside: UniformPrior, priors.py)
-            inside &= !(t.x < lo.x || t.x > hi.x) & !(t.y < lo.y || t.y > hi.y) & !(t.z < lo.z || t.z > hi.z) & !(t.w < lo.w || t.w > hi.w);
-            tx[c][tau] = t;
-        }
-    }
-    const bool in_prior = group_all(inside != 0, lane) != 0;
+    const bool in_prior = spl_tile_map<NT>(tpar, lane, xs, tx);
     const double logl = gdata_tile_loglike<NT>(gd, lane, tx, gmu);
     return combine(logl, ld, in_prior);
 }
@@ -128,8 +96,8 @@ __device__ __forceinline__ void mcmc_gdata_tile_walk(const McmcGdataArgs &a, int
         // the two sides of the accept rule: lp on a local step, the log importance weight on a global one
         double lnew = lpq, lold = lp;
         if (glob) {
-            lnew = mixed_logw(lpq, gdata_tile_row_zz<NT>(q), D);
-            lold = mixed_logw(lp, gdata_tile_row_zz<NT>(z), D);
+            lnew = mixed_logw(lpq, tile_row_zz<NT>(q), D);
+            lold = mixed_logw(lp, tile_row_zz<NT>(z), D);
         }
         const bool acc = moving && ens_accept_factor(lnew, lold, 0.0, uacc);
         const bool take = acc || init;

@@ -21,20 +21,6 @@
 
 namespace nnest {
 
-// the float64 sum of squares of a walker's row (padded dims hold 0), the same bits on its four lane groups
-template <int NT>
-__device__ __forceinline__ double tile_row_zz(const f32x4 (&v)[2][NT]) {
-    double zz = 0.0;
-#pragma unroll
-    for (int tau = 0; tau < NT; ++tau)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const f32x4 zc = v[c][tau];
-            zz += (double)zc.x * (double)zc.x + (double)zc.y * (double)zc.y + (double)zc.z * (double)zc.z + (double)zc.w * (double)zc.w;
-        }
-    return group_sum(zz);
-}
-
 // The walk of one tile (16 walkers, this wave's copy) through the S steps of a launch.  tpar: [4][32 NT] in LDS -- std, mean, lo, hi
 // (padded dims: 0, 0, -inf, +inf).  `writer`: the wave that stores.
 template <int NT, class Inv>

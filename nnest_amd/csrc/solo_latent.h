@@ -1,12 +1,14 @@
 // solo_latent.h -- the LATENT TARGET in the solo layout (nnest_solo.hip's: one walker per wave, lane = 32 n + 16 h + p holds dims
 // 2U p + 2u + c, the four (n, h) rows hold copies), stated once for the fused kernels that evaluate it: ensemble_x_kernel
-// (nnest_ensemble.hip) and mcmc_kernel (nnest_mcmc.hip).  (ensemble_kernel and importance_kernel each keep a written-out copy of this
-// text, for a measured reason: see the comment above each.  Their launchers use the LDS size and the shape table below.)
+// (nnest_ensemble.hip) and the walks of nnest_mcmc.hip and its five siblings.  (ensemble_kernel and importance_kernel
+// each keep a written-out copy of this text, for a measured reason: see the comment above each.  Their launchers use the LDS size
+// and the shape table below.)
 //   z -> x = f^-1(z), ld = log|det dx/dz|;  T(x) = x std + mean per dimension (float32, no contraction: ens_T);  the box on T(x), a NaN
 //   coordinate counting as inside;  logL = safe_loglike(T(x)) at scale 1.
 // Two halves.  SoloFlow is f^-1: the weights' staging in LDS, the lane's share of the three blocks, the inverse.  SoloBox is
-// everything behind it: T, the box, the likelihood.  The x-space kernel uses the box half alone.  What a kernel makes of
-// (logL, ld, in_prior) -- ens_target with its loglstar, mcmc_target_tempered -- is its own last line: the `combine` it hands over.
+// everything behind it: T and the box (map), or both and the likelihood (eval).  The x-space kernel uses the box half alone; the walks on
+// a data likelihood use the map and bring their own likelihood.  What a kernel makes of (logL, ld, in_prior) -- ens_target with its
+// loglstar, mcmc_target_tempered -- is its own last line: the `combine` it hands over.
 // Beside them: the rows' load and store, the lane's normals of a Philox-drawn row, and the table of instantiated shapes.
 #pragma once
 #include "ensemble_common.h"
@@ -37,6 +39,23 @@ __device__ __forceinline__ void solo_store_row(float *base, int D, int pos, cons
             const int d = 2 * U * pos + 2 * u + c;
             if (d < D) base[d] = v[c][u];
         }
+}
+
+// the float64 sum of squares of a row (padded dims hold 0), the same bits on every lane of the wave: importance_kernel's order (the
+// lane's dims in order, then a butterfly over the row's 16 positions).  The global step of the mixed walk and its heirs weighs
+// with it (nnest_mcmc_mixed.hip, _adapt, _gdata, _glm, _glm_prior)
+template <int U>
+__device__ __forceinline__ double solo_row_zz(const float (&v)[2][U]) {
+    double zz = 0.0;
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) zz += (double)v[c][u] * (double)v[c][u];   // (the product of two float32 is exact in float64)
+    zz += __shfl_xor(zz, 1);
+    zz += __shfl_xor(zz, 2);
+    zz += __shfl_xor(zz, 4);
+    zz += __shfl_xor(zz, 8);
+    return zz;
 }
 
 // ---- the flow half: NormalizingFlow.inverse (networks.py:34-42) of the default NVP shape ----
@@ -129,9 +148,25 @@ struct SoloBox {
                 bhi[c][u] = v && a.hi ? a.hi[d] : INFINITY;
             }
     }
-    // tx = T(xs); returns combine(safe logL(tx), ld, in_prior) -- the kernel's own last line; in_prior: the whole row inside the box.
+    // tx = T(xs); returns in_prior: the whole row inside the box.
     // tx may BE xs (ensemble_x_kernel maps its row in place): element (c, u) of xs is read once, before element (c, u) of tx is
     // written, and xs is not read again behind the loop.
+    __device__ __forceinline__ bool map(const float (&xs)[2][U], float (&tx)[2][U]) const {
+        int ok = 1;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                tx[c][u] = ens_T(xs[c][u], sd[c][u], mu[c][u]);
+                ok &= !(tx[c][u] < blo[c][u] || tx[c][u] > bhi[c][u]);   // (NaN counts as inside: UniformPrior, priors.py)
+            }
+        return __ballot(ok != 0) == ~0ull;
+    }
+    // tx = T(xs), then the likelihood: returns combine(safe logL(tx), ld, in_prior) -- the kernel's own last line.  tx may BE xs, as
+    // in map.  A kernel with a likelihood of its own (the data likelihoods of nnest_mcmc_gdata.hip, _glm, _glm_prior) calls map and
+    // goes on from tx itself.
+    // (map's loop written out, not called: with the call, ensemble_x_kernel and every LK = -1 walk kernel at U >= 2 compiled to
+    // another schedule and other SGPR spills -- profiles/mcmc_shared_walk/resources.txt -- and each would have wanted its timing.)
     // (Handed on, not given back through references: out-parameters change hipcc's code for the surrounding kernel; spline_latent.h)
     template <class Combine>
     __device__ __forceinline__ double eval(const float (&xs)[2][U], float (&tx)[2][U], float ld, Combine &&combine) const {
@@ -196,6 +231,20 @@ inline hipError_t solo_for_shape(int NT, int like_id, F &&f) {
         case 2: return rosen ? f(SoloShape<2, NNEST_LIKE_ROSENBROCK>{}) : f(SoloShape<2, -1>{});
         case 3: return rosen ? f(SoloShape<3, NNEST_LIKE_ROSENBROCK>{}) : f(SoloShape<3, -1>{});
         case 4: return rosen ? f(SoloShape<4, NNEST_LIKE_ROSENBROCK>{}) : f(SoloShape<4, -1>{});
+    }
+    return hipErrorInvalidConfiguration;
+}
+// ... of the kernels with no likelihood to select: f(SoloU<U>{}) for U in 1 .. 4 (the walks on data: U = NT; the kernels on rows
+// that are already T(x): U = (D + 31) / 32, the lane's 2U dims with 32 U >= D)
+template <int U_>
+struct SoloU { static constexpr int U = U_; };
+template <class F>
+inline hipError_t solo_for_U(int U, F &&f) {
+    switch (U) {
+        case 1: return f(SoloU<1>{});
+        case 2: return f(SoloU<2>{});
+        case 3: return f(SoloU<3>{});
+        case 4: return f(SoloU<4>{});
     }
     return hipErrorInvalidConfiguration;
 }

@@ -12,7 +12,13 @@ with padded dims); the spline at the six (NTh, NH) keys, at the dims of tests/te
 tests/fused_like_check.py with its recipes for T, a box on every case, start row 1 outside the box, start row 2 with a NaN.
 Per case: the ensemble (the stretch move, and for the NVP the stretch / DE mixture; constrained 0 and 1, loglstar the median of the
 start's logL), the random walk (untempered and at beta = 0.37; lp given and evaluated; steps = 0) and the importance run (M = 100
-with the samples, sample_offset != 0).  The x-space ensemble runs at the NVP's cases, with T and without."""
+with the samples, sample_offset != 0).  The x-space ensemble runs at the NVP's cases, with T and without.
+The walks behind the random walk run at the same cases and, on the data likelihoods, at every shape:
+the mixed walk (global_every 3), the adaptive walk (adapt_steps below and above the 6 steps, step_in given and None, hist_step), each
+also as one launch cut in two with lp, logL and the steps handed on; on the Gaussian likelihood from data, on both regression
+families and on those under normal priors (the targets of tools/mcmc_gdata_cases.py, mcmc_glm_cases.py, mcmc_glm_prior_cases.py:
+tests/gdata_check.replay_target, tests/glm_check.replay_target, tests/gauss_prior_check.replay_prior).  The three stand-alone kernels
+(loglike_gdata, loglike_glm, logprior_gauss) run at D = 1, 31, 32, 33, 65, 128."""
 import os
 import sys
 
@@ -23,9 +29,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nnest_amd import flow  # noqa: E402
 from nnest_amd.spline import HipSpline  # noqa: E402
 from tests import fused_like_check as fl  # noqa: E402
+from tests import gauss_prior_check as pk  # noqa: E402
+from tests import gdata_check as gd  # noqa: E402
+from tests import glm_check as gk  # noqa: E402
 
 C, S, M, BETA, OFFSET = 37, 6, 100, 0.37, 12345
 MIX = {'stretch': 0.5, 'de': 0.5}
+EVERY, CUT = 3, 3   # the mixed walk's global_every; where the launch cut in two is cut
+GLMS = ((40, 'logistic'), (70, 'poisson'))   # (n, family) of the regression targets, as tools/mcmc_glm_cases.py pairs them
+ALONE_DIMS = (1, 31, 32, 33, 65, 128)
 # (likelihood, recipe, x_dim): Rosenbrock (compiled in) and a generic likelihood at every U, all seven likelihoods
 NVP_CASES = [('rosenbrock', 'valley', 5), ('rosenbrock', 'wide', 50), ('rosenbrock', 'valley', 70), ('rosenbrock', 'valley', 100),
              ('shell', 'main', 5), ('gaussmix', 'main', 50), ('himmelblau', 'main', 70), ('double_shell', 'main', 100),
@@ -82,7 +94,54 @@ def latent_case(dump, case, net, like_id, params, D, sd, mu, lo, hi, mixes):
     dump(case, 'ens-s0', net.ensemble_steps(like_id, z0, 0, seed=21, **kw))
     dump(case, 'imp', net.importance_evidence(like_id, M, seed=31, sample_offset=OFFSET, want_samples=True, **kw))
     dump(case, 'imp-sums', net.importance_evidence(like_id, M, seed=32, **kw))
+    walk_case(dump, case, net, like_id, z0, step, **kw)
     return star
+
+
+def walk_case(dump, case, net, like_id, z0, step, **kw):
+    """the mixed and the adaptive walk on one target (kw: T, the box, and like_params or a data likelihood's descriptors)"""
+    C = z0.shape[0]
+    step_in = torch.as_tensor(step * np.linspace(0.5, 2.0, C), dtype=torch.float64, device=z0.device)
+    runs = (('mixed', dict(global_every=EVERY, beta=BETA)),
+            ('adapt-lo', dict(global_every=EVERY, adapt_steps=S - 2)),
+            ('adapt-hi-in', dict(global_every=EVERY, beta=BETA, adapt_steps=S + 4, step_in=step_in)),
+            ('adapt-in', dict(step_in=step_in)))
+    for tag, opts in runs:
+        dump(case, tag, net.mcmc_steps(like_id, z0, S, step, seed=51, walker_offset=5, **opts, **kw))
+        # the same launch cut in two: the state handed on (the second half must be the first run's second half)
+        a = dump(case, tag + '-cut1', net.mcmc_steps(like_id, z0, CUT, step, seed=51, walker_offset=5, **opts, **kw))
+        rest = dict(opts, step_in=a['step']) if 'step' in a else opts
+        dump(case, tag + '-cut2', net.mcmc_steps(like_id, a['z'], S - CUT, step, lp=a['lp'], logl=a['logl'], seed=51, walker_offset=5,
+                                                 step0=CUT, **rest, **kw))
+
+
+def data_cases(dump, case, net, D):
+    """the walks on the data likelihoods at one shape, and their start evaluated (steps = 0)"""
+    r = np.random.RandomState(D)
+    sd, mu = r.uniform(0.5, 1.5, D).astype(np.float32), r.uniform(-0.3, 0.3, D).astype(np.float32)
+    lo, hi = np.full(D, -4.0, np.float32), np.full(D, 4.0, np.float32)
+    z0 = net.forward(start_x(D, sd, mu, lo, hi))[0].contiguous()
+    step = 1.0 / np.sqrt(D)
+    targets = [('gdata', dict(like_data=gd.replay_target(D)))]
+    for n, family in GLMS:
+        glm = gk.replay_target(D, n, family)
+        targets.append(('glm-%s' % family, dict(like_glm=glm)))
+        targets.append(('glmp-%s' % family, dict(like_glm=glm, prior_gauss=pk.replay_prior(D, 1.0).hip_gauss_prior)))
+    for tag, like in targets:
+        kw = dict(t_std=sd, t_mean=mu, lo=lo, hi=hi, **like)
+        dump(case + '-' + tag, 's0', net.mcmc_steps(None, z0, 0, step, seed=51, **kw))
+        walk_case(dump, case + '-' + tag, net, None, z0, step, **kw)
+
+
+def alone_cases(dump):
+    """the likelihoods and the prior alone, on rows that are already T(x)"""
+    for D in ALONE_DIMS:
+        t = (np.random.RandomState(D).normal(size=(C, D)) * 0.7).astype(np.float32)
+        t[2, 0] = np.nan
+        dump('alone-%d' % D, 'gdata', {'logl': flow.loglike_gdata(gd.replay_target(D), t)})
+        for n, family in GLMS:
+            dump('alone-%d' % D, 'glm-%s' % family, {'logl': flow.loglike_glm(gk.replay_target(D, n, family), t)})
+        dump('alone-%d' % D, 'prior', {'logp': flow.logprior_gauss(pk.replay_prior(D, 1.0).hip_gauss_prior, t)})
 
 
 def x_case(dump, case, like_id, params, D, sd, mu, lo, hi, star):
@@ -105,6 +164,8 @@ def main():
         case = 'nvp-%s-%s-%d' % (name, recipe, D)
         star = latent_case(dump, case, flow.HipNVP(D, 16, 3, 1, seed=D), e['id'], e['params'], D, sd, mu, lo, hi, (('st', None), ('mix', MIX)))
         x_case(dump, case, e['id'], e['params'], D, sd, mu, lo, hi, star)
+    for D in (5, 50, 70, 100):   # (U = 1 .. 4)
+        data_cases(dump, 'nvp-data-%d' % D, flow.HipNVP(D, 16, 3, 1, seed=D), D)
     for name, recipe, D, H in SPLINE_CASES:
         e = fl.LIKES[name]
         sd, mu = fl.affine(name, recipe, D, D)
@@ -112,6 +173,11 @@ def main():
         sp = HipSpline(D, H, 3, seed=D + H)
         sp.forward((np.random.RandomState(D + H).normal(size=(40, D)) * 0.5).astype(np.float32))   # (sets the ActNorm layers)
         latent_case(dump, 'spl-%s-%s-%d-%d' % (name, recipe, D, H), sp, e['id'], e['params'], D, sd, mu, lo, hi, (('st', None),))
+    for D, H in sorted(set((D, H) for _, _, D, H in SPLINE_CASES if D > 2)):   # (the six keys)
+        sp = HipSpline(D, H, 3, seed=D + H)
+        sp.forward((np.random.RandomState(D + H).normal(size=(40, D)) * 0.5).astype(np.float32))
+        data_cases(dump, 'spl-data-%d-%d' % (D, H), sp, D)
+    alone_cases(dump)
     print('%d arrays under %s' % (dump.n, root))
 
 
