@@ -964,6 +964,34 @@ int nnest_spline_importance_glm_evidence(struct nnest_spline *spl, const nnest_g
                                          float *z_out_dev, float *x_out_dev, double *logl_out_dev, double *logw_out_dev,
                                          double *partials_dev, double *sums_dev, int M, uint64_t seed, uint64_t sample_offset,
                                          void *stream);
+
+/* SLICE PROPOSAL ON A REGRESSION: nnest_slice_steps's update -- directions, Philox uniforms noise_uniform(seed, walker, 64 step + k),
+ * log y = log|det| + log u1, the bracket, the step-out budget with the random split, shrinkage, the counters and NNEST_MH_ALL_MOVED,
+ * word for word -- with the likelihood of a nnest_glm_t (above: float32 eta in the layout's own order, float64 terms, rows >= n
+ * masked, the safe rule -1e100) compiled in, one kernel per flow and family.  BUILD-DEFINED.  Two differences:
+ *   logL(x) := GLM(T(x)), T(x)_d = x_d * t_std[d] + t_mean[d] in float32 without contraction (t_std_dev / t_mean_dev [D], both or
+ *     neither; NULL: the identity);
+ *   the likelihood is not evaluated where no decision depends on it: a candidate outside the box or below the slice level cannot be
+ *     moved to and its logL is read by nothing (the spline tile skips only where none of its 16 walkers needs one).  No output shows it:
+ *     n_eval_dev counts every candidate, n_call_dev those that passed the box and the slice level.
+ * The box is on x (!(x < -1 || x > 1), a NaN coordinate inside), as in nnest_slice_steps -- not on T(x).  The other arguments are
+ * nnest_slice_steps's (max_stepout 0..2^24, max_shrink 1..60, width > 0; the counters may each be NULL); the descriptor is checked
+ * as everywhere (its D against the flow's x_dim, family, n <= 65536: NNEST_E_ARG).  The NVP runs one walker per wave, the spline flow
+ * its team tile (four waves per 16 walkers, the only form); no cross-workgroup wait: any C.
+ * nnest_slice_glm_check, nnest_spline_slice_glm_check: NNEST_OK where the entry takes this handle's shape (the NVP: hidden 16, 3
+ * blocks, 1 layer, scale '', x_dim <= 128; the spline flow: the team tile's shapes) and a descriptor of dimension D, else
+ * NNEST_E_UNSUPPORTED / NNEST_E_ARG with the reason in nnest_hip_last_error; nothing is launched.  Other flows and shapes run the
+ * same definition through nnest_slice_rounds_* with nnest_loglike_glm between the launches.  (All added within ABI 15.) */
+int nnest_slice_glm_check(nnest_nvp_t *nvp, int D);
+int nnest_spline_slice_glm_check(struct nnest_spline *spl, int D);
+int nnest_slice_glm_steps(nnest_nvp_t *nvp, const nnest_glm_t *glm, const float *t_std_dev, const float *t_mean_dev, float *z_dev,
+                          float *x_dev, double *logl_dev, double loglstar, float width, int steps, int C, int max_stepout, int max_shrink,
+                          const float *noise_dz_dev, uint64_t seed, uint64_t walker_offset, float *hist_x_dev, int *n_call_dev,
+                          int *n_move_dev, int *n_eval_dev, void *stream);
+int nnest_spline_slice_glm_steps(struct nnest_spline *spl, const nnest_glm_t *glm, const float *t_std_dev, const float *t_mean_dev,
+                                 float *z_dev, float *x_dev, double *logl_dev, double loglstar, float width, int steps, int C,
+                                 int max_stepout, int max_shrink, const float *noise_dz_dev, uint64_t seed, uint64_t walker_offset,
+                                 float *hist_x_dev, int *n_call_dev, int *n_move_dev, int *n_eval_dev, void *stream);
 /* size of sync_dev in 8-byte words for a launch of `steps` steps */
 int nnest_mh_sync_words(int steps);
 /* number of adaptation groups nnest_mh_constrained_steps uses for C walkers (size of scale_out_dev) */

@@ -281,6 +281,12 @@ SIGNATURES = {
     'nnest_loglike_glm': [_vp, _vp, _vp, _i, _i, _vp],
     'nnest_mcmc_glm_check': [_vp, _i],
     'nnest_spline_mcmc_glm_check': [_vp, _i],
+    # the slice proposal on them: nnest_slice_steps's arguments with `const nnest_glm_t *glm, const float *t_std_dev, const float
+    # *t_mean_dev` for `like` (the spline's takes no flags word: one form); (handle, D)
+    'nnest_slice_glm_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _f, _i, _i, _i, _i, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp],
+    'nnest_spline_slice_glm_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _f, _i, _i, _i, _i, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp],
+    'nnest_slice_glm_check': [_vp, _i],
+    'nnest_spline_slice_glm_check': [_vp, _i],
     # their pointwise predictive statistics: (S, n); (glm, t_dev, stats_dev, partials_dev, S, D, stream)
     'nnest_glm_pointwise_groups': [_i, _i],
     'nnest_glm_pointwise': [_vp, _vp, _vp, _vp, _i, _i, _vp],

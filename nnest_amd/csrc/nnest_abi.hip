@@ -19,6 +19,7 @@
 #include "gauss_prior.h"
 #include "importance_glm.h"
 #include "glm_newton.h"
+#include "slice_glm.h"
 
 using namespace nnest;
 
@@ -887,6 +888,42 @@ int nnest_mcmc_glm_steps(nnest_nvp_t *h, const nnest_glm_t *glm, const float *t_
     hipError_t e = launch_mcmc_glm(h->s, h->w, a, (hipStream_t)stream);
     if (e == hipErrorInvalidConfiguration) return fail(NNEST_E_UNSUPPORTED, "mcmc glm: x_dim=%d not instantiated", h->s.D);
     if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_mcmc_glm: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+// what nnest_slice_glm_steps takes, asked before a launch (and by the entry itself): the shapes of nnest_slice_steps, and a
+// descriptor of the flow's x_dim
+int nnest_slice_glm_check(nnest_nvp_t *h, int D) {
+    if (!h) return fail(NNEST_E_ARG, "NULL handle");
+    if (!slice_form_eligible(h->s))
+        return fail(NNEST_E_UNSUPPORTED, "slice glm: x_dim=%d hidden=%d blocks=%d layers=%d scale mode %d: the kernel takes hidden 16, 3 blocks, "
+                    "1 layer, scale '' (the one-walker-per-wave layout), x_dim <= 128", h->s.D, h->s.H, h->s.B, h->s.L, h->s.scale_mode);
+    if (D != h->s.D) return fail(NNEST_E_ARG, "slice glm: the likelihood's D=%d is not the flow's x_dim=%d", D, h->s.D);
+    return NNEST_OK;
+}
+
+// the slice proposal on the regression likelihoods of the user's data (nnest_slice_glm.hip); the argument checks of nnest_slice_steps
+// and glm_ok (those that need no handle come first)
+int nnest_slice_glm_steps(nnest_nvp_t *h, const nnest_glm_t *glm, const float *t_std_dev, const float *t_mean_dev, float *z_dev,
+                          float *x_dev, double *logl_dev, double loglstar, float width, int steps, int C, int max_stepout, int max_shrink,
+                          const float *noise_dz_dev, uint64_t seed, uint64_t walker_offset, float *hist_x_dev, int *n_call_dev,
+                          int *n_move_dev, int *n_eval_dev, void *stream) {
+    SliceGlmArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc;
+    if ((rc = glm_ok(glm, glm ? glm->D : 0, &a.gl))) return rc;
+    if (!t_std_dev != !t_mean_dev) return fail(NNEST_E_ARG, "t_std_dev and t_mean_dev: both or neither");
+    if (!slice_params_ok(steps, max_stepout, max_shrink, width))
+        return fail(NNEST_E_ARG, "steps=%d max_stepout=%d (0..2^24) max_shrink=%d (1..60) width=%g", steps, max_stepout, max_shrink, (double)width);
+    if ((rc = check_rows(h, z_dev, logl_dev, C))) return rc;
+    if ((rc = nnest_slice_glm_check(h, a.gl.D))) return rc;
+    a.z = z_dev; a.x = x_dev; a.logl = logl_dev; a.loglstar = loglstar; a.width = width; a.steps = steps; a.C = C;
+    a.max_out = max_stepout; a.max_shrink = max_shrink; a.like.scale = 1.0f; a.seed = seed; a.walker_offset = walker_offset;
+    a.noise_dz = noise_dz_dev; a.hist_x = hist_x_dev; a.n_call = n_call_dev; a.n_move = n_move_dev; a.n_eval = n_eval_dev;
+    a.t_std = t_std_dev; a.t_mean = t_mean_dev;
+    hipError_t e = launch_slice_glm(h->s, h->w, a, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(NNEST_E_UNSUPPORTED, "slice glm: x_dim=%d not instantiated", h->s.D);
+    if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_slice_glm: %s", hipGetErrorString(e));
     return NNEST_OK;
 }
 

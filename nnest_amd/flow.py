@@ -291,7 +291,7 @@ class _HipFlow(object):
         return _MhResult(x=x, n_accept_word=n_acc, n_call=n_call, scale=scale_out, hist_x=hx, hist_logl=hl, sync=sync)
 
     def slice_steps(self, like_id, like_scale, z, logl, loglstar, width, steps, max_stepout=8, max_shrink=32, noise=None, seed=0,
-                    walker_offset=0, history=False, like_params=None, form=None):
+                    walker_offset=0, history=False, like_params=None, form=None, like_glm=None, t_std=None, t_mean=None):
         """SLICE proposal in latent space (the family's `slice` entry point: nnest_slice_steps, nnest_spline_slice_steps; BUILD-DEFINED:
         the reference has none, nnest/sampler.py:310-316 is random-walk Metropolis): `steps` slice-sampling updates (stepping out +
         shrinkage along a random direction) of every walker under the hard constraint logL > loglstar, the target the reference's
@@ -299,13 +299,25 @@ class _HipFlow(object):
         recorded directions (fill_slice_noise exports the in-kernel ones).  form: the kernel form, where the family has several
         (HipSpline: None = by population | 'wave' | 'team' | 'pair').  Returns x, n_call (candidates whose likelihood decided),
         n_move, moved (nested.py:432), n_eval (flow evaluations), hist_x.  A family without a fused slice kernel raises
-        NotImplementedError (its handle must not reach another family's): the slice proposal runs it through nnest_amd.slice_rounds."""
-        fn = self._sym.get('slice')
+        NotImplementedError (its handle must not reach another family's): the slice proposal runs it through nnest_amd.slice_rounds.
+        like_glm: None -- the entries above, as they were; the descriptor of a regression likelihood of user data
+        (likelihoods.GLMData.hip_like_glm, as `mcmc_steps` takes it) -- `like_id` must then be None (ValueError otherwise; like_scale
+        and like_params are not read) and the launch goes through the family's `slice_glm` entry (nnest_slice_glm_steps,
+        nnest_spline_slice_glm_steps): the same update with logL(x) = GLM(T(x)), T(x) = x * t_std + t_mean per dimension (t_std /
+        t_mean [D], both or neither; None: the identity).  The box stays on x.  The spline's `slice_glm` kernel has the team form only:
+        form None or 'team' (ValueError otherwise).  `slice_glm_refusal` says beforehand whether the flow's shape is taken."""
+        glm = like_glm is not None
+        if glm and like_id is not None:
+            raise ValueError('slice_steps: like_glm goes with like_id=None, got like_id=%r' % (like_id,))
+        if not glm and (t_std is not None or t_mean is not None):
+            raise ValueError('slice_steps: t_std and t_mean go only with a like_glm (the analytic likelihoods take like_scale)')
+        fn = self._sym.get('slice_glm' if glm else 'slice')
         if fn is None:
-            raise NotImplementedError('no fused slice kernel for %s: use nnest_amd.slice_rounds' % type(self).__name__)
+            raise NotImplementedError('no fused slice kernel for %s%s: use nnest_amd.slice_rounds' % (
+                type(self).__name__, ' on a regression likelihood of user data' if glm else ''))
         assert z.is_cuda and z.dtype == torch.float32 and z.is_contiguous()
         assert logl.is_cuda and logl.dtype == torch.float64 and logl.is_contiguous()
-        form_args = self._slice_form_args(form)
+        form_args = self._slice_glm_form_args(form) if glm else self._slice_form_args(form)
         C, dev = z.shape[0], self.device
         x = torch.empty_like(z)
         n_call = torch.empty(C, dtype=torch.int32, device=dev)
@@ -316,13 +328,40 @@ class _HipFlow(object):
         if noise is not None:
             dz = _as_dev_f32(noise.reshape(-1, self.D), dev)
             assert dz.shape[0] == steps * C
+        t_args = ()
+        if glm:
+            t_std, t_mean, _, _ = target_vectors('slice_steps', dev, t_std, t_mean, None, None, D=self.D)
+            t_args = (_lib.ptr(t_std), _lib.ptr(t_mean))
         with torch.cuda.device(dev):
-            lk = _lib.like_spec(like_id, like_scale, like_params)
-            _lib.check(fn(self._h, ctypes.byref(lk), _lib.ptr(z), _lib.ptr(x), _lib.ptr(logl), float(loglstar), float(width), int(steps), C,
-                          int(max_stepout), int(max_shrink), *form_args, _lib.ptr(dz), int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset),
-                          _lib.ptr(hx), _lib.ptr(n_call), _lib.ptr(n_move), _lib.ptr(n_eval), _lib.current_stream(dev)))
+            if glm:
+                lk, keep = glm_spec(like_glm, dev)   # (`keep`: the staged arrays, alive until the call has been enqueued)
+            else:
+                lk = _lib.like_spec(like_id, like_scale, like_params)
+            _lib.check(fn(self._h, ctypes.byref(lk), *t_args, _lib.ptr(z), _lib.ptr(x), _lib.ptr(logl), float(loglstar), float(width),
+                          int(steps), C, int(max_stepout), int(max_shrink), *form_args, _lib.ptr(dz), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                          int(walker_offset), _lib.ptr(hx), _lib.ptr(n_call), _lib.ptr(n_move), _lib.ptr(n_eval), _lib.current_stream(dev)))
         n_move, moved = split_move_word(n_move)
         return dict(x=x, n_call=n_call, n_move=n_move, moved=moved, n_eval=n_eval, hist_x=hx)
+
+    def slice_glm_refusal(self, D=None):
+        """why `slice_steps` with a like_glm of dimension D (None: the flow's own) would refuse this flow (its shape) -- the library's
+        own words (the family's `slice_glm_check` entry; nothing is launched) --, or None where it is taken.  NotImplementedError
+        for a family without such a kernel"""
+        fn = self._sym.get('slice_glm_check')
+        if fn is None or 'slice_glm' not in self._sym:
+            raise NotImplementedError('no fused slice kernel for %s on a regression likelihood of user data' % type(self).__name__)
+        with torch.cuda.device(self.device):
+            rc = fn(self._h, self.D if D is None else int(D))
+        if rc == _lib.NNEST_OK:
+            return None
+        msg = self._lib.nnest_hip_last_error()
+        return msg.decode() if msg else 'error %d' % rc
+
+    def _slice_glm_form_args(self, form):
+        """`_slice_form_args` for the family's `slice_glm` entry point: nothing, and one form"""
+        if form is not None:
+            raise ValueError('form=%r: %s has one slice kernel form on a regression likelihood of user data' % (form, type(self).__name__))
+        return ()
 
     def _slice_form_args(self, form):
         """what the family's slice entry point takes between max_shrink and noise_dz_dev: nothing, for a kernel with one form"""
@@ -929,7 +968,8 @@ class HipNVP(_PaddedVectors, _HipFlow):
                    mcmc_mixed_check='nnest_mcmc_mixed_check', mcmc_adapt='nnest_mcmc_adapt_steps',
                    mcmc_adapt_check='nnest_mcmc_adapt_check', mcmc_gdata='nnest_mcmc_gdata_steps',
                    mcmc_gdata_check='nnest_mcmc_gdata_check', mcmc_glm='nnest_mcmc_glm_steps',
-                   mcmc_glm_check='nnest_mcmc_glm_check', mcmc_glm_prior='nnest_mcmc_glm_prior_steps',
+                   mcmc_glm_check='nnest_mcmc_glm_check', slice_glm='nnest_slice_glm_steps',
+                   slice_glm_check='nnest_slice_glm_check', mcmc_glm_prior='nnest_mcmc_glm_prior_steps',
                    mcmc_glm_prior_check='nnest_mcmc_glm_prior_check', importance_glm='nnest_importance_glm_evidence',
                    importance_glm_check='nnest_importance_glm_check')
         self._h = ctypes.c_void_p()

@@ -19,6 +19,12 @@ text -- O(n^2) over a run, 995 s of a 15 s GPU run).  Here a checkpoint writes t
 saved_*.npy (GrowingNpy: the same files, valid .npy at any time), so it costs ~1 ms; it is taken at the reference's cadence but
 at most once per `checkpoint_min_seconds` (default 2; 0 = exactly the reference's cadence and file set), and chain.txt -- a
 derived product -- is rewritten at most once per `chain_min_seconds` (default 30) and at the end.
+
+A regression likelihood of user data (likelihoods.GLMData) under mcmc_proposal='slice' and a transform x -> s * x runs its MCMC batches
+on the device: the fused slice kernels of that likelihood (nnest_slice_glm_steps, nnest_spline_slice_glm_steps) where they take the
+flow's shape, nnest_amd.slice_rounds with the device likelihood otherwise (`slice_route`: 'fused-glm' / 'rounds-glm').  The initial
+live points, the prior-rejection phase and the loops around the batches keep the host callable.  With mcmc_proposal='mh', or under
+a GaussianPrior (a Sampler's prior, not this class's unit box), a GLMData stays on the host protocol.
 """
 import csv
 import glob
@@ -460,7 +466,7 @@ class NestedSampler(Sampler):
                     my = ctl[lo:lo + per]
                     kw = dict(init_samples=active_u[my, :], init_loglikes=active_logl[my], loglstar=st.loglstar,
                               walker_offset=lo, seed=int(ctl[-1]), form=self._pinned_form(C, dynamic))
-                    if self._fused_like_id is not None and nd == 0:
+                    if (self._fused_like_id is not None or self._slice_glm is not None) and nd == 0:
                         ends, scale, nc = self._mcmc_endpoints_fused(mcmc_steps, step_size, dynamic, **kw)
                     else:
                         s_x, _lat, s_d, s_l, scale, nc = self._mcmc_sample(
@@ -772,7 +778,8 @@ class NestedSampler(Sampler):
                     # what the loop below consumes of a chain is its last x, the last logL and whether every coordinate moved
                     # (+ derived): one row [x_S | logL_S | moved | derived_S] per chain, all-gathered over the ranks (C2) -- on
                     # device memory when the whole batch ran inside the HIP kernel
-                    if self._fused_like_id is not None and nd == 0:
+                    # (or, under the slice proposal, on a regression likelihood of user data: Sampler._slice_glm)
+                    if (self._fused_like_id is not None or self._slice_glm is not None) and nd == 0:
                         ends, scale, nc = self._mcmc_endpoints_fused(mcmc_steps, step_size, mcmc_dynamic_step_size, **kw)
                     else:
                         s_x, _lat, s_d, s_l, scale, nc = self._mcmc_sample(

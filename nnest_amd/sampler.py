@@ -74,7 +74,9 @@ class Sampler(object):
         # 'mh' = that step; 'slice' = the build-defined slice proposal in latent space (BASELINE north_star; include/nnest_hip.h,
         # parity unpinned) under the hard constraint logL > L*, with every flow and every likelihood: the fused kernels
         # (nnest_slice_steps, nnest_spline_slice_steps) where they take the flow and the likelihood is a known id, the round driver
-        # nnest_amd.slice_rounds otherwise (other flows and shapes; a user likelihood, derived parameters or another prior)
+        # nnest_amd.slice_rounds otherwise (other flows and shapes; a user likelihood, derived parameters or another prior).  A
+        # likelihoods.GLMData under the unit box on x and x -> s * x runs on the device too: the fused kernels of that likelihood
+        # (nnest_slice_glm_steps, nnest_spline_slice_glm_steps) where they take the flow, slice_rounds(like_glm=...) otherwise
         if mcmc_proposal not in ('mh', 'slice'):
             raise ValueError("mcmc_proposal=%r: 'mh' (the reference's step) or 'slice' (build-defined)" % (mcmc_proposal,))
         self.mcmc_proposal = mcmc_proposal
@@ -160,6 +162,11 @@ class Sampler(object):
         self._fused_like_params = ()
         if fused:
             self._fused_like_id = self._fused_eligibility()
+        # the slice proposal on a regression likelihood of user data (likelihoods.GLMData): its device target, resolved once, or None
+        self._slice_glm = None
+        self.slice_route = None   # 'fused-glm' | 'rounds-glm' | 'fused' | 'rounds' | 'host': what the last slice batch ran, logged once
+        if fused and mcmc_proposal == 'slice' and self._fused_like_id is None and getattr(self.trainer, 'netG', None) is not None:
+            self._slice_glm, _ = self._device_target(unit_box_on_x=True, entry='slice_glm')
 
     # ---- the user's callables behind shape checks (sampler.py:97-163) ----------------------------------------------
     def _rows(self, x):
@@ -330,25 +337,50 @@ class Sampler(object):
         population and the kernels know the likelihood (netG.slice_steps), else -- or with rounds=True, for a caller that needs
         hist_z / hist_logl -- nnest_amd.slice_rounds: the device likelihood when the kernels know it, else the host protocol
         (self.loglike on the rows whose likelihood decides, so it counts exactly sum n_call calls itself; the prior in place of the
-        box unless it is the unit box).  Initial bracket: twice the Metropolis step.  Books total_calls / total_accepted /
+        box unless it is the unit box).  With a device target for a regression likelihood of user data (`_slice_glm`): the fused
+        kernel of that likelihood where the flow's `slice_glm_refusal` is None, else slice_rounds(like_glm=...); either way the rows
+        stay on the device.  `slice_route` names what ran.  Initial bracket: twice the Metropolis step.  Books total_calls / total_accepted /
         total_rejected; returns (res, ncall).  One small device-to-host copy for the counts."""
         netG = self.trainer.netG
         C = z.shape[0]
         kw = dict(seed=self._next_seed() if seed is None else seed, walker_offset=walker_offset, history=history)
         args = (z, logl, float(loglstar), 2.0 * float(step_size), int(mcmc_steps))
         fused_slice = getattr(netG, 'supports_fused_slice', None)
-        if self._fused_like_id is None:
+        glm = self._slice_glm if self._fused_like_id is None else None
+        if glm is not None:
+            tk = glm.launch_kwargs(netG.device)
+            tk = dict(like_glm=tk['like_glm'], t_std=tk['t_std'], t_mean=tk['t_mean'])
+            refusal = getattr(netG, 'slice_glm_refusal', None)
+            try:
+                fused_glm = not rounds and refusal is not None and refusal(self.x_dim) is None
+            except NotImplementedError:   # (a family without such a kernel)
+                fused_glm = False
+            if fused_glm:
+                route = 'fused-glm'
+                res = netG.slice_steps(None, 1.0, *args, **tk, **kw)
+            else:
+                from .slice_rounds import slice_rounds
+                route = 'rounds-glm'
+                res = slice_rounds(netG, *args, **tk, **kw)
+        elif self._fused_like_id is None:
             from .slice_rounds import slice_rounds
+            route = 'host'
             prior = None if self._unit_box_on_x() else (lambda x: self.prior(x) > -1e30)
             res = slice_rounds(netG, *args, loglike=self.loglike, prior=prior, num_derived=self.num_derived, init_derived=init_derived, **kw)
         elif rounds or (fused_slice is not None and not fused_slice(C)):
             from .slice_rounds import slice_rounds
+            route = 'rounds'
             res = slice_rounds(netG, *args, like_id=self._fused_like_id, like_scale=self._linear_scale, like_params=self._fused_like_params, **kw)
         else:
+            route = 'fused'
             res = netG.slice_steps(self._fused_like_id, self._linear_scale, *args, like_params=self._fused_like_params, **kw)
+        if route != self.slice_route:
+            self.slice_route = route
+            if self.single_or_primary_process:
+                self.logger.info('slice proposal route [%s]' % route)
         counts = torch.stack([res['n_call'].sum(), res['n_move'].sum()]).cpu()
         ncall, nmove = int(counts[0]), int(counts[1])
-        if self._fused_like_id is not None:
+        if self._fused_like_id is not None or glm is not None:   # (a device likelihood: the host callable did not count these)
             self.total_calls += ncall
         self.total_accepted += nmove
         self.total_rejected += C * int(mcmc_steps) - nmove
@@ -805,7 +837,9 @@ class Sampler(object):
         entries (GDATA_ENTRIES) where the flow's `mcmc_gdata` entry is bound and takes the flow (`mcmc_gdata_refusal`) and the
         descriptor agrees with the host callable (`_probe_agrees_gdata`): the target then has like_id None and the data.  Likewise
         a likelihood with a `hip_like_glm` (likelihoods.GLMData): the flow's `mcmc_glm` entry, `mcmc_glm_refusal`,
-        `_probe_agrees_glm`.  Beside such a likelihood, and only there, a priors.GaussianPrior on T(x) whose `__call__` is its own
+        `_probe_agrees_glm`.  Entry 'slice_glm' (the NestedSampler's slice proposal; `unit_box_on_x` goes with it) takes such a
+        likelihood, and nothing else, under mcmc_proposal='slice', the unit box on x and x -> s * x, with any flow and fast/slow
+        parameters too: `_slice_batch` chooses between the fused kernel and the round driver.  Beside such a likelihood, and only there, a priors.GaussianPrior on T(x) whose `__call__` is its own
         is taken where the flow binds `mcmc_glm_prior` and takes the shape (`mcmc_glm_prior_refusal`) and the prior's
         `hip_gauss_prior` agrees with its callable (`_probe_agrees_gauss_prior`): the target then carries `prior_gauss` and no box.
         With any other likelihood, entry or flow a GaussianPrior stays a Python prior: refused here, the host route's.
@@ -818,7 +852,7 @@ class Sampler(object):
         netG = self.trainer.netG
         if self.num_derived != 0:
             return None, 'derived parameters (num_derived=%d)' % self.num_derived
-        if entry is not None and self.num_slow != 0:
+        if entry not in (None, 'slice_glm') and self.num_slow != 0:   # (the slice proposal's round driver takes any flow)
             return None, 'the fast/slow proposal (num_slow=%d)' % self.num_slow
         for need in self.ENTRY_NEEDS.get(entry, ()):
             if need not in getattr(netG, '_sym', ()):
@@ -836,14 +870,23 @@ class Sampler(object):
             proper = (gauss_own or (unit_box_on_x and self._unit_box_on_x() and self._linear_scale is not None)
                       or (self._transform_prior and isinstance(prior, UniformPrior) and type(prior).__call__ is UniformPrior.__call__))
             glm_evidence = proper and 'importance_glm' in getattr(netG, '_sym', ())
-        if like_glm is not None and not glm_evidence and not (entry in self.GDATA_ENTRIES and 'mcmc_glm' in getattr(netG, '_sym', ())):
+        # (the slice proposal on a regression: the NestedSampler's prior, the unit box on x under x -> s * x.  Any flow: the fused kernel
+        # or the round driver is `_slice_batch`'s choice, batch by batch)
+        glm_slice = (entry == 'slice_glm' and like_glm is not None and self.mcmc_proposal == 'slice' and self._unit_box_on_x()
+                     and self._linear_scale is not None)
+        if entry == 'slice_glm' and not glm_slice:
+            return None, ("anything but mcmc_proposal='slice' on a likelihood with a hip_like_glm (likelihoods.GLMData) under the unit box on x and "
+                          "x -> s * x")
+        if like_glm is not None and not glm_evidence and not glm_slice and not (entry in self.GDATA_ENTRIES and 'mcmc_glm' in getattr(netG, '_sym', ())):
             like_glm = None
         if like_id is None and like_data is None and like_glm is None:
             return None, 'a likelihood the kernels do not know (a Python callable)'
         prior_gauss = None   # (normal priors: beside a regression likelihood of user data only)
         if like_glm is not None and gauss_own and (glm_evidence or 'mcmc_glm_prior' in getattr(netG, '_sym', ())):
             prior_gauss = prior.hip_gauss_prior
-        if like_glm is not None:   # (as below for like_data: one kernel per flow and family serves the four entries)
+        if glm_slice:
+            entry = None
+        elif like_glm is not None:   # (as below for like_data: one kernel per flow and family serves the four entries)
             ask = netG.importance_glm_refusal if glm_evidence else netG.mcmc_glm_refusal if prior_gauss is None else netG.mcmc_glm_prior_refusal
             why = ask(np.shape(like_glm['at'])[0])
             if why is not None:
@@ -880,7 +923,7 @@ class Sampler(object):
             box = (prior.minimum, prior.maximum) if ok else None
         params = tuple(getattr(like, 'hip_like_params', ()) or ())
         if like_glm is not None:
-            if affine is None or box is None or not self._probe_agrees_glm(like_glm, affine, warn='mcmc: '):
+            if affine is None or box is None or not self._probe_agrees_glm(like_glm, affine, warn='slice: ' if glm_slice else 'mcmc: '):
                 return None, refused
             if prior_gauss is not None and (box != (None, None) or not self._probe_agrees_gauss_prior(prior_gauss, affine, warn='mcmc: ')):
                 return None, refused
@@ -899,6 +942,7 @@ class Sampler(object):
         self._ensemble_transform = (np.asarray(std, np.float64), np.asarray(mean, np.float64))
         self._linear_scale = None   # (the Metropolis kernels only know x -> s * x)
         self._fused_like_id = None
+        self._slice_glm = None
 
     # ---- importance-sampled evidence from the trained flow (build-defined: the reference has none) ---------------------------------
     IMPORTANCE_CHUNK = 1 << 22   # samples per launch when nothing per sample comes back

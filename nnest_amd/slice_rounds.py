@@ -6,7 +6,8 @@ keep running where they apply.  Here each walker's slice state machine lives on 
 
 1. the flow's own `inverse` maps every walker's candidate (NVP of any shape, spline, MAF, Cholesky, fast/slow);
 2. a screen kernel tests the box and the slice level and packs the rows that need a likelihood, in ascending walker order;
-3. the likelihood is evaluated on those rows only: a host callable, or the device likelihood kernel (nnest_loglike) for a known id;
+3. the likelihood is evaluated on those rows only: a host callable, the device likelihood kernel (nnest_loglike) for a known id, or
+   the regression likelihood of user data on the device (nnest_loglike_glm on T(rows)) for a `like_glm`;
 4. an advance kernel consumes the results and writes the next candidates.
 
 One small device-to-host copy per round tells the host how many rows to evaluate and whether any walker is still live.
@@ -18,6 +19,7 @@ import torch
 
 from . import _lib
 from . import flow as _flow
+from .device_target import affine_on_device
 
 _HANDLES = {}
 _MAX_HANDLES = 4
@@ -62,7 +64,8 @@ def _handle(lib, dev, C, D, steps):
 
 
 def slice_rounds(flow, z, logl, loglstar, width, steps, loglike=None, like_id=None, like_scale=1.0, like_params=None, prior=None,
-                 num_derived=0, init_derived=None, max_stepout=8, max_shrink=32, noise=None, seed=0, walker_offset=0, history=False):
+                 num_derived=0, init_derived=None, max_stepout=8, max_shrink=32, noise=None, seed=0, walker_offset=0, history=False,
+                 like_glm=None, t_std=None, t_mean=None):
     """`steps` slice-sampling updates of every walker (stepping out + shrinkage along a random direction of latent space) under the
     hard constraint logL > loglstar, of the target |det dx/dz| on {x(z) in the prior, logL(x(z)) > loglstar}.  With a fast/slow flow
     the directions span all coordinates (there are no fast-only updates).
@@ -72,17 +75,25 @@ def slice_rounds(flow, z, logl, loglstar, width, steps, loglike=None, like_id=No
     The likelihood, exactly one of:
       loglike(x [n, D] float32 numpy) -> logl [n] (or (logl, derived [n, num_derived])), called only on the rows whose likelihood
           decides (never with zero rows); non-finite values count as -1e100;
-      like_id (NNEST_LIKE_*, with like_scale / like_params): the device likelihood kernel, the rows never leave the device.
+      like_id (NNEST_LIKE_*, with like_scale / like_params): the device likelihood kernel, the rows never leave the device;
+      like_glm (the descriptor of a regression likelihood of user data, likelihoods.GLMData.hip_like_glm): logL = GLM(T(row)) with
+          T(x) = x * t_std + t_mean per dimension in float32 (affine_on_device; t_std / t_mean [D], both or neither, None: the
+          identity) through flow.loglike_glm, the rows never leave the device -- the definition of nnest_slice_glm_steps for the
+          flows and shapes its kernels do not take.  The box stays on x.
     prior: None = the unit box on the device; else a host callable x [C, D] -> bool [C] (inside the prior) applied to every candidate
         in place of the box (host-callable route only; every candidate row is copied back for it).
     init_derived [C, num_derived]: the starting points' derived parameters (host-callable route).
     noise: recorded directions dz [steps, C, D] (fill_slice_noise exports the in-kernel ones for (seed, walker_offset)).
     Returns x, n_call (rows evaluated), n_move, moved (every coordinate of x changed: nested.py:432), n_eval (candidates), hist_x,
     plus hist_z, hist_logl (history=True), derived [C, num_derived] and hist_derived (numpy; None without num_derived), rounds."""
-    if (loglike is None) == (like_id is None):
-        raise ValueError('slice_rounds: give exactly one of loglike (host callable) and like_id (device likelihood)')
-    if like_id is not None and (prior is not None or num_derived):
+    if (loglike is not None) + (like_id is not None) + (like_glm is not None) != 1:
+        raise ValueError('slice_rounds: give exactly one of loglike (host callable), like_id (device likelihood) and like_glm (regression '
+                         'likelihood of user data on the device)')
+    on_device = like_id is not None or like_glm is not None
+    if on_device and (prior is not None or num_derived):
         raise ValueError('slice_rounds: the device likelihood runs in the unit box without derived parameters')
+    if like_glm is None and (t_std is not None or t_mean is not None):
+        raise ValueError('slice_rounds: t_std and t_mean go only with a like_glm')
     assert z.is_cuda and z.dtype == torch.float32 and z.is_contiguous() and z.dim() == 2
     assert logl.is_cuda and logl.dtype == torch.float64 and logl.is_contiguous()
     dev = z.device
@@ -95,6 +106,10 @@ def slice_rounds(flow, z, logl, loglstar, width, steps, loglike=None, like_id=No
         stream = torch.cuda.current_stream(dev)
         sp = _lib.current_stream(dev)
         h = _handle(lib, dev, C, D, steps)
+        if like_glm is not None:   # (staged once for the batch's rounds)
+            t_std, t_mean, _, _ = _flow.target_vectors('slice_rounds', dev, t_std, t_mean, None, None, D=D)
+            _, (at, y, o) = _flow.glm_spec(like_glm, dev)
+            like_glm = dict(like_glm, at=at, y=y, o=o)
         x0, ld0 = flow.inverse(z)
         hx = torch.empty(C, steps + 1, D, dtype=torch.float32, device=dev) if history else None
         hz = torch.empty(C, steps + 1, D, dtype=torch.float32, device=dev) if history else None
@@ -134,6 +149,9 @@ def slice_rounds(flow, z, logl, loglstar, width, steps, loglike=None, like_id=No
             lrows = h.logl_rows
             if n_rows and like_id is not None:
                 lrows = _flow.loglike(like_id, h.rows[:n_rows], like_scale, device=dev, like_params=like_params)
+            elif n_rows and like_glm is not None:
+                rows = h.rows[:n_rows]
+                lrows = _flow.loglike_glm(like_glm, rows if t_std is None else affine_on_device(rows, t_std, t_mean), device=dev)
             elif n_rows:
                 xr = h.down[2:2 + n_rows * D].view(n_rows, D)
                 xr.copy_(h.rows[:n_rows], non_blocking=True)

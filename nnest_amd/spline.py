@@ -41,6 +41,7 @@ class HipSpline(_PaddedVectors, _HipFlow):
                    mcmc_adapt='nnest_spline_mcmc_adapt_steps', mcmc_adapt_check='nnest_spline_mcmc_adapt_check',
                    mcmc_gdata='nnest_spline_mcmc_gdata_steps', mcmc_gdata_check='nnest_spline_mcmc_gdata_check',
                    mcmc_glm='nnest_spline_mcmc_glm_steps', mcmc_glm_check='nnest_spline_mcmc_glm_check',
+                   slice_glm='nnest_spline_slice_glm_steps', slice_glm_check='nnest_spline_slice_glm_check',
                    mcmc_glm_prior='nnest_spline_mcmc_glm_prior_steps', mcmc_glm_prior_check='nnest_spline_mcmc_glm_prior_check',
                    importance_glm='nnest_spline_importance_glm_evidence', importance_glm_check='nnest_spline_importance_glm_check')
         self._h = ctypes.c_void_p()
@@ -87,6 +88,13 @@ class HipSpline(_PaddedVectors, _HipFlow):
 
     def _slice_form_args(self, form):
         return (self._slice_flags(form),)
+
+    def _slice_glm_form_args(self, form):
+        """nnest_spline_slice_glm_steps takes no flags word: the team tile is its only form (glm_tile_loglike needs the whole workgroup)"""
+        if form not in (None, 'team'):
+            raise ValueError("form=%r: the spline flow's slice kernel on a regression likelihood of user data has the team form only "
+                             "(None or 'team')" % (form,))
+        return ()
 
     # the spline flow's slice proposal: the shared method on this family's entry point (`slice` in _bind above) with the flags word of
     # _slice_form_args -- form: None (by population) | 'wave' | 'team' | 'pair'.  Named here so that the class says it has one
