@@ -992,6 +992,41 @@ int nnest_spline_slice_glm_steps(struct nnest_spline *spl, const nnest_glm_t *gl
                                  float *z_dev, float *x_dev, double *logl_dev, double loglstar, float width, int steps, int C,
                                  int max_stepout, int max_shrink, const float *noise_dz_dev, uint64_t seed, uint64_t walker_offset,
                                  float *hist_x_dev, int *n_call_dev, int *n_move_dev, int *n_eval_dev, void *stream);
+
+/* METROPOLIS PROPOSAL ON A REGRESSION: nnest_mh_constrained_steps's hard-constraint step (sampler.py:229-463) -- fs = (float)scale,
+ * z' = z + eps * fs in float32 (a product and a sum), x' = f^-1(z'), log_ratio = inbox(x') ? ld' - ld : -inf, ratio =
+ * min(exp(log_ratio), 1) with a NaN kept, pre = u < ratio, acc = pre && logL' > loglstar; n_call_dev counts pre, n_accept_dev counts acc
+ * with NNEST_MH_ALL_MOVED in bit 30 -- with the likelihood of a nnest_glm_t (above: float32 eta in the layout's own order, float64
+ * terms, rows >= n masked, the safe rule -1e100) compiled in, one kernel per flow and family.  BUILD-DEFINED.
+ *   logL(x) := GLM(T(x)), T(x)_d = x_d * t_std[d] + t_mean[d] in float32 without contraction (t_std_dev / t_mean_dev [D], both or
+ *     neither; NULL: the identity).  The box is on x (!(x < -1 || x > 1), a NaN coordinate inside) -- not on T(x).
+ *   Draws: eps[4g .. 4g+3] = Philox normals of (seed, walker_offset + row, step 1.., g) on stream DZ (what nnest_slice_fill_noise
+ *     exports), padded dimensions exactly 0; u = the Philox uniform of (seed, walker, step) on stream U (24 bits).  A chain is a
+ *     function of seed, walker and step (and of the votes under a step rule).  noise_dz_dev [steps, C, D] and noise_u_dev [steps, C],
+ *     both or neither, replace them.  hist_x_dev [C, steps + 1, D], hist_logl_dev [C, steps + 1]: optional.
+ *   The likelihood is not evaluated where nothing reads it: a proposal with pre false is rejected whatever its logL (the spline tile
+ *     skips only where none of its 16 walkers has pre).  No output shows it.
+ *   flags: 0 (fixed step) | NNEST_MH_DYNAMIC_BATCH | NNEST_MH_LAG(0..15) (the reference's rule over all C walkers; the vote of step s
+ *     applies from step s + 1 + lag on; sync_dev: nnest_mh_sync_words(steps) words, ZERO at the launch, the last one the error word
+ *     of a bounded wait that ran out) | NNEST_MH_DYNAMIC_STEP, the spline entry only (the rule per 16-walker tile, any C).  Anything
+ *     else -- NNEST_MH_UNCONSTRAINED (that walk is nnest_mcmc_glm_steps), NNEST_MH_WARM, form bits, the sync halves -- is NNEST_E_ARG.
+ *   The batch rule needs every workgroup resident: a grid beyond the kernel's occupancy times the device's CUs is refused with
+ *     NNEST_E_UNSUPPORTED and nothing is launched.  scale_out_dev: one float per workgroup (4 walkers: the NVP; 16: the spline flow).
+ * The descriptor is checked as everywhere (NNEST_E_ARG).  The NVP runs one walker per wave (hidden 16, 3 blocks, 1 layer, scale '',
+ * x_dim <= 128), the spline flow its team tile.  nnest_mh_glm_check, nnest_spline_mh_glm_check: NNEST_OK where the entry takes this
+ * handle's shape, a descriptor of dimension D, C walkers and this flags word (the residency verdict included), else the code and
+ * the reason in nnest_hip_last_error; nothing is launched.  (All added within ABI 15.) */
+int nnest_mh_glm_check(nnest_nvp_t *nvp, int D, int C, int flags);
+int nnest_spline_mh_glm_check(struct nnest_spline *spl, int D, int C, int flags);
+int nnest_mh_glm_steps(nnest_nvp_t *nvp, const nnest_glm_t *glm, const float *t_std_dev, const float *t_mean_dev, float *z_dev,
+                       float *x_dev, double *logl_dev, double loglstar, float step_size, int steps, int C, int flags,
+                       const float *noise_dz_dev, const float *noise_u_dev, uint64_t seed, uint64_t walker_offset, float *hist_x_dev,
+                       double *hist_logl_dev, int *n_accept_dev, int *n_call_dev, float *scale_out_dev, void *sync_dev, void *stream);
+int nnest_spline_mh_glm_steps(struct nnest_spline *spl, const nnest_glm_t *glm, const float *t_std_dev, const float *t_mean_dev,
+                              float *z_dev, float *x_dev, double *logl_dev, double loglstar, float step_size, int steps, int C,
+                              int flags, const float *noise_dz_dev, const float *noise_u_dev, uint64_t seed, uint64_t walker_offset,
+                              float *hist_x_dev, double *hist_logl_dev, int *n_accept_dev, int *n_call_dev, float *scale_out_dev,
+                              void *sync_dev, void *stream);
 /* size of sync_dev in 8-byte words for a launch of `steps` steps */
 int nnest_mh_sync_words(int steps);
 /* number of adaptation groups nnest_mh_constrained_steps uses for C walkers (size of scale_out_dev) */

@@ -287,6 +287,12 @@ SIGNATURES = {
     'nnest_spline_slice_glm_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _f, _i, _i, _i, _i, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp],
     'nnest_slice_glm_check': [_vp, _i],
     'nnest_spline_slice_glm_check': [_vp, _i],
+    # the constrained Metropolis proposal on them: nnest_mh_constrained_steps's arguments with `const nnest_glm_t *glm, const float
+    # *t_std_dev, const float *t_mean_dev` for `like`; (handle, D, C, flags)
+    'nnest_mh_glm_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _f, _i, _i, _i, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'nnest_spline_mh_glm_steps': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _f, _i, _i, _i, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'nnest_mh_glm_check': [_vp, _i, _i, _i],
+    'nnest_spline_mh_glm_check': [_vp, _i, _i, _i],
     # their pointwise predictive statistics: (S, n); (glm, t_dev, stats_dev, partials_dev, S, D, stream)
     'nnest_glm_pointwise_groups': [_i, _i],
     'nnest_glm_pointwise': [_vp, _vp, _vp, _vp, _i, _i, _vp],

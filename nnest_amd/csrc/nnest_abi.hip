@@ -20,6 +20,8 @@
 #include "importance_glm.h"
 #include "glm_newton.h"
 #include "slice_glm.h"
+#include <limits.h>
+#include "mh_glm.h"
 
 using namespace nnest;
 
@@ -924,6 +926,67 @@ int nnest_slice_glm_steps(nnest_nvp_t *h, const nnest_glm_t *glm, const float *t
     hipError_t e = launch_slice_glm(h->s, h->w, a, (hipStream_t)stream);
     if (e == hipErrorInvalidConfiguration) return fail(NNEST_E_UNSUPPORTED, "slice glm: x_dim=%d not instantiated", h->s.D);
     if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_slice_glm: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+// what nnest_mh_glm_steps takes, asked before a launch (and by the entry itself): the flags' three settings less the per-tile rule, the
+// shapes of nnest_slice_steps, a descriptor of the flow's x_dim, and -- under the batch rule -- a grid that is proven resident
+int nnest_mh_glm_check(nnest_nvp_t *h, int D, int C, int flags) {
+    if (!h) return fail(NNEST_E_ARG, "NULL handle");
+    if (!mh_glm_flags_ok(flags, false))
+        return fail(NNEST_E_ARG, "mh glm: flags 0x%x: 0 (fixed step) or NNEST_MH_DYNAMIC_BATCH | NNEST_MH_LAG(0..15); the unconstrained walk is "
+                    "nnest_mcmc_glm_steps, one walker per wave has no per-tile rule, and there are no forms, warm-up steps or sync halves", flags);
+    if (!slice_form_eligible(h->s))
+        return fail(NNEST_E_UNSUPPORTED, "mh glm: x_dim=%d hidden=%d blocks=%d layers=%d scale mode %d: the kernel takes hidden 16, 3 blocks, "
+                    "1 layer, scale '' (the one-walker-per-wave layout), x_dim <= 128", h->s.D, h->s.H, h->s.B, h->s.L, h->s.scale_mode);
+    if (D != h->s.D) return fail(NNEST_E_ARG, "mh glm: the likelihood's D=%d is not the flow's x_dim=%d", D, h->s.D);
+    if (C < 0) return fail(NNEST_E_ARG, "mh glm: C=%d < 0", C);
+    if (flags & NNEST_MH_DYNAMIC_BATCH) {   // (the smaller of the two families' grids: the verdict holds for either)
+        int cap = INT_MAX;
+        for (int fam : {GLM_LOGISTIC, GLM_POISSON}) {
+            MhGlmArgs probe;
+            memset(&probe, 0, sizeof(probe));
+            probe.gl.family = fam;
+            int c = 0;
+            hipError_t e = launch_mh_glm(h->s, h->w, probe, h->num_cu, &c, nullptr);
+            if (e != hipSuccess) return fail(NNEST_E_HIP, "mh glm: occupancy query: %s", hipGetErrorString(e));
+            cap = c < cap ? c : cap;
+        }
+        if ((C + 3) / 4 > cap)
+            return fail(NNEST_E_UNSUPPORTED, "mh glm: the batch-wide step rule needs every workgroup resident: C=%d walkers are %d workgroups, "
+                        "%d fit this device", C, (C + 3) / 4, cap);
+    }
+    return NNEST_OK;
+}
+
+// the constrained Metropolis proposal on the regression likelihoods of the user's data (nnest_mh_glm.hip); the argument checks of
+// nnest_mh_constrained_steps and glm_ok (those that need no handle come first)
+int nnest_mh_glm_steps(nnest_nvp_t *h, const nnest_glm_t *glm, const float *t_std_dev, const float *t_mean_dev, float *z_dev, float *x_dev,
+                       double *logl_dev, double loglstar, float step_size, int steps, int C, int flags, const float *noise_dz_dev,
+                       const float *noise_u_dev, uint64_t seed, uint64_t walker_offset, float *hist_x_dev, double *hist_logl_dev,
+                       int *n_accept_dev, int *n_call_dev, float *scale_out_dev, void *sync_dev, void *stream) {
+    MhGlmArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc;
+    if ((rc = glm_ok(glm, glm ? glm->D : 0, &a.gl))) return rc;
+    if (!t_std_dev != !t_mean_dev) return fail(NNEST_E_ARG, "t_std_dev and t_mean_dev: both or neither");
+    if (steps < 0) return fail(NNEST_E_ARG, "steps=%d < 0", steps);
+    if ((noise_dz_dev == nullptr) != (noise_u_dev == nullptr))
+        return fail(NNEST_E_ARG, "noise_dz_dev and noise_u_dev must both be given or both be NULL");
+    if ((rc = check_rows(h, z_dev, logl_dev, C))) return rc;
+    if ((rc = nnest_mh_glm_check(h, a.gl.D, C, flags))) return rc;
+    if ((flags & NNEST_MH_DYNAMIC_BATCH) && !sync_dev) return fail(NNEST_E_ARG, "NNEST_MH_DYNAMIC_BATCH needs sync_dev");
+    a.z = z_dev; a.x = x_dev; a.logl = logl_dev; a.loglstar = loglstar; a.step_size = step_size; a.steps = steps; a.C = C; a.flags = flags;
+    a.like.scale = 1.0f; a.noise_dz = noise_dz_dev; a.noise_u = noise_u_dev; a.seed = seed; a.walker_offset = walker_offset;
+    a.hist_x = hist_x_dev; a.hist_logl = hist_logl_dev; a.n_accept = n_accept_dev; a.n_call = n_call_dev; a.scale_out = scale_out_dev;
+    a.sync = (flags & NNEST_MH_DYNAMIC_BATCH) ? (unsigned long long *)sync_dev : nullptr;
+    a.sync_err = a.sync ? reinterpret_cast<int *>(a.sync + mh_sync_words(steps)) : nullptr;   // the word behind the counters
+    a.t_std = t_std_dev; a.t_mean = t_mean_dev;
+    hipError_t e = launch_mh_glm(h->s, h->w, a, h->num_cu, nullptr, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(NNEST_E_UNSUPPORTED, "mh glm: x_dim=%d not instantiated", h->s.D);
+    if (e == hipErrorLaunchOutOfResources)
+        return fail(NNEST_E_UNSUPPORTED, "mh glm: the batch-wide step rule needs every workgroup resident: C=%d walkers do not fit this device", C);
+    if (e != hipSuccess) return fail(NNEST_E_HIP, "launch_mh_glm: %s", hipGetErrorString(e));
     return NNEST_OK;
 }
 

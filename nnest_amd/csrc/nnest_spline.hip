@@ -24,6 +24,8 @@
 #include "gauss_prior.h"
 #include "importance_glm.h"
 #include "slice_glm.h"
+#include <limits.h>
+#include "mh_glm.h"
 #include "nnest_internal.h"
 #include "mh_common.h"
 
@@ -709,6 +711,65 @@ int nnest_spline_slice_glm_steps(nnest_spline_t *h, const nnest_glm_t *glm, cons
     a.t_std = t_std_dev; a.t_mean = t_mean_dev;
     const hipError_t e = launch_spline_slice_glm(SplArgs{h->img, h->s}, a, (hipStream_t)stream);
     if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_slice_glm: %s", hipGetErrorString(e));
+    return NNEST_OK;
+}
+
+// what nnest_spline_mh_glm_steps takes, asked before a launch (and by the entry itself): the flags' three settings, the team tile's
+// shapes, a descriptor of the flow's x_dim, and -- under the batch rule -- a grid that is proven resident
+int nnest_spline_mh_glm_check(nnest_spline_t *h, int D, int C, int flags) {
+    if (!h) return spline_fail(NNEST_E_ARG, "NULL handle");
+    if (!mh_glm_flags_ok(flags, true))
+        return spline_fail(NNEST_E_ARG, "spline mh glm: flags 0x%x: 0 (fixed step), NNEST_MH_DYNAMIC_STEP (the rule per 16-walker tile) or "
+                           "NNEST_MH_DYNAMIC_BATCH | NNEST_MH_LAG(0..15); the unconstrained walk is nnest_spline_mcmc_glm_steps, and there are "
+                           "no forms, warm-up steps or sync halves", flags);
+    int cap = INT_MAX;
+    for (int fam : {GLM_LOGISTIC, GLM_POISSON}) {   // (the smaller of the two families' grids: the verdict holds for either)
+        MhGlmArgs probe;
+        memset(&probe, 0, sizeof(probe));
+        probe.gl.family = fam;
+        int c = 0;
+        hipError_t e = launch_spline_mh_glm(SplArgs{h->img, h->s}, probe, h->num_cu, &c, nullptr);
+        if (e == hipErrorInvalidConfiguration)
+            return spline_fail(NNEST_E_UNSUPPORTED, "spline mh glm: x_dim=%d hidden_dim=%d not instantiated (the team tile's shapes)", h->s.D, h->s.H);
+        if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "spline mh glm: occupancy query: %s", hipGetErrorString(e));
+        cap = c < cap ? c : cap;
+    }
+    if (D != h->s.D) return spline_fail(NNEST_E_ARG, "mh glm: the likelihood's D=%d is not the flow's x_dim=%d", D, h->s.D);
+    if (C < 0) return spline_fail(NNEST_E_ARG, "mh glm: C=%d < 0", C);
+    if ((flags & NNEST_MH_DYNAMIC_BATCH) && (C + 15) / 16 > cap)
+        return spline_fail(NNEST_E_UNSUPPORTED, "spline mh glm: the batch-wide step rule needs every workgroup resident: C=%d walkers are %d "
+                           "workgroups, %d fit this device", C, (C + 15) / 16, cap);
+    return NNEST_OK;
+}
+
+// the constrained Metropolis proposal through the spline flow on the regression likelihoods of the user's data
+// (nnest_spline_mh_glm.hip); the argument checks of nnest_mh_glm_steps
+int nnest_spline_mh_glm_steps(nnest_spline_t *h, const nnest_glm_t *glm, const float *t_std_dev, const float *t_mean_dev, float *z_dev,
+                              float *x_dev, double *logl_dev, double loglstar, float step_size, int steps, int C, int flags,
+                              const float *noise_dz_dev, const float *noise_u_dev, uint64_t seed, uint64_t walker_offset, float *hist_x_dev,
+                              double *hist_logl_dev, int *n_accept_dev, int *n_call_dev, float *scale_out_dev, void *sync_dev, void *stream) {
+    MhGlmArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc;
+    if ((rc = glm_ok(glm, glm ? glm->D : 0, &a.gl))) return rc;
+    if (!t_std_dev != !t_mean_dev) return spline_fail(NNEST_E_ARG, "t_std_dev and t_mean_dev: both or neither");
+    if (steps < 0) return spline_fail(NNEST_E_ARG, "steps=%d < 0", steps);
+    if ((noise_dz_dev == nullptr) != (noise_u_dev == nullptr))
+        return spline_fail(NNEST_E_ARG, "noise_dz_dev and noise_u_dev must both be given or both be NULL");
+    if ((rc = scheck_rows(h, z_dev, logl_dev, C))) return rc;
+    if ((rc = nnest_spline_mh_glm_check(h, a.gl.D, C, flags))) return rc;
+    if ((flags & NNEST_MH_DYNAMIC_BATCH) && !sync_dev) return spline_fail(NNEST_E_ARG, "NNEST_MH_DYNAMIC_BATCH needs sync_dev");
+    a.z = z_dev; a.x = x_dev; a.logl = logl_dev; a.loglstar = loglstar; a.step_size = step_size; a.steps = steps; a.C = C; a.flags = flags;
+    a.like.scale = 1.0f; a.noise_dz = noise_dz_dev; a.noise_u = noise_u_dev; a.seed = seed; a.walker_offset = walker_offset;
+    a.hist_x = hist_x_dev; a.hist_logl = hist_logl_dev; a.n_accept = n_accept_dev; a.n_call = n_call_dev; a.scale_out = scale_out_dev;
+    a.sync = (flags & NNEST_MH_DYNAMIC_BATCH) ? (unsigned long long *)sync_dev : nullptr;
+    a.sync_err = a.sync ? reinterpret_cast<int *>(a.sync + mh_sync_words(steps)) : nullptr;   // the word behind the counters
+    a.t_std = t_std_dev; a.t_mean = t_mean_dev;
+    const hipError_t e = launch_spline_mh_glm(SplArgs{h->img, h->s}, a, h->num_cu, nullptr, (hipStream_t)stream);
+    if (e == hipErrorLaunchOutOfResources)
+        return spline_fail(NNEST_E_UNSUPPORTED, "spline mh glm: the batch-wide step rule needs every workgroup resident: C=%d walkers do not fit "
+                           "this device", C);
+    if (e != hipSuccess) return spline_fail(NNEST_E_HIP, "launch_spline_mh_glm: %s", hipGetErrorString(e));
     return NNEST_OK;
 }
 

@@ -225,7 +225,8 @@ class _HipFlow(object):
                                               _lib.current_stream(self.device)))
 
     def mh_steps(self, like_id, like_scale, z, logl, loglstar, step_size, steps, dynamic=False, noise=None, seed=0,
-                 walker_offset=0, history=False, like_params=None, lag=None, form=None, warm=None):
+                 walker_offset=0, history=False, like_params=None, lag=None, form=None, warm=None, like_glm=None, t_std=None,
+                 t_mean=None):
         """K4: `steps` constrained Metropolis steps for all walkers in one launch (Sampler._mcmc_sample,
         sampler.py:229-463).  z [C,D] float32 and logl [C] float64 are updated in place.
         noise = (dz [steps,C,D], u [steps,C]) replays recorded draws; None = in-kernel Philox.
@@ -233,7 +234,19 @@ class _HipFlow(object):
         dynamic: False | True or 'batch' (sampler.py:422-431 over all C walkers; `lag` steps between a step and the
         scale that reflects its count, 0 = the reference exactly) | 'group' (per 16 walkers, shard-invariant).
         warm: with a lagged batch rule, the first `warm` steps apply it exactly (NNEST_MH_WARM); None = default_warm().
-        form: None (by population) | 'solo' | 'quad' | 'team' | 'reg' | 'image' (include/nnest_hip.h NNEST_MH_FORM_*)."""
+        form: None (by population) | 'solo' | 'quad' | 'team' | 'reg' | 'image' (include/nnest_hip.h NNEST_MH_FORM_*).
+        like_glm: None -- the entry above, as it was; the descriptor of a regression likelihood of user data
+        (likelihoods.GLMData.hip_like_glm, as `slice_steps` takes it) -- `like_id` must then be None (ValueError otherwise;
+        like_scale and like_params are not read) and the launch goes through the family's `mh_glm` entry (nnest_mh_glm_steps,
+        nnest_spline_mh_glm_steps): the same step with logL(x) = GLM(T(x)), T(x) = x * t_std + t_mean per dimension (t_std / t_mean
+        [D], both or neither; None: the identity), the box on x, Philox draws per (seed, walker, step).  That entry has the hard
+        constraint only (a loglstar), one form and no warm-up steps; dynamic 'group' is the spline flow's alone.  The result is
+        the same dict.  `mh_glm_refusal` says beforehand whether shape, population and rule are taken."""
+        if like_glm is not None:
+            return self._mh_glm_steps(like_id, like_glm, t_std, t_mean, z, logl, loglstar, step_size, steps, dynamic, noise, seed,
+                                      walker_offset, history, lag, form, warm)
+        if t_std is not None or t_mean is not None:
+            raise ValueError('mh_steps: t_std and t_mean go only with a like_glm (the analytic likelihoods take like_scale)')
         free = loglstar is None or loglstar != loglstar
         loglstar = 0.0 if free else loglstar
         assert z.is_cuda and z.dtype == torch.float32 and z.is_contiguous()
@@ -289,6 +302,68 @@ class _HipFlow(object):
         # (include/nnest_hip.h NNEST_MH_ALL_MOVED): the reference's usable-chain test, nested.py:432
         # (split on first use: two element-wise launches that a caller who reads neither does not pay for)
         return _MhResult(x=x, n_accept_word=n_acc, n_call=n_call, scale=scale_out, hist_x=hx, hist_logl=hl, sync=sync)
+
+    @staticmethod
+    def _mh_glm_flags(dynamic, lag):
+        """the flags word of the `mh_glm` entries: 0, the batch rule with its lag (None: MH_DEFAULT_LAG), or the per-tile rule"""
+        return _lib.mh_flags(dynamic, False, lag, None, 0)
+
+    def _mh_glm_steps(self, like_id, like_glm, t_std, t_mean, z, logl, loglstar, step_size, steps, dynamic, noise, seed, walker_offset,
+                      history, lag, form, warm):
+        """`mh_steps` with a like_glm: the family's `mh_glm` entry"""
+        if like_id is not None:
+            raise ValueError('mh_steps: like_glm goes with like_id=None, got like_id=%r' % (like_id,))
+        if loglstar is None or loglstar != loglstar:
+            raise ValueError('mh_steps: a like_glm runs under the hard constraint only (the unconstrained walk is mcmc_steps)')
+        if form is not None or warm:
+            raise ValueError('mh_steps: form=%r warm=%r: %s has one Metropolis kernel form on a regression likelihood of user data, '
+                             'without warm-up steps' % (form, warm, type(self).__name__))
+        fn = self._sym.get('mh_glm')
+        if fn is None:
+            raise NotImplementedError('no fused Metropolis kernel for %s on a regression likelihood of user data' % type(self).__name__)
+        assert z.is_cuda and z.dtype == torch.float32 and z.is_contiguous()
+        assert logl.is_cuda and logl.dtype == torch.float64 and logl.is_contiguous()
+        C, dev, steps = z.shape[0], self.device, int(steps)
+        x = torch.empty_like(z)
+        n_acc = torch.empty(C, dtype=torch.int32, device=dev)
+        n_call = torch.empty(C, dtype=torch.int32, device=dev)
+        scale_out = torch.empty(max((C + self.MH_GLM_WALKERS_PER_WORKGROUP - 1) // self.MH_GLM_WALKERS_PER_WORKGROUP, 1),
+                                dtype=torch.float32, device=dev)
+        hx = torch.empty(C, steps + 1, self.D, dtype=torch.float32, device=dev) if history else None
+        hl = torch.empty(C, steps + 1, dtype=torch.float64, device=dev) if history else None
+        dz = u = None
+        if noise is not None:
+            dz = _as_dev_f32(noise[0].reshape(-1, self.D), dev)
+            u = noise[1].to(device=dev, dtype=torch.float32).contiguous()
+            assert dz.shape[0] == steps * C and u.numel() == steps * C
+        flags = self._mh_glm_flags(dynamic, lag)
+        sync = None
+        if flags & _lib.MH_DYNAMIC_BATCH:   # per-step batch counters, zero at the launch; last word = error flag
+            sync = torch.zeros(int(self._lib.nnest_mh_sync_words(steps)), dtype=torch.int64, device=dev)
+        t_std, t_mean, _, _ = target_vectors('mh_steps', dev, t_std, t_mean, None, None, D=self.D)
+        with torch.cuda.device(dev):
+            lk, keep = glm_spec(like_glm, dev)   # (`keep`: the staged arrays, alive until the call has been enqueued)
+            _lib.check(fn(self._h, ctypes.byref(lk), _lib.ptr(t_std), _lib.ptr(t_mean), _lib.ptr(z), _lib.ptr(x), _lib.ptr(logl),
+                          float(loglstar), float(step_size), steps, C, flags, _lib.ptr(dz), _lib.ptr(u), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                          int(walker_offset), _lib.ptr(hx), _lib.ptr(hl), _lib.ptr(n_acc), _lib.ptr(n_call), _lib.ptr(scale_out),
+                          _lib.ptr(sync), _lib.current_stream(dev)))
+        return _MhResult(x=x, n_accept_word=n_acc, n_call=n_call, scale=scale_out, hist_x=hx, hist_logl=hl, sync=sync)
+
+    MH_GLM_WALKERS_PER_WORKGROUP = 4   # (scale_out_dev of the `mh_glm` entry: one float per workgroup)
+
+    def mh_glm_refusal(self, D=None, C=0, dynamic=False, lag=None):
+        """why `mh_steps` with a like_glm of dimension D (None: the flow's own) would refuse this flow (its shape), C walkers or this
+        step rule (the batch rule on a grid that is not proven resident) -- the library's own words (the family's `mh_glm_check`
+        entry; nothing is launched) --, or None where it is taken.  NotImplementedError for a family without such a kernel"""
+        fn = self._sym.get('mh_glm_check')
+        if fn is None or 'mh_glm' not in self._sym:
+            raise NotImplementedError('no fused Metropolis kernel for %s on a regression likelihood of user data' % type(self).__name__)
+        with torch.cuda.device(self.device):
+            rc = fn(self._h, self.D if D is None else int(D), int(C), self._mh_glm_flags(dynamic, lag))
+        if rc == _lib.NNEST_OK:
+            return None
+        msg = self._lib.nnest_hip_last_error()
+        return msg.decode() if msg else 'error %d' % rc
 
     def slice_steps(self, like_id, like_scale, z, logl, loglstar, width, steps, max_stepout=8, max_shrink=32, noise=None, seed=0,
                     walker_offset=0, history=False, like_params=None, form=None, like_glm=None, t_std=None, t_mean=None):
@@ -969,7 +1044,8 @@ class HipNVP(_PaddedVectors, _HipFlow):
                    mcmc_adapt_check='nnest_mcmc_adapt_check', mcmc_gdata='nnest_mcmc_gdata_steps',
                    mcmc_gdata_check='nnest_mcmc_gdata_check', mcmc_glm='nnest_mcmc_glm_steps',
                    mcmc_glm_check='nnest_mcmc_glm_check', slice_glm='nnest_slice_glm_steps',
-                   slice_glm_check='nnest_slice_glm_check', mcmc_glm_prior='nnest_mcmc_glm_prior_steps',
+                   slice_glm_check='nnest_slice_glm_check', mh_glm='nnest_mh_glm_steps', mh_glm_check='nnest_mh_glm_check',
+                   mcmc_glm_prior='nnest_mcmc_glm_prior_steps',
                    mcmc_glm_prior_check='nnest_mcmc_glm_prior_check', importance_glm='nnest_importance_glm_evidence',
                    importance_glm_check='nnest_importance_glm_check')
         self._h = ctypes.c_void_p()

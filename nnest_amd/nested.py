@@ -23,8 +23,11 @@ derived product -- is rewritten at most once per `chain_min_seconds` (default 30
 A regression likelihood of user data (likelihoods.GLMData) under mcmc_proposal='slice' and a transform x -> s * x runs its MCMC batches
 on the device: the fused slice kernels of that likelihood (nnest_slice_glm_steps, nnest_spline_slice_glm_steps) where they take the
 flow's shape, nnest_amd.slice_rounds with the device likelihood otherwise (`slice_route`: 'fused-glm' / 'rounds-glm').  The initial
-live points, the prior-rejection phase and the loops around the batches keep the host callable.  With mcmc_proposal='mh', or under
-a GaussianPrior (a Sampler's prior, not this class's unit box), a GLMData stays on the host protocol.
+live points, the prior-rejection phase and the loops around the batches keep the host callable.  With mcmc_proposal='mh' (the default)
+the batches run the fused Metropolis kernels of that likelihood (nnest_mh_glm_steps, nnest_spline_mh_glm_steps; `mh_route`:
+'fused-glm') where the flow has them and they take its shape -- the RealNVP of the one-walker-per-wave shapes, the spline flow's team
+tile --, the host protocol otherwise ('host'), as with several MPI ranks.  Under a GaussianPrior (a Sampler's prior, not this class's
+unit box) a GLMData stays on the host protocol.
 """
 import csv
 import glob
@@ -459,14 +462,14 @@ class NestedSampler(Sampler):
                     if primary:
                         idx = np.random.randint(low=0, high=N, size=C)      # nested.py:405
                         ctl[:-1] = np.resize(idx, per * self.mpi_size)
-                        if self._fused_like_id is not None or self.mcmc_proposal == 'slice':   # only the HIP kernels' noise streams consume a seed
+                        if self._fused_like_id is not None or self._mh_glm is not None or self.mcmc_proposal == 'slice':   # only the HIP kernels' noise streams consume a seed
                             ctl[-1] = self._next_seed() & 0x7FFFFFFFFFFFFFFF
                     ctl = self._broadcast(ctl)
                     lo = self.mpi_rank * per
                     my = ctl[lo:lo + per]
                     kw = dict(init_samples=active_u[my, :], init_loglikes=active_logl[my], loglstar=st.loglstar,
                               walker_offset=lo, seed=int(ctl[-1]), form=self._pinned_form(C, dynamic))
-                    if (self._fused_like_id is not None or self._slice_glm is not None) and nd == 0:
+                    if (self._fused_like_id is not None or self._slice_glm is not None or self._mh_glm is not None) and nd == 0:
                         ends, scale, nc = self._mcmc_endpoints_fused(mcmc_steps, step_size, dynamic, **kw)
                     else:
                         s_x, _lat, s_d, s_l, scale, nc = self._mcmc_sample(
@@ -768,7 +771,7 @@ class NestedSampler(Sampler):
                     if primary:
                         idx = np.random.randint(low=0, high=N, size=C)      # nested.py:405
                         ctl[:-1] = np.resize(idx, per * self.mpi_size)
-                        if self._fused_like_id is not None or self.mcmc_proposal == 'slice':   # only the HIP kernels' noise streams consume a seed
+                        if self._fused_like_id is not None or self._mh_glm is not None or self.mcmc_proposal == 'slice':   # only the HIP kernels' noise streams consume a seed
                             ctl[-1] = self._next_seed() & 0x7FFFFFFFFFFFFFFF
                     ctl = self._broadcast(ctl)
                     lo = self.mpi_rank * per
@@ -779,7 +782,7 @@ class NestedSampler(Sampler):
                     # (+ derived): one row [x_S | logL_S | moved | derived_S] per chain, all-gathered over the ranks (C2) -- on
                     # device memory when the whole batch ran inside the HIP kernel
                     # (or, under the slice proposal, on a regression likelihood of user data: Sampler._slice_glm)
-                    if (self._fused_like_id is not None or self._slice_glm is not None) and nd == 0:
+                    if (self._fused_like_id is not None or self._slice_glm is not None or self._mh_glm is not None) and nd == 0:
                         ends, scale, nc = self._mcmc_endpoints_fused(mcmc_steps, step_size, mcmc_dynamic_step_size, **kw)
                     else:
                         s_x, _lat, s_d, s_l, scale, nc = self._mcmc_sample(

@@ -167,6 +167,12 @@ class Sampler(object):
         self.slice_route = None   # 'fused-glm' | 'rounds-glm' | 'fused' | 'rounds' | 'host': what the last slice batch ran, logged once
         if fused and mcmc_proposal == 'slice' and self._fused_like_id is None and getattr(self.trainer, 'netG', None) is not None:
             self._slice_glm, _ = self._device_target(unit_box_on_x=True, entry='slice_glm')
+        # the Metropolis proposal on such a likelihood (nnest_mh_glm_steps, nnest_spline_mh_glm_steps): its device target, or None
+        self._mh_glm = None
+        self.mh_route = None   # 'fused-glm' | 'fused' | 'host': what the last Metropolis batch ran, logged once
+        if (fused and mcmc_proposal == 'mh' and self._fused_like_id is None and getattr(self.trainer, 'netG', None) is not None
+                and getattr(self, 'mpi_size', 1) <= 1):
+            self._mh_glm, _ = self._device_target(unit_box_on_x=True, entry='mh_glm')
 
     # ---- the user's callables behind shape checks (sampler.py:97-163) ----------------------------------------------
     def _rows(self, x):
@@ -407,9 +413,20 @@ class Sampler(object):
         return (res['hist_x'].cpu().numpy(), res['hist_z'].cpu().numpy(), derived, res['hist_logl'].cpu().numpy(), float(step_size),
                 ncall + ncall0)
 
+    def _note_mh_route(self, route):
+        """`mh_route`: what the last Metropolis batch ran; logged when it changes"""
+        if route != self.mh_route:
+            self.mh_route = route
+            if self.single_or_primary_process:
+                self.logger.info('Metropolis proposal route [%s]' % route)
+
     def _fused_launch(self, mcmc_steps, step_size, dynamic, init_samples, init_loglikes, loglstar, walker_offset, seed,
-                      form=None):
-        """One K4 launch from live points: returns (res, z0, z, logl) device-side (no host copies)."""
+                      form=None, target=None):
+        """One K4 launch from live points: returns (res, z0, z, logl) device-side (no host copies).  target: None -- the known
+        likelihood (`_fused_like_id`, `_linear_scale`, `_fused_like_params`); a DeviceTarget with a like_glm (`_mh_glm`) -- the
+        kernels of that likelihood (netG.mh_steps(like_glm=...)), with the same lag choice and the same fallback ladder; where the
+        batch rule is refused and the flow has no per-tile rule (the NVP: one walker per wave) the result is None: the caller's
+        batches go back to the host protocol."""
         netG = self.trainer.netG
         z, _ = netG.forward(init_samples)                               # sampler.py:264
         logl = torch.as_tensor(np.ascontiguousarray(init_loglikes, dtype=np.float64)).to(netG.device)
@@ -418,6 +435,11 @@ class Sampler(object):
                   history=self.mcmc_history or self.chain_stats, like_params=self._fused_like_params, form=form)
         star = None if loglstar is None else float(loglstar)
         args = (self._fused_like_id, self._linear_scale, z, logl, star, float(step_size), int(mcmc_steps))
+        if target is not None:
+            tk = target.launch_kwargs(netG.device)
+            kw = dict(seed=kw['seed'], walker_offset=walker_offset, history=kw['history'], like_glm=tk['like_glm'], t_std=tk['t_std'],
+                      t_mean=tk['t_mean'])
+            args = (None, 1.0) + args[2:]
         # dynamic: the reference's rule over the whole batch (sampler.py:422-431), `mcmc_step_lag` steps behind (0 = exactly
         # the reference; the default keeps the grid-wide wait off the step); populations too large for a
         # resident grid fall back to the per-16-walker rule
@@ -425,8 +447,23 @@ class Sampler(object):
         lag = getattr(self, 'mcmc_step_lag', None)
         if lag is None and int(mcmc_steps) < 100:
             lag = 0   # short chains: the lag would be a sizeable part of the launch, and the exact rule costs microseconds here
-        if getattr(self, 'mcmc_step_warm', None) is not None:
+        if getattr(self, 'mcmc_step_warm', None) is not None and target is None:
             kw['warm'] = int(self.mcmc_step_warm)
+        if target is not None:
+            # the same ladder in the `mh_glm` entries' terms: the `_check` entry is asked, nothing is launched and refused.  The spline
+            # flow falls back to the per-tile rule; the NVP has none (one walker per wave): its batches go back to the host protocol
+            if mode == 'batch':
+                why = netG.mh_glm_refusal(self.x_dim, z.shape[0], 'batch', lag)
+                if why is not None:
+                    self._batch_rule_ok = False
+                    mode = 'group'
+                    per_tile = netG.mh_glm_refusal(self.x_dim, z.shape[0], 'group', None) is None
+                    self.logger.warning('batch-wide step rule not available for %d walkers (%s); using %s' % (
+                        z.shape[0], why, 'the per-group rule' if per_tile else 'the host protocol'))
+            if mode == 'group' and netG.mh_glm_refusal(self.x_dim, z.shape[0], 'group', None) is not None:
+                self._mh_glm = None
+                return None, z0, z, logl
+            return netG.mh_steps(*args, dynamic=mode, lag=lag, **kw), z0, z, logl
         try:
             res = netG.mh_steps(*args, dynamic=mode, lag=lag, **kw)
         except _lib.NnestHipError as e:
@@ -465,6 +502,7 @@ class Sampler(object):
                                               walker_offset, seed, form)
         ncall = int(res['n_call'].sum().item())
         nacc = int(res['n_accept'].sum().item())
+        self._note_mh_route('fused')
         netG.check_sync(res)
         self.total_calls += ncall
         self.total_accepted += nacc
@@ -504,8 +542,12 @@ class Sampler(object):
             self._chain_hist = res['hist_x'] if self.chain_stats else None
             ends = torch.cat([res['x'].double(), logl[:, None], res['moved'][:, None].double()], dim=1)
             return ends, float(step_size), ncall
+        target = self._mh_glm if self._fused_like_id is None else None
         res, z0, z, logl = self._fused_launch(mcmc_steps, step_size, dynamic, init_samples, init_loglikes, loglstar,
-                                              walker_offset, seed, form)
+                                              walker_offset, seed, None if target is not None else form, target=target)
+        if res is None:   # (a regression likelihood of user data whose batch rule was refused, on a flow without a per-tile rule)
+            return self._mcmc_endpoints_host(mcmc_steps, step_size, dynamic, init_samples, init_loglikes, loglstar)
+        self._note_mh_route('fused-glm' if target is not None else 'fused')
         # "every coordinate moved" (nested.py:432: samples[:, 0] != samples[:, -1] in every dimension): the kernel's own test of the
         # chain's last x against its first x = f^-1(z_0), coordinate by coordinate (NNEST_MH_ALL_MOVED; round 4 took "accepted at
         # least once" for it, which differs once a proposal is so small that a coordinate of x does not change in float32)
@@ -520,6 +562,15 @@ class Sampler(object):
         self.total_rejected += C * int(mcmc_steps) - nacc
         scale = float(res['scale'].mean().item()) if dynamic else float(step_size)
         return ends, scale, ncall
+
+    def _mcmc_endpoints_host(self, mcmc_steps, step_size, dynamic, init_samples, init_loglikes, loglstar):
+        """`_mcmc_endpoints_fused`'s return from the host protocol (`_mcmc_sample_host`), for a batch the kernels refused: ends
+        [C, D + 2] float64 on the flow's device -- the last x, the last logL, every coordinate moved (nested.py:432)"""
+        s_x, _lat, _d, s_l, scale, nc = self._mcmc_sample_host(mcmc_steps, step_size, dynamic, init_samples.shape[0], init_samples,
+                                                               init_loglikes, None, loglstar, 100, 1)
+        moved = np.all(s_x[:, 0, :] != s_x[:, -1, :], axis=1)
+        ends = np.concatenate([s_x[:, -1, :].astype(np.float64), s_l[:, -1, None], moved[:, None].astype(np.float64)], axis=1)
+        return torch.as_tensor(ends, device=self.trainer.netG.device), scale, nc
 
     class _StepScale(object):
         """the proposal scale under the reference's adaptation rule (sampler.py:422-431): a step in which more than half of
@@ -557,6 +608,7 @@ class Sampler(object):
                           loglstar, max_start_tries, prior_volume_steps):
         """The reference's step loop (sampler.py:246-463) with the flow passes on the GPU and the user's
         likelihood / prior callables on the host: the path for likelihoods the kernels do not know."""
+        self._note_mh_route('host')
         tr = self.trainer
         tr.netG.eval()
         ncall = 0
@@ -837,7 +889,8 @@ class Sampler(object):
         entries (GDATA_ENTRIES) where the flow's `mcmc_gdata` entry is bound and takes the flow (`mcmc_gdata_refusal`) and the
         descriptor agrees with the host callable (`_probe_agrees_gdata`): the target then has like_id None and the data.  Likewise
         a likelihood with a `hip_like_glm` (likelihoods.GLMData): the flow's `mcmc_glm` entry, `mcmc_glm_refusal`,
-        `_probe_agrees_glm`.  Entry 'slice_glm' (the NestedSampler's slice proposal; `unit_box_on_x` goes with it) takes such a
+        `_probe_agrees_glm`.  Entry 'mh_glm' (the NestedSampler's Metropolis proposal) takes such a likelihood under mcmc_proposal='mh',
+        the unit box on x and x -> s * x where the flow binds `mh_glm` and takes the shape (`mh_glm_refusal`).  Entry 'slice_glm' (the NestedSampler's slice proposal; `unit_box_on_x` goes with it) takes such a
         likelihood, and nothing else, under mcmc_proposal='slice', the unit box on x and x -> s * x, with any flow and fast/slow
         parameters too: `_slice_batch` chooses between the fused kernel and the round driver.  Beside such a likelihood, and only there, a priors.GaussianPrior on T(x) whose `__call__` is its own
         is taken where the flow binds `mcmc_glm_prior` and takes the shape (`mcmc_glm_prior_refusal`) and the prior's
@@ -872,11 +925,20 @@ class Sampler(object):
             glm_evidence = proper and 'importance_glm' in getattr(netG, '_sym', ())
         # (the slice proposal on a regression: the NestedSampler's prior, the unit box on x under x -> s * x.  Any flow: the fused kernel
         # or the round driver is `_slice_batch`'s choice, batch by batch)
-        glm_slice = (entry == 'slice_glm' and like_glm is not None and self.mcmc_proposal == 'slice' and self._unit_box_on_x()
+        # (entry 'mh_glm': the same under mcmc_proposal='mh', with a flow that binds the `mh_glm` entry and whose shape it takes --
+        # there is no round driver behind the Metropolis proposal; population and step rule are `_fused_launch`'s, batch by batch)
+        nested_glm = {'slice_glm': 'slice', 'mh_glm': 'mh'}.get(entry)
+        glm_slice = (nested_glm is not None and like_glm is not None and self.mcmc_proposal == nested_glm and self._unit_box_on_x()
                      and self._linear_scale is not None)
-        if entry == 'slice_glm' and not glm_slice:
-            return None, ("anything but mcmc_proposal='slice' on a likelihood with a hip_like_glm (likelihoods.GLMData) under the unit box on x and "
-                          "x -> s * x")
+        if nested_glm is not None and not glm_slice:
+            return None, ("anything but mcmc_proposal='%s' on a likelihood with a hip_like_glm (likelihoods.GLMData) under the unit box on x and "
+                          "x -> s * x" % nested_glm)
+        if entry == 'mh_glm':
+            if 'mh_glm' not in getattr(netG, '_sym', ()):
+                return None, 'the flow %s (no fused Metropolis kernel on a regression likelihood of user data)' % type(netG).__name__
+            why = netG.mh_glm_refusal(np.shape(like_glm['at'])[0])
+            if why is not None:
+                return None, 'the flow %s: %s' % (type(netG).__name__, why)
         if like_glm is not None and not glm_evidence and not glm_slice and not (entry in self.GDATA_ENTRIES and 'mcmc_glm' in getattr(netG, '_sym', ())):
             like_glm = None
         if like_id is None and like_data is None and like_glm is None:
@@ -923,7 +985,7 @@ class Sampler(object):
             box = (prior.minimum, prior.maximum) if ok else None
         params = tuple(getattr(like, 'hip_like_params', ()) or ())
         if like_glm is not None:
-            if affine is None or box is None or not self._probe_agrees_glm(like_glm, affine, warn='slice: ' if glm_slice else 'mcmc: '):
+            if affine is None or box is None or not self._probe_agrees_glm(like_glm, affine, warn=('%s: ' % nested_glm) if glm_slice else 'mcmc: '):
                 return None, refused
             if prior_gauss is not None and (box != (None, None) or not self._probe_agrees_gauss_prior(prior_gauss, affine, warn='mcmc: ')):
                 return None, refused
@@ -943,6 +1005,7 @@ class Sampler(object):
         self._linear_scale = None   # (the Metropolis kernels only know x -> s * x)
         self._fused_like_id = None
         self._slice_glm = None
+        self._mh_glm = None
 
     # ---- importance-sampled evidence from the trained flow (build-defined: the reference has none) ---------------------------------
     IMPORTANCE_CHUNK = 1 << 22   # samples per launch when nothing per sample comes back

@@ -42,6 +42,7 @@ class HipSpline(_PaddedVectors, _HipFlow):
                    mcmc_gdata='nnest_spline_mcmc_gdata_steps', mcmc_gdata_check='nnest_spline_mcmc_gdata_check',
                    mcmc_glm='nnest_spline_mcmc_glm_steps', mcmc_glm_check='nnest_spline_mcmc_glm_check',
                    slice_glm='nnest_spline_slice_glm_steps', slice_glm_check='nnest_spline_slice_glm_check',
+                   mh_glm='nnest_spline_mh_glm_steps', mh_glm_check='nnest_spline_mh_glm_check',
                    mcmc_glm_prior='nnest_spline_mcmc_glm_prior_steps', mcmc_glm_prior_check='nnest_spline_mcmc_glm_prior_check',
                    importance_glm='nnest_spline_importance_glm_evidence', importance_glm_check='nnest_spline_importance_glm_check')
         self._h = ctypes.c_void_p()
@@ -88,6 +89,8 @@ class HipSpline(_PaddedVectors, _HipFlow):
 
     def _slice_form_args(self, form):
         return (self._slice_flags(form),)
+
+    MH_GLM_WALKERS_PER_WORKGROUP = 16   # (nnest_spline_mh_glm_steps: the team tile, one scale_out entry per 16 walkers)
 
     def _slice_glm_form_args(self, form):
         """nnest_spline_slice_glm_steps takes no flags word: the team tile is its only form (glm_tile_loglike needs the whole workgroup)"""
